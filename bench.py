@@ -6,7 +6,7 @@ A "step" is one Levenberg-Marquardt outer iteration of the hot path: damped solv
 sweep(s) (src/iterators.jl:139-172) followed by the gradient sweep that builds the next linear system
 (src/optimize.jl:167-170).  Inputs are resident in HBM before the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 For N > 1 the driver launches this file under torch.distributed.run (one rank per GPU, RCCL).
 
 Prints ONE JSON line on rank 0 with the contract fields plus "roofline" (accumulate sweep vs the HBM roof,
@@ -142,6 +142,32 @@ def oracle_loop_fixture(workload, steps):
         return {"oracle_trials": None, "oracle_final_cost": None}
 
 
+def loop_outputs(ls, loop):
+    """What optimize() hands its caller after the loop's last iteration (OuterLoop.finish, src/optimize.jl:173-176): the best variables and
+    the start / best cost.  The variables are read without the swap finish() makes, so the context is left as the timed loop left it."""
+    from nllssolver_jl_amd._capi import VARS_CURRENT, VARS_BEST
+    best = not (loop.data.bestcost >= loop.cost)
+    return {"variables": ls.variables(VARS_BEST if best else VARS_CURRENT),
+            "cost": np.array([loop.data.startcost, loop.data.bestcost], dtype=np.float64)}
+
+
+def dump_outputs(outdir, arrays, budget=64 * 2 ** 20):
+    """DIR/<name>.npy in float64, flattened.  The arrays share the budget smallest first; one larger than its share is replaced by a fixed
+    sample of its entries (seeded, sorted indices: the same entries for the same size on every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    flat = {name: np.ascontiguousarray(a, dtype=np.float64).ravel() for name, a in arrays.items()}
+    written = {}
+    for i, name in enumerate(sorted(flat, key=lambda k: flat[k].size)):
+        a = flat[name]; total = a.size
+        share = (budget - 1024 * len(flat)) // (len(flat) - i)          # (1 KiB per file for the .npy header)
+        if a.nbytes > share:
+            a = a[np.sort(np.random.default_rng(0).choice(total, share // a.itemsize, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        budget -= a.nbytes
+        written[name] = {"entries": int(a.size), "of": int(total)}
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -161,7 +187,11 @@ def main():
     ap.add_argument("--cpu-iters", type=int, default=10, help="LM iterations of the CPU oracle behind cpu_baseline (about 12 s of one core at BASELINE config 4)")
     ap.add_argument("--repeats", type=int, default=7, help="the (W warm-up + K timed) loop is run this many times from the same start; value = the MEDIAN run")
     ap.add_argument("--die-rank", type=int, default=-1, help=argparse.SUPPRESS)     # test hook: this rank exits non-zero in the middle of the timed loop
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps (e.g. into bench_outputs/, which git ignores), write what the last timed run returns to a caller (best variables, start / best cost) as DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -281,6 +311,8 @@ def main():
             os._exit(17)
         loop_r, elapsed_r = timed_loop(ls, problem, start_vars, profile=(rep == max(1, args.repeats) - 1))
         runs.append((elapsed_r, loop_r))
+    # read back before anything else runs on the context (every rank: the sharded variables are gathered collectively)
+    outputs = loop_outputs(ls, runs[-1][1]) if args.dump_outputs else None
     stats_loop = ls.ctx.solve_stats()
     mf_loop = world == 1 and args.path == "default" and stats_loop.get("mf_trials", 0) > 0      # did the timed loop run matrix-free trials?
     # `roofline` describes the MATERIALISING accumulate launch (north_star names it).  Where the timed loop ran matrix-free it holds no such launch: one more loop of the same K
@@ -570,6 +602,8 @@ def main():
             out["strong_scaling_10x"] = strong
         if phases:
             out["phases_measured"] = phases
+        if outputs is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "run": "the last of the timed runs", "arrays": dump_outputs(args.dump_outputs, outputs)}
         if world > 1 and args.workload == "ba_1kx100k":
             out["predicted"] = predicted_scaling(world)
         sys.stdout.flush(); os.dup2(saved_stdout, 1)
