@@ -242,7 +242,12 @@ int  nlls_copy_variables(nlls_ctx* ctx, int32_t dst, int32_t src);/* deepcopy, s
  *           src/optimize.jl:118,167-170 -> src/cost.jl:29-54, src/residual.jl:57-111,
  *           src/linearsystem.jl:132-175.  Evaluated at NLLS_VARS_CURRENT.  Resets the damping.
  * cost_out == NULL: the cost is not wanted (the outer loop discards it between iterations, src/optimize.jl:167-170):
- * the sweep is only enqueued -- no cost reduction, no synchronisation; the next synchronising call waits for it. */
+ * the sweep is only enqueued -- no cost reduction, no synchronisation; the next synchronising call waits for it.
+ * The linearisation is that of the values NLLS_VARS_CURRENT holds at this call, whatever is written to them afterwards: a trial
+ * after nlls_set_variables / nlls_copy_variables / nlls_retract into CURRENT (without a sweep between) solves with A and b of the
+ * old values and retracts from the new ones -- also where the sweep is deferred or the trial is matrix-free.  One exception, the
+ * same on every path: once an nlls_lm_trial has enqueued its look-ahead sweep (A and b then hold the linearisation at the trial
+ * point), a trial from a CURRENT written after it is linearised at the new values. */
 int  nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out);
 /* replaces: cost(vars, costs)  src/cost.jl:10-13, src/residual.jl:49-55 */
 int  nlls_sweep_cost(nlls_ctx* ctx, int32_t which, double* cost_out);

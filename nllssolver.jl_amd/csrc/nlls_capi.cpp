@@ -48,15 +48,24 @@ int ensure_grad(nlls_ctx* ctx, int level) {
 }
 int ensure_grad_current(nlls_ctx* ctx) { return ensure_grad(ctx, 2); }
 // a variable set is about to be written: a look-ahead sweep of it is stale, and so is a linearisation at it that is not (fully) formed yet
-void spec_note_write(nlls_ctx* ctx, int32_t which) {
-    if (ctx->vars_slot[which] != ctx->grad_phys) return;
+int spec_note_write(nlls_ctx* ctx, int32_t which) {
+    ctx->mf_step = false;                                       // (the last matrix-free trial's point and cost are of the sets as they were: its tail is not finished again)
+    if (ctx->vars_slot[which] != ctx->grad_phys) return NLLS_OK;
     if (ctx->spec_pending) ctx->spec_stale = true;
+    else if (which == NLLS_VARS_CURRENT && ctx->have_grad && ctx->mf_ok) {
+        // CURRENT under the linearisation of the last nlls_sweep_gradhess (include/nlls_amd.h): the trial that follows takes A and b of the values BEFORE this write. What the
+        // matrix-free path has not formed yet is formed now, in stream order ahead of the write, and its trial -- the eliminated rows evaluated at CURRENT -- is off until the
+        // next sweep.  (No LM loop gets here: it writes NEXT, swaps, and sweeps again.)
+        if (ctx->grad_level < 2) { const double lam = ctx->lambda; TRY(enqueue_sweep_gradhess(ctx, false, NLLS_VARS_CURRENT, 0)); ctx->lambda = lam; ctx->solved = false; }
+        ctx->mf_stale_point = true;
+    }
     else if (ctx->grad_level < 2) ctx->grad_level = 0;          // (what is formed on demand would be formed at the NEW values: the caller sweeps again after writing CURRENT -- every iterator does)
+    return NLLS_OK;
 }
 // phase events (nlls_ctx::phase_on): record event k on the stream
 void phase_mark(nlls_ctx* ctx, int k) { if (ctx->phase_on && (size_t)k < ctx->phase_ev.size()) (void)hipEventRecord(ctx->phase_ev[k], ctx->stream); }
 // is this trial matrix-free?  (nlls_ctx::mf_ok: the structure qualifies; mf_on: not switched off; the trial starts at CURRENT, one rank, no collective route)
-bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->mf_on && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
+bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->mf_on && !ctx->mf_stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
 }  // namespace
 
 extern "C" {
@@ -213,7 +222,7 @@ int nlls_get_bsm_index(const nlls_ctx* ctx, int64_t* colptr, int64_t* rowval, in
 
 int nlls_set_variables(nlls_ctx* ctx, int32_t which, const double* packed) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(which) || !packed) return NLLS_ERR_INVALID_ARG;
-    spec_note_write(ctx, which);
+    TRY(spec_note_write(ctx, which));
     if (which == NLLS_VARS_CURRENT) { ctx->sweeps_since_set = 0; ctx->tb_prev_end = 0.0; }         // (a new starting point: its first trial gets no look-ahead sweep, see nlls_sweep_gradhess)
     HIPCHK(hipMemcpyAsync(vars_ptr(ctx, which), packed, sizeof(double) * ctx->info.var_storage, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -234,7 +243,7 @@ int nlls_swap_variables(nlls_ctx* ctx, int32_t a, int32_t b) { NLLS_API_BEGIN
 }
 int nlls_copy_variables(nlls_ctx* ctx, int32_t dst, int32_t src) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(dst) || !valid_set(src)) return NLLS_ERR_INVALID_ARG;
-    if (dst != src) spec_note_write(ctx, dst);
+    if (dst != src) TRY(spec_note_write(ctx, dst));
     if (dst != src) HIPCHK(hipMemcpyAsync(vars_ptr(ctx, dst), vars_ptr(ctx, src), sizeof(double) * ctx->info.var_storage, hipMemcpyDeviceToDevice, ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
@@ -258,6 +267,7 @@ int nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out) { NLLS_API_BEGIN
     //  (1e-6 of the largest diagonal entry, src/iterators.jl:131-137) is the one guess of the loop that is routinely rejected -- five times in a row at BASELINE config 5 --,
     //  and a look-ahead behind it is a sweep thrown away plus the current point swept again)
     ctx->spec_armed = ctx->sweeps_since_set >= 1; ctx->sweeps_since_set++;
+    ctx->mf_stale_point = false;                 // (a linearisation at CURRENT as it is now: the matrix-free trial applies again)
     if (ctx->spec_pending) {
         const bool hit = !cost_out && !ctx->spec_stale && ctx->grad_phys == ctx->vars_slot[NLLS_VARS_CURRENT];
         ctx->spec_pending = false; ctx->spec_stale = false;
@@ -565,7 +575,7 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
     HIPCHK(d_groups.upload(gbuf));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->have_grad = false; ctx->solved = false; ctx->step_cached = false; ctx->tE_valid = false;   // the variables change under the linear system
-    spec_note_write(ctx, NLLS_VARS_CURRENT); ctx->spec_pending = false; ctx->spec_stale = false; ctx->grad_level = 0;   // (... and under a look-ahead sweep of this very set: its A and b are of the point before the relaxation)
+    TRY(spec_note_write(ctx, NLLS_VARS_CURRENT)); ctx->spec_pending = false; ctx->spec_stale = false; ctx->grad_level = 0;   // (... and under a look-ahead sweep of this very set: its A and b are of the point before the relaxation)
     if (nloc > 0) TRY(enqueue_optimize_singles(ctx, nloc, d_sel.p, d_cptr.p, d_cgroup.p, d_cidx.p, d_cslot.p, d_groups.p, iterator, maxiters, maxfails, reldcost, absdcost, dstep, d_iters.p));
     if (!sharded) {
         if (iters_out) HIPCHK(hipMemcpyAsync(iters_out, d_iters.p, sizeof(int64_t) * nsel, hipMemcpyDeviceToHost, ctx->stream));      // (unsharded: nloc == nsel, the caller's order)
@@ -633,7 +643,7 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
 }
 int nlls_set_step(nlls_ctx* ctx, const double* x) { NLLS_API_BEGIN
     NEED_READY(); if (!x) return NLLS_ERR_INVALID_ARG;
-    ctx->tE_valid = false; ctx->step_cached = false;   // the step is no longer the one the last solve produced
+    ctx->tE_valid = false; ctx->step_cached = false; ctx->mf_step = false;   // the step is no longer the one the last solve produced (nor are the matrix-free trial's partials of it)
     HIPCHK(hipMemcpyAsync(ctx->x.p, x, sizeof(double) * ctx->info.ndof, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
@@ -669,7 +679,7 @@ int nlls_quadform(nlls_ctx* ctx, double* xHx_out, double* gx_out) { NLLS_API_BEG
 }
 int nlls_retract(nlls_ctx* ctx, int32_t to, int32_t from) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(to) || !valid_set(from) || to == from) return NLLS_ERR_INVALID_ARG;
-    spec_note_write(ctx, to);
+    TRY(spec_note_write(ctx, to));
     return enqueue_retract(ctx, to, from);
     NLLS_API_END(ctx)
 }
@@ -678,7 +688,7 @@ int nlls_retract(nlls_ctx* ctx, int32_t to, int32_t from) { NLLS_API_BEGIN
 //   nlls_sweep_cost / nlls_quadform / nlls_max_abs_diag / nlls_grad_* return this rank's PARTIAL values (the caller
 //   sums, or takes the max of, them over ranks); the *_local / *_finish pairs bracket the buffer reductions.
 int nlls_sweep_gradhess_local(nlls_ctx* ctx) { NLLS_API_BEGIN
-    NEED_READY(); ctx->spec_pending = false; ctx->spec_stale = false; TRY(enqueue_sweep_gradhess(ctx));
+    NEED_READY(); ctx->spec_pending = false; ctx->spec_stale = false; ctx->mf_stale_point = false; TRY(enqueue_sweep_gradhess(ctx));
     ctx->lambda = 0.0; ctx->have_grad = true; ctx->solved = false; ctx->reduced_summed = true;     // (the caller sums the reduce buffer)
     if (ctx->nranks > 1) TRY(enqueue_pack_reduce0(ctx));
     return NLLS_OK;                                  // enqueue only: the reduce buffer is complete in stream order

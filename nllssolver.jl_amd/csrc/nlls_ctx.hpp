@@ -270,6 +270,9 @@ struct nlls_ctx {
     // nlls_set_option(NLLS_OPT_MATERIALIZE): the round-5 path.
     bool mf_ok = false, mf_on = true; int mf_group = -1, mf_ps = -1;     // eligibility (build_mf), run-time switch, the cost group and its eliminated slot
     int grad_level = 0;                      // what A and b hold of the linearisation at grad_phys: 0 nothing, 1 the reduced rows, 2 everything
+    bool mf_stale_point = false;             // CURRENT was written after the linearisation the caller asked for: A and b hold it whole (formed before the write), the matrix-free
+                                             // trial -- which evaluates the eliminated rows at CURRENT -- stays off until the next nlls_sweep_gradhess
+    int mf_to_phys = -1, mf_from_phys = -1;  // (with mf_step: the physical variable slots that back-substitution retracted from / into)
     bool mf_step = false;                    // the last solve was matrix-free: its back-substitution launch has left the trial's cost and the step statistics as rows of partials in mf_q (mf_rows of them)
     nlls::DevBuf<double> mf_q; int mf_rows = 0; bool mf_fin_defer = false, mf_fin_pending = false;   // (the finishing workgroup may ride in the look-ahead sweep's launch)
     nlls::DevBuf<nlls::MfDesc> d_mf_desc; int64_t mf_nbig = 0; size_t mf_lds = 0; uint32_t mf_ecap = 0, mf_wsz = 0; bool mf_use = false;    // per-supernode partials of the step's quadratic form; dynamic LDS of the two launches

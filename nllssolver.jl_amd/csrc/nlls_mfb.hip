@@ -324,6 +324,7 @@ static int launch_mf_cost(nlls_ctx* c, const Group& G, int which) {
 }
 int enqueue_mf_sweep_cost(nlls_ctx* c, int which) {
     const Group& G = c->groups[c->mf_group];
+    c->mf_step = false;                       // (its rows of mf_q overwrite the last trial's: that trial's tail is no longer there to be finished)
     switch (G.res_kind) {
 #define X(K) case K: return c->mf_ps == 0 ? launch_mf_cost<K, 0>(c, G, which) : launch_mf_cost<K, 1>(c, G, which);
         NLLS_FOR_EACH_RES(X)

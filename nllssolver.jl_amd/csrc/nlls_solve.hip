@@ -1677,7 +1677,8 @@ int enqueue_post_solve(nlls_ctx* c, int retract_to, int retract_from, bool finis
 // what follows the solve in an LM trial (src/iterators.jl:155-163)
 int enqueue_lm_trial_tail(nlls_ctx* c, int to, int from) {
     // (matrix-free trial: the back-substitution launch has retracted, taken the trial point's cost and left the step statistics -- one finishing launch sums its rows)
-    if (c->mf_step) { c->retract_done = false; return enqueue_mf_trial_finish(c); }
+    // (... but only for the sets it retracted: the tail of the same step between other sets -- or after a set was written, which clears mf_step -- takes the path below)
+    if (c->mf_step) { c->retract_done = false; if (c->vars_slot[to] == c->mf_to_phys && c->vars_slot[from] == c->mf_from_phys) return enqueue_mf_trial_finish(c); c->mf_step = false; }
     if (!c->info.is_sparse) { int rc = enqueue_post_solve(c, to, from); if (rc != NLLS_OK) return rc; return enqueue_sweep_cost(c, to); }
     int rc; int64_t ncp = 0;
     if (c->retract_done) {
@@ -1949,7 +1950,7 @@ int enqueue_solve_finish(nlls_ctx* c) {
         if (c->mf_use) {
             if (!rt.on) { c->err = "matrix-free trial without the fused retraction"; return NLLS_ERR_NOT_READY; }
             const int rc = enqueue_mf_backsub(c, rt, write_red, zptr, zcount, nextra, nrestwg); if (rc != NLLS_OK) return rc;
-            c->tE_valid = false; c->mf_step = true; c->tiles_zeroed = true;
+            c->tE_valid = false; c->mf_step = true; c->tiles_zeroed = true; c->mf_to_phys = c->vars_slot[c->trial_to]; c->mf_from_phys = c->vars_slot[c->trial_from];
             return NLLS_OK;
         }
         c->mf_step = false;

@@ -208,7 +208,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     c->rank = c->shard_rank; c->nranks = c->shard_nranks; c->replicated = false;      // what nlls_set_shard asked for (a problem that does not shard falls back to replicas below)
     c->presharded = (flags & NLLS_FLAG_PRESHARDED) != 0 && c->nranks > 1;
     c->ready = false; c->solved = false; c->have_grad = false; c->lambda = 0; c->reduced_summed = true; c->n_stage0 = 0; c->n_lazy_trials = 0;
-    c->spec_pending = false; c->spec_stale = false; c->spec_armed = true; c->grad_phys = -1; c->grad_level = 0; c->sweeps_since_set = 0; c->dense_fin_pending = false; c->heavy_rows_zeroed = false; c->tail_zero_for_lookahead = false;   // (a re-upload starts from a clean look-ahead state)
+    c->mf_stale_point = false; c->spec_pending = false; c->spec_stale = false; c->spec_armed = true; c->grad_phys = -1; c->grad_level = 0; c->sweeps_since_set = 0; c->dense_fin_pending = false; c->heavy_rows_zeroed = false; c->tail_zero_for_lookahead = false;   // (a re-upload starts from a clean look-ahead state)
     { std::vector<HotItem> v; hot_set(c, v); for (HotItem& it : v) if (!*it.owned) { *it.pp = nullptr; *it.owned = true; } }   // what lived in the previous upload's arena is gone with it
     c->arena.release(); c->arena_pre.release();     // ... so release it NOW: a re-upload would otherwise hold two arenas (and every buffer once more) at its peak
     c->groups.clear();
@@ -607,7 +607,6 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
 int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const uint64_t* bi, int32_t flags) {
     c->mf_ok = false; c->mf_group = -1; c->mf_ps = -1; c->mf_step = false; c->mf_use = false; c->mf_q.release(); c->d_mf_desc.release(); c->mf_nbig = 0;
     for (Group& G : c->groups) { G.mf_data.release(); G.mf_voff.release(); }
-    { const char* e = getenv("NLLS_MATERIALIZE"); c->mf_on = !(e && e[0] == '1'); }
     // (the gather index of build_schur was built for this trial: without it -- or when the problem turns out not to qualify below -- it goes again, unless the flag asked for it)
     struct Drop { nlls_ctx* c; bool keep; ~Drop() { if (!c->mf_ok && !keep) { c->gather_ready = false; c->slab.release(); c->d_slab_off.release(); c->d_slab_groups.release(); c->d_gjobs.release(); c->d_gcons.release(); c->n_gjobs = 0; } } } drop{c, (flags & NLLS_FLAG_DETERMINISTIC) != 0};
     if ((flags & NLLS_FLAG_MATERIALIZE) || ngroups != 1 || c->nranks != 1 || !c->info.is_sparse || !c->gather_ready || c->h_slab_off.size() != c->h_elim_desc.size()) return NLLS_OK;
@@ -932,7 +931,7 @@ int build_schur(nlls_ctx* c, int32_t flags) {
         // back-substitution.  Runs are cut into balanced pieces of about nelim / 384 members, never below 24 (every piece pays its own flush of the packed image: 1830 atomics at
         // ten cameras) -- measured at config 3: 5903 (99 members per workgroup), 6346 (50), 6478 (25), 6330 (16), 5706 (8) LM iterations/s; configs 4 and 5 (991 / 500 runs)
         // lose with ANY cut (2848 -> 2667 / 2505 -> 2332 at 64) and are not cut.  NLLS_SUPERNODE_PIECE=n: the piece size by hand (A/B).
-        { static const int piece_env = [] { const char* e = getenv("NLLS_SUPERNODE_PIECE"); return e ? atoi(e) : 0; }();
+        { const char* pe = getenv("NLLS_SUPERNODE_PIECE"); const int piece_env = pe ? atoi(pe) : 0;      // (read per upload: an A/B switch that holds for the next upload, not the process)
           const int64_t total = (int64_t)ediag.size();
           const int64_t piece = piece_env > 0 ? piece_env : std::min<int64_t>(128, std::max<int64_t>(24, (total + 383) / 384));
           if (piece < 128 && c->nranks == 1) {

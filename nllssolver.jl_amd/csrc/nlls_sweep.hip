@@ -835,7 +835,7 @@ static int launch_gh(nlls_ctx* c, const Group& G, const double* vars, int64_t& p
 int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost, int which, int mode) {
     if (mode == 1 && (!c->mf_ok || want_cost)) mode = 0;
     c->grad_level = mode == 1 ? 1 : 2; if (mode == 1) c->mf_reduced_sweeps++; else c->full_sweeps++;
-    c->tE_valid = false; c->step_cached = false;  // A and b change: what the last solve kept of them is stale
+    c->tE_valid = false; c->step_cached = false; c->mf_step = false;  // A and b change: what the last solve kept of them is stale
     c->grad_phys = c->vars_slot[which];           // the variable set (physical slot) A and b are the linearisation of
     const double* vars = vars_ptr(c, which); int64_t pbase = 0;
     c->dense_slab_used = 0;

@@ -12,7 +12,7 @@ from nllssolver_jl_amd import kinds as K
 from nllssolver_jl_amd import synthetic, _capi
 from nllssolver_jl_amd.variables import contaminated_gaussian
 from oracle import oracle as O
-from tests.helpers import oracle_problem, blockindices
+from tests.helpers import oracle_problem, blockindices, longdouble_backward_error
 
 pytestmark = pytest.mark.gpu
 
@@ -23,6 +23,27 @@ RTOL_X = 1e-7     # solve: conditioning of the damped normal equations enters
 def rel(a, b):
     a, b = np.asarray(a), np.asarray(b)
     return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300)
+
+
+# normwise backward error of the device's damped step against the oracle's H and g (tests/helpers.longdouble_backward_error: long double, conditioning-free),
+# by the solver of the reduced system.  1e-13 for every solver: the largest values measured over the GPU suite's callers before this check existed were 1.3e-14
+# (small dense), 7.1e-15 (dense), 6.7e-15 (block cyclic reduction; the matrix-free trial included), 4.9e-15 (chain), 4.5e-15 (tile-sparse).
+ETA_BOUND = {"small": 1e-13, "dense": 1e-13, "bcr": 1e-13, "chain": 1e-13, "tile_sparse": 1e-13}
+
+
+def solver_of(info, st):
+    mode = ("small", "dense", "band", "tile_sparse")[info.solve_mode]
+    return ("bcr" if st["bcr_launches"] > 0 else "chain") if mode == "band" else mode
+
+
+def check_step(ctx, info, ols, A_ora, lam, x, where):
+    """after a damped solve or a trial: no pivot dropped, and the step backward-stable for the oracle's system"""
+    st = ctx.solve_stats()
+    assert st["dropped_pivots"] == 0, (where, st["dropped_pivots"])
+    eta = longdouble_backward_error(A_ora, ols.bsm_index() if info.is_sparse else None, ols.b, lam, x)
+    mode = solver_of(info, st)
+    print(f"ETA {mode} {where} ndof={info.ndof} {eta:.3e}")
+    assert eta <= ETA_BOUND[mode], f"{where}: backward error {eta:.3e} of the {mode} solve above {ETA_BOUND[mode]:.0e}"
 
 
 def check_problem(problem, unfixed=None, flags=0, lam_scale=1e-6, expect_sparse=None, expect_schur=None):
@@ -58,6 +79,7 @@ def check_problem(problem, unfixed=None, flags=0, lam_scale=1e-6, expect_sparse=
     lam = ols.max_abs_diag() * lam_scale
     ctx.damp(lam)
     x_gpu = ctx.solve(want_x=True)
+    check_step(ctx, info, ols, A_ora, lam, x_gpu, "solve")
     assert ols.solve(lam) == 0
     assert rel(x_gpu, ols.x) < RTOL_X, f"x mismatch {rel(x_gpu, ols.x)}"
     xHx, gx = ctx.quadform()
@@ -85,6 +107,7 @@ def check_problem(problem, unfixed=None, flags=0, lam_scale=1e-6, expect_sparse=
     # must give the same step, point, cost and statistics; and against the oracle's x the matrix-free step holds the tolerance of the materialised one.
     st = ctx.solve_stats(); x_trial = ctx.get_step()
     assert rel(x_trial, ols.x) < RTOL_X, f"trial step vs oracle {rel(x_trial, ols.x)}"
+    check_step(ctx, info, ols, A_ora, lam, x_trial, "mf trial" if st["mf_trials"] > 0 else "trial")
     if st["mf_trials"] > 0:
         v_mf = ctx.get_variables(_capi.VARS_NEXT)
         ctx.set_option(_capi.OPT_MATERIALIZE, 1)
@@ -710,6 +733,14 @@ def test_ab_switches_select_paths_that_still_match_the_oracle(env, monkeypatch):
     for flags in (0, _capi.FLAG_NO_BAND):
         info = check_problem(p, flags=flags, lam_scale=1e-4)
         assert info.has_schur and info.nreduced_dof == 2100 and info.solve_mode == (1 if flags else 2)
+    if "NLLS_SUPERNODE_PIECE" in env:            # the switch took effect: more supernodes in pieces of five than by default, no more in pieces of 128
+        piece, n = env["NLLS_SUPERNODE_PIECE"], {}
+        for v in (None, piece):
+            if v is None: monkeypatch.delenv("NLLS_SUPERNODE_PIECE")
+            else: monkeypatch.setenv("NLLS_SUPERNODE_PIECE", v)
+            ctx = _capi.Context(); ctx.upload(p.var_kind, p.var_dim, np.arange(1, p.nvariables + 1, dtype=np.uint64), p.groups())
+            n[v] = ctx.solve_stats()["elim_supernodes"]; ctx.close()
+        assert (n[piece] > n[None]) if piece == "5" else (n[piece] <= n[None]), n
 
 
 def _ba(ncam, npts, prop, seed, robust=None):

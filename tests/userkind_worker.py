@@ -91,6 +91,37 @@ def check(kind):
     print(f"user kind {kind}: cost {c_dev:.6e} = numpy, gradient = central differences, optimize -> {res.bestcost:.2e} in {res.niterations} iterations, optimizesingles ok")
 
 
+def check_matrix_free(percam):
+    """USER0 (DC = 7) through the matrix-free LM trial: 9 cameras per point (nd + 1 = 64, a full tile), 10 (nd + 1 = 71, TR = 5) -- against the same trial materialised
+    and the normwise backward error with the device's own H and g (no oracle has the kind); 11 (nd + 1 = 78): build_mf declines, the trial is the materialised one."""
+    from tests.helpers import longdouble_backward_error
+    p, vi, meas, truth, _ = make(USER0, 40, 1500, percam, seed=USER0)
+    start = truth + 1e-3 * np.random.default_rng(11).standard_normal(truth.size)
+    ctx = _capi.Context(0)
+    info = ctx.upload(p.var_kind, p.var_dim, np.arange(1, p.nvariables + 1, dtype=np.uint64), p.groups())
+    assert info.is_sparse and info.has_schur and info.solve_mode in (1, 2), (info.is_sparse, info.has_schur, info.solve_mode)
+    ctx.set_variables(start); c0 = ctx.sweep_gradhess()
+    H, g, idx = ctx.get_bsm_data(), ctx.get_grad(), ctx.bsm_index()             # (the materialised linearisation: what the step is held against)
+    lam = 1e-6 * ctx.max_abs_diag()
+    n0 = ctx.solve_stats()["mf_trials"]
+    c_mf = ctx.lm_trial(lam); st = ctx.solve_stats()
+    expect_mf = percam <= 10
+    assert st["mf_trials"] - n0 == (1 if expect_mf else 0), (percam, st["mf_trials"] - n0)
+    assert st["dropped_pivots"] == 0 and st["status"] == 0, st
+    x_mf, v_mf = ctx.get_step(), ctx.get_variables(_capi.VARS_NEXT)
+    eta = longdouble_backward_error(H, idx, g, lam, x_mf)
+    assert eta <= 1e-13, (percam, eta)
+    ctx.set_option(_capi.OPT_MATERIALIZE, 1)
+    c_mat = ctx.lm_trial(0.0)
+    assert ctx.solve_stats()["mf_trials"] == st["mf_trials"]
+    x_mat, v_mat = ctx.get_step(), ctx.get_variables(_capi.VARS_NEXT)
+    rx = np.max(np.abs(x_mf - x_mat)) / np.max(np.abs(x_mat)); rv = np.max(np.abs(v_mf - v_mat)) / np.max(np.abs(v_mat))
+    assert rx < 1e-9 and rv < 1e-11 and np.isclose(c_mf, c_mat, rtol=1e-9, atol=1e-13 * c0), (percam, rx, rv, c_mf, c_mat)
+    assert longdouble_backward_error(H, idx, g, lam, x_mat) <= 1e-13
+    ctx.close()
+    print(f"user kind {USER0}, {percam} cameras per point: {'matrix-free' if expect_mf else 'materialised (build_mf declines)'} trial, backward error {eta:.2e}, = materialised")
+
+
 def check_five_slots():
     """USER2: five variables per cost block (more than any built-in kind): a quartic fitted through 4000 noisy samples -- the optimum is the linear least-squares solution"""
     USER2 = 102
@@ -107,4 +138,5 @@ def check_five_slots():
 
 if __name__ == "__main__":
     check(USER0); check(USER1); check_five_slots()
+    for percam in (9, 10, 11): check_matrix_free(percam)
     print("user kinds ok")
