@@ -56,6 +56,26 @@ typedef struct nlls_ctx nlls_ctx;
 #define NLLS_VAR_DYNAMIC                6 /* DynamicVector{Float64}: a Euclidean vector of RUN-TIME length `dim` (1 .. NLLS_MAX_DYN_DIM):
                                              storage = dof = dim, update = v + delta (src/variable.jl); only under the DYN residual kinds */
 #define NLLS_MAX_DYN_DIM             4096
+/* USER variable kinds: the reference's variable blocks are any type with nvars() and update() (src/variable.jl; the Jacobian is taken through
+ * update(var, dualzeros), src/autodiff.jl:57-61).  Ids 100 .. 107 are reserved for kinds a user header adds at BUILD time, next to its user residual
+ * kinds (see NLLS_RES_USER0 below; variable and residual kinds are separate namespaces).  The header specialises
+ *     template <> struct nlls::Var<NLLS_VAR_USERk> {
+ *         static constexpr int STORAGE, DOF;             // 1 <= DOF <= STORAGE <= 12, DOF <= NLLS_MAX_BLOCK_SZ
+ *         template <class T> static NLLS_HD void update(const double* v, const T* d, T* out);   // out = update(v, d), generic in T like Res<>::eval
+ *     };
+ * and lists its kinds in NLLS_USER_VAR(X), as it lists its residual kinds in NLLS_USER_RES(X).  The Jacobian of a user residual w.r.t. such a
+ * variable is update() differentiated at d = 0 by dual numbers; the retraction of an LM step is update<double>.  A slot of a user residual names the
+ * kind in SK (its SD is the kind's DOF); the variable's var_dim is its DOF.  User variable kinds are never Euclidean for the solver: an eliminated
+ * one takes the materialised Schur elimination, a reduced one keeps the matrix-free LM trial.  They are refused in non-squared cost kinds.
+ * In a library built without a user header nlls_var_storage / nlls_var_dof return a negative value for these ids. */
+#define NLLS_VAR_USER0          100
+#define NLLS_VAR_USER1          101
+#define NLLS_VAR_USER2          102
+#define NLLS_VAR_USER3          103
+#define NLLS_VAR_USER4          104
+#define NLLS_VAR_USER5          105
+#define NLLS_VAR_USER6          106
+#define NLLS_VAR_USER7          107
 
 /* ---- residual kinds: computeresidual() bodies ----------------------------------------------- */
 #define NLLS_RES_BA_AFFINE        1 /* SimpleError2{2}: (pose[1:3].X, pose[4:6].X) - meas; vars (EUCL6, EUCL3);

@@ -59,6 +59,18 @@ int enqueue_lm_trial_tail(nlls_ctx* c, int to, int from);   // post-solve statis
 // dx: the variable's own step (its block of x)
 // DX(q) = component q of the variable's own step.  No staging arrays with run-time indices (they would live in scratch memory -- 1040 bytes per lane
 // of every kernel this is inlined into): Euclidean / dynamic vectors add in place, the other kinds have compile-time sizes.
+template <int K, class DXF>
+__device__ __forceinline__ void retract_user_var(uint32_t o, const double* __restrict__ from, double* __restrict__ to, DXF DX) {   // a user kind: update<double>, sizes of Var<K>
+    constexpr int ST = Var<K>::STORAGE, DF = Var<K>::DOF;
+    double in[ST], st[DF], out[ST];
+#pragma unroll
+    for (int q = 0; q < ST; ++q) in[q] = from[o + q];
+#pragma unroll
+    for (int q = 0; q < DF; ++q) st[q] = DX(q);
+    Var<K>::template update<double>(in, st, out);
+#pragma unroll
+    for (int q = 0; q < ST; ++q) to[o + q] = out[q];
+}
 template <class DXF>
 __device__ __forceinline__ void retract_var_fn(int k, int d, uint32_t o, const double* __restrict__ from, double* __restrict__ to, DXF DX) {
     switch (k) {
@@ -80,6 +92,9 @@ __device__ __forceinline__ void retract_var_fn(int k, int d, uint32_t o, const d
 #pragma unroll
         for (int q = 0; q < 12; ++q) to[o + q] = out[q];
         return; }
+#define X(K) case K: retract_user_var<K>(o, from, to, DX); return;
+    NLLS_USER_VAR(X)
+#undef X
     }
 }
 __device__ __forceinline__ void retract_var(int k, int d, uint32_t o, const double* __restrict__ from, const double* __restrict__ dx, double* __restrict__ to) {

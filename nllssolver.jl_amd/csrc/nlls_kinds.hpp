@@ -14,6 +14,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/nlls_amd.h"
 
@@ -62,11 +63,32 @@ template <int N> NLLS_DEV Dual<N> dexp(const Dual<N>& a) { Dual<N> r; r.v = exp(
 #pragma unroll
     for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * r.v; return r; }
 NLLS_DEV double dexp(double a) { return exp(a); }
+// (what a user variable's update() or a user residual needs beyond the above; d-prefixed like dexp, so that sqrt / sin / cos of a double keep meaning the library's)
+template <int N> NLLS_DEV Dual<N> dsqrt(const Dual<N>& a) { Dual<N> r; r.v = sqrt(a.v); const double h = 0.5 / r.v;
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * h; return r; }
+template <int N> NLLS_DEV Dual<N> dsin(const Dual<N>& a) { Dual<N> r; r.v = sin(a.v); const double c = cos(a.v);
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * c; return r; }
+template <int N> NLLS_DEV Dual<N> dcos(const Dual<N>& a) { Dual<N> r; r.v = cos(a.v); const double s = -sin(a.v);
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * s; return r; }
+template <int N> NLLS_DEV Dual<N> operator+(double c, const Dual<N>& a) { return a + c; }
+template <int N> NLLS_DEV Dual<N> operator-(const Dual<N>& a) { return 0.0 - a; }
+template <int N> NLLS_DEV Dual<N> operator/(const Dual<N>& a, double s) { return a * (1.0 / s); }
+template <int N> NLLS_DEV Dual<N> operator/(double c, const Dual<N>& a) { Dual<N> r; const double ia = 1.0 / a.v; r.v = c * ia; const double f = -r.v * ia;
+#pragma unroll
+    for (int i = 0; i < N; ++i) r.d[i] = a.d[i] * f; return r; }
+NLLS_HD double dsqrt(double a) { return sqrt(a); }
+NLLS_HD double dsin(double a) { return sin(a); }
+NLLS_HD double dcos(double a) { return cos(a); }
 NLLS_DEV double dval(double a) { return a; }
 template <int N> NLLS_DEV double dval(const Dual<N>& a) { return a.v; }
 NLLS_DEV double dpart(double, int) { return 0.0; }
 template <int N> NLLS_DEV double dpart(const Dual<N>& a, int i) { return a.d[i]; }
 
+template <class T> struct IsDual : std::false_type {};
+template <int N> struct IsDual<Dual<N>> : std::true_type {};
 template <class T> struct Lift;                // constant / seeded construction generic in T
 template <> struct Lift<double> {
     static NLLS_DEV double c(double v) { return v; }
@@ -158,20 +180,59 @@ template <int N> struct Lift<Dual2N<N>> {     // (seeding through a LINEAR retra
         for (int i = 0; i < N; ++i) if (i == k) r.g[i] = w; return r; }
 };
 
+constexpr int MAXST = 12;   // largest variable storage (POSE_SO3)
+constexpr int MAX_SLOTS = 10;   // variables per cost block: MAX_ARGS of the reference (src/NLLSsolver.jl:28).  The built-in kinds declare SK / SD with four entries; a kind with more slots (a user kind) declares as many as it has
+
+template <int KIND> struct Var;   // user variable kinds (include/nlls_amd.h, NLLS_VAR_USER0 .. 7): STORAGE, DOF, update<T>(v, d, out)
+template <int KIND> struct Res;
+}  // namespace nlls
+// user variable and residual kinds, added at BUILD time (include/nlls_amd.h, NLLS_VAR_USER0 .. 7, NLLS_RES_USER0 .. 7): the header specialises nlls::Var<> and
+// nlls::Res<> and defines NLLS_USER_VAR(X) / NLLS_USER_RES(X).  It sees the dual numbers above; everything below sees its kinds.
+// Pitfall of a user update(): it is differentiated at d = 0 by dual numbers, so its derivatives there must be finite -- sqrt(|w|^2) of a zero dual has NaN partials
+// (0.5 / 0 times 0): take a series branch for small arguments, as so3_exp does.
+#ifdef NLLS_USER_KINDS_HEADER
+#include NLLS_USER_KINDS_HEADER
+#endif
+#ifndef NLLS_USER_RES
+#define NLLS_USER_RES(X)
+#endif
+#ifndef NLLS_USER_VAR
+#define NLLS_USER_VAR(X)
+#endif
+namespace nlls {
+
 // ------------------------------------------------------------------------------------------------
 // variable kinds
 // ------------------------------------------------------------------------------------------------
+#define NLLS_USER_VAR_LIMITS(K) \
+    static_assert((K) >= NLLS_VAR_USER0 && (K) <= NLLS_VAR_USER7, "user variable kinds are NLLS_VAR_USER0 .. NLLS_VAR_USER7"); \
+    static_assert(1 <= Var<K>::DOF && Var<K>::DOF <= Var<K>::STORAGE && Var<K>::STORAGE <= MAXST, "a user variable kind needs 1 <= DOF <= STORAGE <= MAXST"); \
+    static_assert(Var<K>::DOF <= NLLS_MAX_BLOCK_SZ, "a user variable kind's DOF is at most NLLS_MAX_BLOCK_SZ");
+NLLS_USER_VAR(NLLS_USER_VAR_LIMITS)
+#undef NLLS_USER_VAR_LIMITS
+NLLS_HD constexpr int user_var_storage(int kind) {
+#define X(K) if (kind == K) return Var<K>::STORAGE;
+    NLLS_USER_VAR(X)
+#undef X
+    return -1;
+}
+NLLS_HD constexpr int user_var_dof(int kind) {
+#define X(K) if (kind == K) return Var<K>::DOF;
+    NLLS_USER_VAR(X)
+#undef X
+    return -1;
+}
 NLLS_HD constexpr int var_storage(int kind, int dim) {
     return (kind == NLLS_VAR_EUCLIDEAN || kind == NLLS_VAR_DYNAMIC) ? dim
          : (kind == NLLS_VAR_ZERO_TO_INF || kind == NLLS_VAR_ZERO_TO_ONE) ? 1
          : kind == NLLS_VAR_CONTAMINATED_GAUSSIAN ? 3
-         : kind == NLLS_VAR_POSE_SO3 ? 12 : -1;
+         : kind == NLLS_VAR_POSE_SO3 ? 12 : user_var_storage(kind);
 }
 NLLS_HD constexpr int var_dof(int kind, int dim) {   // nvars(): src/variable.jl:4,9,21,28; robustadaptive.jl:21
     return (kind == NLLS_VAR_EUCLIDEAN || kind == NLLS_VAR_DYNAMIC) ? dim
          : (kind == NLLS_VAR_ZERO_TO_INF || kind == NLLS_VAR_ZERO_TO_ONE) ? 1
          : kind == NLLS_VAR_CONTAMINATED_GAUSSIAN ? 3
-         : kind == NLLS_VAR_POSE_SO3 ? 6 : -1;
+         : kind == NLLS_VAR_POSE_SO3 ? 6 : user_var_dof(kind);
 }
 
 NLLS_DEV double zti_update(double v, double d) { return (v > 0 ? v : DBL_MIN) * exp(d); }          // variable.jl:22
@@ -212,6 +273,9 @@ NLLS_DEV void var_update_real(int kind, int dim, const double* in, const double*
             out[r + 3 * c] = s; }
         for (int i = 0; i < 3; ++i) out[9 + i] = in[9 + i] + d[3 + i];
         break; }
+#define X(K) case K: Var<K>::template update<double>(in, d, out); break;
+    NLLS_USER_VAR(X)
+#undef X
     }
 }
 // update(var, dualzeros) (src/autodiff.jl:57-61): storage of the variable as T, seeded from `start`
@@ -245,17 +309,27 @@ NLLS_DEV void var_load(const double* v, int start, T* out) {
         }
 #pragma unroll
         for (int i = 0; i < 3; ++i) out[9 + i] = L::seed(v[9 + i], start < 0 ? -1 : start + 3 + i);
+    } else {      // a user kind: update(v, dualzeros) (src/autodiff.jl:57-61) -- its value the variable as stored (what the reference's cost reads), its partials those of update() at d = 0
+        using V = Var<KIND>;
+        static_assert(std::is_same_v<T, double> || IsDual<T>::value,
+                      "user variable kinds are loaded as double or Dual<N> (not under the second-order duals of a non-squared cost kind)");
+        if constexpr (std::is_same_v<T, double>) {
+#pragma unroll
+            for (int i = 0; i < V::STORAGE; ++i) out[i] = v[i];
+        } else {
+            T d[V::DOF];
+#pragma unroll
+            for (int i = 0; i < V::DOF; ++i) d[i] = start < 0 ? L::c(0.0) : L::seed(0.0, start + i);
+            V::template update<T>(v, d, out);
+#pragma unroll
+            for (int i = 0; i < V::STORAGE; ++i) out[i].v = v[i];
+        }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // residual kinds: computeresidual() bodies, generic in the scalar type
 // ------------------------------------------------------------------------------------------------
-constexpr int MAXST = 12;   // largest variable storage (POSE_SO3)
-constexpr int MAX_SLOTS = 10;   // variables per cost block: MAX_ARGS of the reference (src/NLLSsolver.jl:28).  The built-in kinds declare SK / SD with four entries; a kind with more slots (a user kind) declares as many as it has
-
-template <int KIND> struct Res;
-
 template <> struct Res<NLLS_RES_BA_AFFINE> {   // test/optimizeba.jl:4 + src/residual.jl:13
     static constexpr int NDEPS = 2, M = 2, NDATA = 2, ADAPT = 0;
     static constexpr int SK[4] = {NLLS_VAR_EUCLIDEAN, NLLS_VAR_EUCLIDEAN, 0, 0};
@@ -368,15 +442,6 @@ template <> struct Res<NLLS_RES_SCALE_MIX> {   // standalone bounded scalars (sr
         const T s = sv[0][0], w = sv[1][0]; r[0] = s * (w * data[0] + (1.0 - w) * data[1]) - data[2];
     }
 };
-}  // namespace nlls
-// user residual kinds, added at BUILD time (include/nlls_amd.h, NLLS_RES_USER0 .. 7): the header specialises nlls::Res<> and defines NLLS_USER_RES(X)
-#ifdef NLLS_USER_KINDS_HEADER
-#include NLLS_USER_KINDS_HEADER
-#endif
-#ifndef NLLS_USER_RES
-#define NLLS_USER_RES(X)
-#endif
-namespace nlls {
 // kinds whose block is an AbstractCost (value / gradient / Hessian of computecost itself, src/autodiff.jl:144-159), not half a squared residual norm
 template <int KIND> constexpr bool is_cost_kind = (KIND == NLLS_COST_LINEAR3);
 

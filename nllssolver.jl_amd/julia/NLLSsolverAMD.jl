@@ -46,6 +46,13 @@ varkind(::ZeroToOneScalar) = (VAR_ZERO_TO_ONE, Int32(1));         pack!(out, v::
 varkind(::ContaminatedGaussian) = (VAR_CONTAMINATED_GAUSSIAN, Int32(3))
 pack!(out, v::ContaminatedGaussian) = append!(out, (v.invsigma1.val, v.invsigma2.val, v.w.val))
 varkind(v::NLLSsolver.DynamicVector{Float64}) = (VAR_DYNAMIC, Int32(length(v))); pack!(out, v::NLLSsolver.DynamicVector{Float64}) = append!(out, v)
+# USER variable kinds of a library built with a user header (include/nlls_amd.h, NLLS_VAR_USER0 .. 7; NLLS_AMD_LIB names that library): the Julia type maps to the id and its packed
+# storage, in the order nlls::Var<K>::update reads it, and back.  For the unit-quaternion pose of tests/user_kinds/manifold_ba.hpp (storage (qw, qx, qy, qz, t), dof 6):
+#   struct QuatPose; q::SVector{4, Float64}; t::SVector{3, Float64}; end          (NLLSsolver.nvars(::QuatPose) = 6, update as in the header)
+#   NLLSsolverAMD.varkind(::QuatPose) = (NLLSsolverAMD.VAR_USER0 + Int32(1), Int32(6))
+#   NLLSsolverAMD.pack!(out, v::QuatPose) = append!(out, v.q, v.t)
+#   NLLSsolverAMD.unpack(::QuatPose, p, o) = (QuatPose(SVector{4}(p[o+1:o+4]), SVector{3}(p[o+5:o+7])), o + 7)
+const VAR_USER0 = Int32(100)                                       # .. 107
 varkind(::Any) = nothing                                          # unregistered: decline
 
 robustspec(::NoRobust) = (ROBUST_NONE, (0.0, 0.0, 0.0, 0.0))

@@ -2,7 +2,8 @@
 
 The reference lets users write arbitrary Julia residuals differentiated by ForwardDiff
 (src/autodiff.jl:81-93); a HIP kernel cannot call those, so the accelerated path is a closed
-registry.  Anything outside it is declined (NLLS_ERR_UNSUPPORTED).
+registry.  Anything outside it is declined (NLLS_ERR_UNSUPPORTED).  A library built
+with a user header adds residual kinds (register_user_kind) and variable kinds (register_user_var).
 """
 # variable kinds: nvars()/update() of src/variable.jl:3-32, src/robustadaptive.jl:3-23
 VAR_EUCLIDEAN = 1
@@ -80,14 +81,36 @@ def res_ndata(kind):
     return RES_TABLE[kind][2]
 
 
+VAR_USER0 = 100           # .. 107: variable kinds a USER header adds at build time (include/nlls_amd.h, Var<NLLS_VAR_USERk>); a namespace of its own, apart from RES_USER0
+USER_VARS = {}            # kind -> (storage, dof), as register_user_var recorded it
+
+
+def register_user_var(kind, storage, dof):
+    """Tell the host mirror about a variable kind of a library built with a user header (ids 100 .. 107): what Var<kind> declares there -- STORAGE and DOF.
+    Checked against the loaded library's nlls_var_storage / nlls_var_dof: a library without the kind, or with other sizes, raises ValueError."""
+    kind, storage, dof = int(kind), int(storage), int(dof)
+    if not (100 <= kind <= 107 and 1 <= dof <= storage <= 12):
+        raise ValueError(f"user variable kind {kind}: ids 100 .. 107, 1 <= dof <= storage <= 12 (got storage {storage}, dof {dof})")
+    from . import _capi
+    L = _capi.lib()
+    got = (L.nlls_var_storage(kind, dof), L.nlls_var_dof(kind, dof))
+    if got != (storage, dof):
+        raise ValueError(f"user variable kind {kind}: the loaded library ({_capi.LIB_PATH}) declares (storage, dof) = {got}, not {(storage, dof)}")
+    USER_VARS[kind] = (storage, dof)
+
+
 def var_storage(kind, dim):
     """Storage length of a variable (may exceed its dof, src/docstrings.jl:11-14)."""
+    if kind in USER_VARS:
+        return USER_VARS[kind][0]
     return {VAR_EUCLIDEAN: dim, VAR_DYNAMIC: dim, VAR_ZERO_TO_INF: 1, VAR_ZERO_TO_ONE: 1,
             VAR_CONTAMINATED_GAUSSIAN: 3, VAR_POSE_SO3: 12}[kind]
 
 
 def var_dof(kind, dim):
     """nvars(): src/variable.jl:4,9,21,28; src/robustadaptive.jl:21."""
+    if kind in USER_VARS:
+        return USER_VARS[kind][1]
     return {VAR_EUCLIDEAN: dim, VAR_DYNAMIC: dim, VAR_ZERO_TO_INF: 1, VAR_ZERO_TO_ONE: 1,
             VAR_CONTAMINATED_GAUSSIAN: 3, VAR_POSE_SO3: 6}[kind]
 
