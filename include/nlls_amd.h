@@ -133,6 +133,26 @@ typedef struct nlls_ctx nlls_ctx;
 #define NLLS_ROBUST_GEMAN_MCCLURE  3 /* GemanMcclureKernel(w): params[0] = width               */
 #define NLLS_ROBUST_SCALED      0x10 /* OR-ed flag: Scaled(inner, height): params[1] = height  */
 /* adaptive residual kinds ignore robust_kind: their kernel is variable #1. */
+/* USER robust kernels: the reference robustifies with any AbstractRobustifier -- robustify(kernel, cost), and robustifydcost either by second-order
+ * autodiff of it (src/robust.jl:14, src/autodiff.jl:163) or in a closed form of the kernel's own (HuberKernel, src/robust.jl:48-55).  Ids 8 .. 15 are
+ * reserved for kernels a user header adds at BUILD time, next to its residual and variable kinds; they compose with NLLS_ROBUST_SCALED like the built-in
+ * ones.  The header specialises
+ *     template <> struct nlls::Robust<NLLS_ROBUST_USERk> {
+ *         static constexpr int NPARAM;                                        // 0 .. 2: p[0] = robust_params[0], p[1] = robust_params[2]
+ *         template <class T> static NLLS_DEV T robustify(const double* p, T cost);                    // generic in T: double, and the jet nlls::Jet2
+ *         static NLLS_DEV void dcost(const double* p, double cost, double& rho, double& d1, double& d2);   // optional: robustifydcost in closed form
+ *     };
+ * and lists its kernels in NLLS_USER_ROBUST(X).  Without dcost, (rho, d1, d2) are robustify and its first and second derivatives at the cost, by the
+ * one-variable second-order dual nlls::Jet2 (+ - * / with doubles and jets, dsqrt, dexp, dexpm1, dlog, dlog1p; dval for branches on the value).
+ * robust_params[1] stays Scaled's height.  In a library built without a user header these ids are refused (NLLS_ERR_UNSUPPORTED). */
+#define NLLS_ROBUST_USER0          8
+#define NLLS_ROBUST_USER1          9
+#define NLLS_ROBUST_USER2         10
+#define NLLS_ROBUST_USER3         11
+#define NLLS_ROBUST_USER4         12
+#define NLLS_ROBUST_USER5         13
+#define NLLS_ROBUST_USER6         14
+#define NLLS_ROBUST_USER7         15
 
 /* ---- problem description --------------------------------------------------------------------- */
 /* One group per Julia cost type (one VectorRepo entry, src/VectorRepo.jl:1-7), in values(costs)
@@ -212,6 +232,9 @@ int  nlls_set_shard(nlls_ctx* ctx, int32_t rank, int32_t nranks);
  * residual kind, and the variable kind+dim it expects in each slot. */
 int  nlls_var_storage(int32_t var_kind, int32_t var_dim);
 int  nlls_var_dof(int32_t var_kind, int32_t var_dim);
+/* number of parameters of a robust kernel this library has (built-in or NLLS_ROBUST_USER0 .. 7 of its user header; the id without NLLS_ROBUST_SCALED),
+ * negative for any other id */
+int  nlls_robust_nparams(int32_t robust_kind);
 int  nlls_res_ndeps(int32_t res_kind);
 int  nlls_res_nres(int32_t res_kind);
 int  nlls_res_ndata(int32_t res_kind);
@@ -437,6 +460,10 @@ int  nlls_get_memory_info(nlls_ctx* ctx, int64_t* out, int32_t n);
  * block of the uploaded problem at NLLS_VARS_CURRENT both ways; out[0..6] = largest difference of J, J'r, cost, rho', rho'', d rho / d kernel,
  * d2 rho / d kernel d(kernel, cost), each relative to the largest magnitude of that quantity in its block.  n >= 7. */
 int  nlls_check_analytic(nlls_ctx* ctx, double* out, int32_t n);
+/* robustify / robustifydcost (src/robust.jl) of a robust kernel (robust_kind and params as in nlls_cost_group) at n costs, evaluated on the device by the
+ * functions every kernel of the path calls: out[4 i + 0] = robustify(cost[i]), out[4 i + 1 .. 3] = robustifydcost's (rho, rho', rho'').  Needs no upload;
+ * an id the library does not have is NLLS_ERR_UNSUPPORTED. */
+int  nlls_robustify(nlls_ctx* ctx, int32_t robust_kind, const double params[4], int64_t n, const double* cost, double* out);
 int  nlls_flush_cache(nlls_ctx* ctx, int64_t bytes);
 
 /* ---- collectives behind the ABI ("RCCL all-reduce over xGMI on the assembled normal equations") ----------------------

@@ -7,10 +7,10 @@ csrc/libnlls_amd.so and FAILS LOUDLY if it is missing or no gfx950 device is vis
 there is no CPU fallback in the product path (oracle/ is test infrastructure only).
 """
 from . import kinds
-from .kinds import (NoRobust, HuberKernel, Huber2oKernel, GemanMcclureKernel, Scaled)
+from .kinds import (NoRobust, HuberKernel, Huber2oKernel, GemanMcclureKernel, Scaled, UserRobust, register_user_robust)
 from .problem import NLLSProblem, runlengthencodesortedints
 
-__all__ = ["kinds", "NLLSProblem", "NoRobust", "HuberKernel", "Huber2oKernel", "GemanMcclureKernel", "Scaled",
+__all__ = ["kinds", "NLLSProblem", "NoRobust", "HuberKernel", "Huber2oKernel", "GemanMcclureKernel", "Scaled", "UserRobust", "register_user_robust",
            "runlengthencodesortedints"]
 
 

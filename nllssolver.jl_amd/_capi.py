@@ -24,7 +24,7 @@ OPT_MATERIALIZE, OPT_LOOKAHEAD, OPT_PHASE_EVENTS = 1, 2, 3
 VARS_CURRENT, VARS_NEXT, VARS_BEST = 0, 1, 2
 
 # every symbol include/nlls_amd.h declares (checked by tests/test_capi_symbols.py)
-SYMBOLS = """nlls_ctx_create nlls_ctx_destroy nlls_last_error nlls_set_stream nlls_set_shard nlls_var_storage nlls_var_dof
+SYMBOLS = """nlls_ctx_create nlls_ctx_destroy nlls_last_error nlls_set_stream nlls_set_shard nlls_var_storage nlls_var_dof nlls_robust_nparams nlls_robustify
 nlls_res_ndeps nlls_res_nres nlls_res_ndata nlls_res_slot_kind nlls_rcm_order nlls_nd_tiles nlls_upload_structure nlls_get_info nlls_get_bsm_index
 nlls_set_variables nlls_get_variables nlls_swap_variables nlls_copy_variables nlls_sweep_gradhess nlls_sweep_cost
 nlls_get_grad nlls_get_bsm_data nlls_max_abs_diag nlls_grad_sqnorm nlls_grad_quadform nlls_damp nlls_solve nlls_get_solve_stats nlls_set_step
@@ -90,6 +90,7 @@ def lib():
         L.nlls_set_stream.argtypes = [vp, vp]
         L.nlls_set_shard.argtypes = [vp, i32, i32]
         L.nlls_var_storage.argtypes = [i32, i32]; L.nlls_var_dof.argtypes = [i32, i32]
+        L.nlls_robust_nparams.argtypes = [i32]; L.nlls_robustify.argtypes = [vp, i32, vp, i64, vp, vp]
         L.nlls_res_ndeps.argtypes = [i32]; L.nlls_res_nres.argtypes = [i32]; L.nlls_res_ndata.argtypes = [i32]
         L.nlls_res_slot_kind.argtypes = [i32, i32, vp, vp]
         L.nlls_rcm_order.argtypes = [i32, vp, vp, vp]
@@ -305,6 +306,12 @@ class Context:
         """closed-form Jacobians / kernel derivatives against the dual-number statement, per quantity (include/nlls_amd.h)"""
         out = np.zeros(7); self._chk(self.L.nlls_check_analytic(self.h, _p(out), 7))
         return dict(zip(("J", "Jtr", "cost", "drho", "d2rho", "dkernel", "d2kernel"), out.tolist()))
+
+    def robustify(self, robust, costs):
+        """robustify / robustifydcost of a kinds.Robustifier at each cost, evaluated on the device (nlls_robustify): an (n, 4) array of (robustify, rho, rho', rho'')"""
+        c = np.ascontiguousarray(costs, dtype=np.float64).ravel(); out = np.zeros((c.size, 4)); par = np.array(robust.params, dtype=np.float64)
+        self._chk(self.L.nlls_robustify(self.h, int(robust.kind), _p(par), c.size, _p(c), _p(out)))
+        return out
 
     def flush_cache(self, nbytes):
         self._chk(self.L.nlls_flush_cache(self.h, int(nbytes)))

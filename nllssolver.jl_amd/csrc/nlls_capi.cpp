@@ -143,6 +143,7 @@ int nlls_set_shard(nlls_ctx* ctx, int32_t rank, int32_t nranks) { NLLS_API_BEGIN
 
 int nlls_var_storage(int32_t k, int32_t d) { NLLS_API_BEGIN return var_storage(k, d); NLLS_API_END(nullptr) }
 int nlls_var_dof(int32_t k, int32_t d) { NLLS_API_BEGIN return var_dof(k, d); NLLS_API_END(nullptr) }
+int nlls_robust_nparams(int32_t k) { NLLS_API_BEGIN return robust_nparams(k) >= 0 ? robust_nparams(k) : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
 int nlls_res_ndeps(int32_t k) { NLLS_API_BEGIN ResDesc d; return res_desc(k, d) ? d.ndeps : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
 int nlls_res_nres(int32_t k) { NLLS_API_BEGIN ResDesc d; return res_desc(k, d) ? d.nres : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
 int nlls_res_ndata(int32_t k) { NLLS_API_BEGIN ResDesc d; return res_desc(k, d) ? d.ndata : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
@@ -810,6 +811,20 @@ int nlls_check_analytic(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
     std::vector<double> h((size_t)nb * 8);
     HIPCHK(hipMemcpyAsync(h.data(), d.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < nb; ++b) for (int q = 0; q < 7; ++q) { const double v = h[(size_t)b * 8 + q]; if (!(v <= out[q])) out[q] = v; }   // (a NaN difference comes through)
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+// robustify / robustifydcost, src/robust.jl:11-14,26-31,47-55,71-77 (user kernels: their robustify and autorobustifydcost, src/autodiff.jl:163)
+int nlls_robustify(nlls_ctx* ctx, int32_t robust_kind, const double params[4], int64_t n, const double* cost, double* out) { NLLS_API_BEGIN
+    if (!ctx || !params || n < 0 || (n > 0 && (!cost || !out)) || n > ((int64_t)1 << 32)) return NLLS_ERR_INVALID_ARG;
+    if (robust_nparams(robust_kind & 0xF) < 0 || (robust_kind & ~0x1F)) return fail(ctx, NLLS_ERR_UNSUPPORTED, "unregistered robust kernel");
+    if (n == 0) return NLLS_OK;
+    (void)hipSetDevice(ctx->device);
+    RobustSpec rk{}; rk.kind = robust_kind; rk.p0 = params[0]; rk.p1 = params[1]; rk.p2 = params[2];
+    nlls::DevBuf<double> d; HIPCHK(d.alloc((size_t)n * 5));
+    HIPCHK(hipMemcpyAsync(d.p, cost, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    TRY(enqueue_robustify(ctx, rk, n, d.p, d.p + n));
+    HIPCHK(hipMemcpyAsync(out, d.p + n, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

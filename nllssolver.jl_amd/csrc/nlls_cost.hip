@@ -474,6 +474,21 @@ int enqueue_check_analytic(nlls_ctx* c, double* d_out /* [nblocks_total][8] */, 
     return hipGetLastError() == hipSuccess ? NLLS_OK : NLLS_ERR_HIP;
 }
 
+// ---- robustify / robustifydcost of one kernel at many costs (nlls_robustify): the two functions every kernel above calls ----------------------------------------------
+__global__ __launch_bounds__(TPB) void robustify_kernel(RobustSpec rk, int64_t n, const double* __restrict__ cost, double* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TPB) {
+        const double c = cost[i]; double rho, d1, d2;
+        robustifydcost_fixed(rk, c, rho, d1, d2);
+        out[4 * i] = robustify_fixed(rk, c); out[4 * i + 1] = rho; out[4 * i + 2] = d1; out[4 * i + 3] = d2;
+    }
+}
+int enqueue_robustify(nlls_ctx* c, const RobustSpec& rk, int64_t n, const double* d_cost, double* d_out) {
+    if (n <= 0) return NLLS_OK;
+    const int grid = (int)std::min<int64_t>((n + TPB - 1) / TPB, 1024);
+    hipLaunchKernelGGL(robustify_kernel, dim3(grid), dim3(TPB), 0, c->stream, rk, n, d_cost, d_out);
+    return hipGetLastError() == hipSuccess ? NLLS_OK : NLLS_ERR_HIP;
+}
+
 int enqueue_reduce_partials(nlls_ctx* c, int64_t n) {
     hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(TPB), 0, c->stream, c->partials.p, n, c->scalars.p);
     HIPCHK(hipGetLastError());

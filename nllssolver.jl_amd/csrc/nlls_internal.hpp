@@ -38,6 +38,7 @@ int enqueue_fixedcost(nlls_ctx* c, const Group& G, const double* vars, int64_t& 
 int enqueue_dyn_gradhess(nlls_ctx* c, const Group& G, const double* vars, int64_t& pbase);   // dynamic-size residual blocks (dense system): accumulate
 int enqueue_reduce_partials(nlls_ctx* c, int64_t n);
 int enqueue_check_analytic(nlls_ctx* c, double* d_out, int64_t* nblocks_out);   // closed-form block maths against the dual-number statement (nlls_check_analytic)
+int enqueue_robustify(nlls_ctx* c, const RobustSpec& rk, int64_t n, const double* d_cost, double* d_out);   // out[4 i ..] = robustify, rho, rho', rho'' at cost[i] (nlls_robustify)
 int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost = true, int which = NLLS_VARS_CURRENT, int mode = 0);   // mode 1: the reduced rows only (the matrix-free trial's gradient sweep: nlls_ctx::grad_level 1)   // which: the variable set to linearise at (the look-ahead sweep of an LM trial: NLLS_VARS_NEXT)
 // vector helpers (nlls_sweep.hip)
 int enqueue_retract(nlls_ctx* c, int to, int from);

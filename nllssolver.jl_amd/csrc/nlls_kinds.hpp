@@ -180,16 +180,48 @@ template <int N> struct Lift<Dual2N<N>> {     // (seeding through a LINEAR retra
         for (int i = 0; i < N; ++i) if (i == k) r.g[i] = w; return r; }
 };
 
+// ------------------------------------------------------------------------------------------------
+// second-order duals in ONE variable (value, d, dd): a user robust kernel's robustify() differentiated twice w.r.t. the cost -- autorobustifydcost, src/autodiff.jl:163
+// ------------------------------------------------------------------------------------------------
+struct Jet2 { double v, d, dd; };
+NLLS_DEV Jet2 j2chain(const Jet2& a, double f0, double f1, double f2) { return Jet2{f0, f1 * a.d, f1 * a.dd + f2 * a.d * a.d}; }   // f(a), f' and f'' at a.v
+NLLS_DEV Jet2 operator+(const Jet2& a, const Jet2& b) { return Jet2{a.v + b.v, a.d + b.d, a.dd + b.dd}; }
+NLLS_DEV Jet2 operator-(const Jet2& a, const Jet2& b) { return Jet2{a.v - b.v, a.d - b.d, a.dd - b.dd}; }
+NLLS_DEV Jet2 operator*(const Jet2& a, const Jet2& b) { return Jet2{a.v * b.v, a.d * b.v + a.v * b.d, a.dd * b.v + 2.0 * (a.d * b.d) + a.v * b.dd}; }
+NLLS_DEV Jet2 operator/(const Jet2& a, const Jet2& b) { const double ib = 1.0 / b.v, q = a.v * ib, d = (a.d - q * b.d) * ib;
+    return Jet2{q, d, (a.dd - 2.0 * (d * b.d) - q * b.dd) * ib}; }
+NLLS_DEV Jet2 operator+(const Jet2& a, double c) { return Jet2{a.v + c, a.d, a.dd}; }
+NLLS_DEV Jet2 operator+(double c, const Jet2& a) { return a + c; }
+NLLS_DEV Jet2 operator-(const Jet2& a, double c) { return Jet2{a.v - c, a.d, a.dd}; }
+NLLS_DEV Jet2 operator-(double c, const Jet2& a) { return Jet2{c - a.v, -a.d, -a.dd}; }
+NLLS_DEV Jet2 operator-(const Jet2& a) { return Jet2{-a.v, -a.d, -a.dd}; }
+NLLS_DEV Jet2 operator*(const Jet2& a, double s) { return Jet2{a.v * s, a.d * s, a.dd * s}; }
+NLLS_DEV Jet2 operator*(double s, const Jet2& a) { return a * s; }
+NLLS_DEV Jet2 operator/(const Jet2& a, double s) { return a * (1.0 / s); }
+NLLS_DEV Jet2 operator/(double c, const Jet2& a) { const double i = 1.0 / a.v; return j2chain(a, c * i, -c * i * i, 2.0 * c * i * i * i); }
+NLLS_DEV Jet2 dsqrt(const Jet2& a) { const double s = sqrt(a.v), h = 0.5 / s; return j2chain(a, s, h, -0.5 * h / a.v); }
+NLLS_DEV Jet2 dexp(const Jet2& a) { const double e = exp(a.v); return j2chain(a, e, e, e); }
+NLLS_DEV Jet2 dexpm1(const Jet2& a) { const double e = exp(a.v); return j2chain(a, expm1(a.v), e, e); }
+NLLS_DEV Jet2 dlog(const Jet2& a) { const double i = 1.0 / a.v; return j2chain(a, log(a.v), i, -i * i); }
+NLLS_DEV Jet2 dlog1p(const Jet2& a) { const double i = 1.0 / (1.0 + a.v); return j2chain(a, log1p(a.v), i, -i * i); }
+NLLS_DEV double dval(const Jet2& a) { return a.v; }
+template <> struct Lift<Jet2> { static NLLS_DEV Jet2 c(double v) { return Jet2{v, 0.0, 0.0}; } };   // (a constant branch of a robustify<T>)
+NLLS_HD double dexpm1(double a) { return expm1(a); }
+NLLS_HD double dlog(double a) { return log(a); }
+NLLS_HD double dlog1p(double a) { return log1p(a); }
+
 constexpr int MAXST = 12;   // largest variable storage (POSE_SO3)
 constexpr int MAX_SLOTS = 10;   // variables per cost block: MAX_ARGS of the reference (src/NLLSsolver.jl:28).  The built-in kinds declare SK / SD with four entries; a kind with more slots (a user kind) declares as many as it has
 
 template <int KIND> struct Var;   // user variable kinds (include/nlls_amd.h, NLLS_VAR_USER0 .. 7): STORAGE, DOF, update<T>(v, d, out)
 template <int KIND> struct Res;
+template <int KIND> struct Robust;   // user robust kernels (include/nlls_amd.h, NLLS_ROBUST_USER0 .. 7): NPARAM, robustify<T>(p, cost), optionally dcost(p, cost, rho, d1, d2)
 }  // namespace nlls
-// user variable and residual kinds, added at BUILD time (include/nlls_amd.h, NLLS_VAR_USER0 .. 7, NLLS_RES_USER0 .. 7): the header specialises nlls::Var<> and
-// nlls::Res<> and defines NLLS_USER_VAR(X) / NLLS_USER_RES(X).  It sees the dual numbers above; everything below sees its kinds.
+// user variable and residual kinds and robust kernels, added at BUILD time (include/nlls_amd.h, NLLS_VAR_USER0 .. 7, NLLS_RES_USER0 .. 7, NLLS_ROBUST_USER0 .. 7): the
+// header specialises nlls::Var<>, nlls::Res<> and nlls::Robust<> and defines NLLS_USER_VAR(X) / NLLS_USER_RES(X) / NLLS_USER_ROBUST(X).  It sees the dual numbers above;
+// everything below sees its kinds.
 // Pitfall of a user update(): it is differentiated at d = 0 by dual numbers, so its derivatives there must be finite -- sqrt(|w|^2) of a zero dual has NaN partials
-// (0.5 / 0 times 0): take a series branch for small arguments, as so3_exp does.
+// (0.5 / 0 times 0): take a series branch for small arguments, as so3_exp does.  The same holds for a user robustify() at cost = 0 (every cost of a zero residual).
 #ifdef NLLS_USER_KINDS_HEADER
 #include NLLS_USER_KINDS_HEADER
 #endif
@@ -198,6 +230,9 @@ template <int KIND> struct Res;
 #endif
 #ifndef NLLS_USER_VAR
 #define NLLS_USER_VAR(X)
+#endif
+#ifndef NLLS_USER_ROBUST
+#define NLLS_USER_ROBUST(X)
 #endif
 namespace nlls {
 
@@ -460,11 +495,62 @@ template <int KIND> struct ResInfo {
 // ------------------------------------------------------------------------------------------------
 // robust kernels
 // ------------------------------------------------------------------------------------------------
-struct RobustSpec { int kind; double p0, p1; };
+// p0 = robust_params[0] (the width), p1 = robust_params[1] (Scaled's height), p2 = robust_params[2] (a user kernel's second parameter).  The layout is the same with and
+// without a user header: the objects that do not instantiate kernels are shared between the default library and `make user`'s.
+struct RobustSpec { int kind; double p0, p1, p2; };
+
+// user robust kernels (include/nlls_amd.h, NLLS_ROBUST_USER0 .. 7): robustify<T> at T = double is robustify(); robustifydcost is the kernel's own dcost() where it
+// has one (as HuberKernel's closed form, src/robust.jl:48-55), else (value, first, second derivative) of robustify<Jet2> -- autorobustifydcost, src/autodiff.jl:163
+#define NLLS_USER_ROBUST_LIMITS(K) \
+    static_assert((K) >= NLLS_ROBUST_USER0 && (K) <= NLLS_ROBUST_USER7, "user robust kernels are NLLS_ROBUST_USER0 .. NLLS_ROBUST_USER7"); \
+    static_assert(0 <= Robust<K>::NPARAM && Robust<K>::NPARAM <= 2, "a user robust kernel takes at most 2 parameters: robust_params[0] and [2]");
+NLLS_USER_ROBUST(NLLS_USER_ROBUST_LIMITS)
+#undef NLLS_USER_ROBUST_LIMITS
+#define X(K) + 1
+constexpr int NUM_USER_ROBUST = 0 NLLS_USER_ROBUST(X);
+#undef X
+NLLS_HD constexpr int robust_nparams(int kind) {   // NPARAM of a kernel this build has, -1 for any other id (flags included)
+    if (kind == NLLS_ROBUST_NONE) return 0;
+    if (kind == NLLS_ROBUST_HUBER || kind == NLLS_ROBUST_HUBER2O || kind == NLLS_ROBUST_GEMAN_MCCLURE) return 1;
+#define X(K) if (kind == K) return Robust<K>::NPARAM;
+    NLLS_USER_ROBUST(X)
+#undef X
+    return -1;
+}
+template <class R> concept HasDcost = requires(const double* p, double c, double& a) { R::dcost(p, c, a, a, a); };
+template <int K>
+NLLS_DEV void autorobustifydcost(const double* p, double cost, double& rho, double& d1, double& d2) {
+    const Jet2 r = Robust<K>::template robustify<Jet2>(p, Jet2{cost, 1.0, 0.0});
+    rho = r.v; d1 = r.d; d2 = r.dd;
+}
+template <int K>
+NLLS_DEV void user_dcost(const double* p, double cost, double& rho, double& d1, double& d2) {
+    if constexpr (HasDcost<Robust<K>>) Robust<K>::dcost(p, cost, rho, d1, d2);
+    else autorobustifydcost<K>(p, cost, rho, d1, d2);
+}
+NLLS_DEV double user_robustify(int base, const RobustSpec& k, double cost) {
+    const double p[2] = {k.p0, k.p2};
+    switch (base) {
+#define X(K) case K: return Robust<K>::template robustify<double>(p, cost);
+    NLLS_USER_ROBUST(X)
+#undef X
+    }
+    return cost;
+}
+NLLS_DEV void user_robustifydcost(int base, const RobustSpec& k, double cost, double& rho, double& d1, double& d2) {
+    const double p[2] = {k.p0, k.p2};
+    switch (base) {
+#define X(K) case K: user_dcost<K>(p, cost, rho, d1, d2); return;
+    NLLS_USER_ROBUST(X)
+#undef X
+    }
+    rho = cost; d1 = 1; d2 = 0;
+}
 
 NLLS_DEV double robustify_fixed(const RobustSpec& k, double cost) {   // src/robust.jl:11,26,47,71
     int base = k.kind & 0xF; double c;
-    if (base == NLLS_ROBUST_HUBER || base == NLLS_ROBUST_HUBER2O) { double w2 = k.p0 * k.p0; c = cost < w2 ? cost : sqrt(cost) * (k.p0 * 2) - w2; }
+    if (NUM_USER_ROBUST > 0 && base >= NLLS_ROBUST_USER0) c = user_robustify(base, k, cost);
+    else if (base == NLLS_ROBUST_HUBER || base == NLLS_ROBUST_HUBER2O) { double w2 = k.p0 * k.p0; c = cost < w2 ? cost : sqrt(cost) * (k.p0 * 2) - w2; }
     else if (base == NLLS_ROBUST_GEMAN_MCCLURE) { double w2 = k.p0 * k.p0; c = cost * w2 / (cost + w2); }
     else c = cost;
     if (k.kind & NLLS_ROBUST_SCALED) c *= k.p1;
@@ -472,7 +558,8 @@ NLLS_DEV double robustify_fixed(const RobustSpec& k, double cost) {   // src/rob
 }
 NLLS_DEV void robustifydcost_fixed(const RobustSpec& k, double cost, double& rho, double& d1, double& d2) {   // src/robust.jl:12,28-31,48-55,72-77
     int base = k.kind & 0xF;
-    if (base == NLLS_ROBUST_HUBER || base == NLLS_ROBUST_HUBER2O) {
+    if (NUM_USER_ROBUST > 0 && base >= NLLS_ROBUST_USER0) user_robustifydcost(base, k, cost, rho, d1, d2);
+    else if (base == NLLS_ROBUST_HUBER || base == NLLS_ROBUST_HUBER2O) {
         double w = k.p0, w2 = w * w;
         if (cost < w2) { rho = cost; d1 = 1; d2 = 0; }
         else { double sq = sqrt(cost); rho = sq * (w * 2) - w2; d1 = w / sq; d2 = base == NLLS_ROBUST_HUBER2O ? (-0.5 * w) / (cost * sq) : 0.0; }

@@ -236,7 +236,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     for (int g = 0; g < ngroups; ++g) {
         if (!res_desc(groups[g].res_kind, desc[g])) return fail(c, NLLS_ERR_UNSUPPORTED, "unregistered residual kind");
         int base = groups[g].robust_kind & 0xF;
-        if (base > NLLS_ROBUST_GEMAN_MCCLURE || (groups[g].robust_kind & ~0x1F)) return fail(c, NLLS_ERR_UNSUPPORTED, "unregistered robust kernel");
+        if (robust_nparams(base) < 0 || (groups[g].robust_kind & ~0x1F)) return fail(c, NLLS_ERR_UNSUPPORTED, "unregistered robust kernel");   // (user kernels: those this build has)
         if (is_dyn_kind(groups[g].res_kind)) {       // n = the run-time length of the block's variable: the same for every block of the group
             any_dyn = true;
             if ((base != NLLS_ROBUST_NONE || (groups[g].robust_kind & NLLS_ROBUST_SCALED)) && groups[g].res_kind == NLLS_COST_DYN_LINEAR) return fail(c, NLLS_ERR_UNSUPPORTED, "a non-squared cost takes no robust kernel");
@@ -387,7 +387,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     for (int g = 0; g < ngroups; ++g) {
         Group& G = c->groups[g]; const ResDesc& d = desc[g]; const nlls_cost_group& in = groups[g];
         G.res_kind = in.res_kind; G.ndeps = d.ndeps; G.ndata = d.ndata; G.nres = d.nres; G.adaptive = d.adaptive; G.ncost = in.ncost;
-        G.rk.kind = in.robust_kind; G.rk.p0 = in.robust_params[0]; G.rk.p1 = in.robust_params[1];
+        G.rk.kind = in.robust_kind; G.rk.p0 = in.robust_params[0]; G.rk.p1 = in.robust_params[1]; G.rk.p2 = in.robust_params[2];
         // cost-order arrays
         std::vector<uint32_t> fixedcost;
         { std::vector<double> hd; std::vector<uint32_t> hv; hd.reserve((size_t)in.ncost * d.ndata); hv.reserve((size_t)in.ncost * d.ndeps);

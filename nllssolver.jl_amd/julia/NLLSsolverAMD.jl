@@ -61,8 +61,15 @@ robustspec(k::GemanMcclureKernel) = (ROBUST_GEMAN_MCCLURE, (sqrt(Float64(k.width
 function robustspec(k::Scaled)
     inner = robustspec(k.robust); inner === nothing && return nothing
     (inner[1] & ROBUST_SCALED) != 0 && return nothing
-    return (inner[1] | ROBUST_SCALED, (inner[2][1], Float64(k.height), 0.0, 0.0))
+    return (inner[1] | ROBUST_SCALED, (inner[2][1], Float64(k.height), inner[2][3], 0.0))
 end
+# USER robust kernels of a library built with a user header (include/nlls_amd.h, NLLS_ROBUST_USER0 .. 7; NLLS_AMD_LIB names that library): the user's
+# AbstractRobustifier type maps to the id and its parameters, p[0] in params[1] and p[1] in params[3] (params[2] is Scaled's height).  For Barron's loss of
+# tests/user_kinds/robust_kernels.hpp (USER4, scale c and shape alpha):
+#   struct BarronKernel <: NLLSsolver.AbstractRobustifier; c::Float64; alpha::Float64; end          (robustify as in the header)
+#   NLLSsolverAMD.robustspec(k::BarronKernel) = (NLLSsolverAMD.ROBUST_USER0 + Int32(4), (k.c, 0.0, k.alpha, 0.0))
+# Scaled(BarronKernel(...), h) then composes like a built-in kernel.
+const ROBUST_USER0 = Int32(8)                                      # .. 15
 robustspec(::Any) = nothing
 
 # Users register the residual kind of their cost type (closed world, SURVEY.md F3), e.g. for the bundle

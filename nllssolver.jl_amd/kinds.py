@@ -3,7 +3,8 @@
 The reference lets users write arbitrary Julia residuals differentiated by ForwardDiff
 (src/autodiff.jl:81-93); a HIP kernel cannot call those, so the accelerated path is a closed
 registry.  Anything outside it is declined (NLLS_ERR_UNSUPPORTED).  A library built
-with a user header adds residual kinds (register_user_kind) and variable kinds (register_user_var).
+with a user header adds residual kinds (register_user_kind), variable kinds (register_user_var) and
+robust kernels (register_user_robust, UserRobust).
 """
 # variable kinds: nvars()/update() of src/variable.jl:3-32, src/robustadaptive.jl:3-23
 VAR_EUCLIDEAN = 1
@@ -38,6 +39,7 @@ ROBUST_HUBER = 1
 ROBUST_HUBER2O = 2
 ROBUST_GEMAN_MCCLURE = 3
 ROBUST_SCALED = 0x10
+ROBUST_USER0 = 8          # .. 15: robust kernels a USER header adds at build time (include/nlls_amd.h, Robust<NLLS_ROBUST_USERk>); they compose with ROBUST_SCALED
 
 # (ndeps, nres, ndata, adaptive, ((slot kind, slot dim), ...))
 RES_TABLE = {
@@ -144,4 +146,31 @@ def GemanMcclureKernel(w):            # src/robust.jl:63-69
 
 def Scaled(inner, height):            # src/robust.jl:22-31
     assert not (inner.kind & ROBUST_SCALED), "nested Scaled is not a registered kernel"
-    return Robustifier(inner.kind | ROBUST_SCALED, (inner.params[0], height))
+    return Robustifier(inner.kind | ROBUST_SCALED, (inner.params[0], height, inner.params[2]))
+
+
+USER_ROBUST = {}          # kind -> NPARAM, as register_user_robust recorded it
+
+
+def register_user_robust(kind, nparams):
+    """Tell the host mirror about a robust kernel of a library built with a user header (ids 8 .. 15): what Robust<kind> declares there -- NPARAM.
+    Checked against the loaded library's nlls_robust_nparams: a library without the kernel, or with another NPARAM, raises ValueError."""
+    kind, nparams = int(kind), int(nparams)
+    if not (ROBUST_USER0 <= kind <= ROBUST_USER0 + 7 and 0 <= nparams <= 2):
+        raise ValueError(f"user robust kernel {kind}: ids 8 .. 15, 0 .. 2 parameters (got {nparams})")
+    from . import _capi
+    got = _capi.lib().nlls_robust_nparams(kind)
+    if got != nparams:
+        raise ValueError(f"user robust kernel {kind}: the loaded library ({_capi.LIB_PATH}) declares NPARAM = {got}, not {nparams}")
+    USER_ROBUST[kind] = nparams
+
+
+def UserRobust(kind, *params):
+    """A user robust kernel (ids 8 .. 15) with its parameters: the kernel sees p[0] = robust_params[0], p[1] = robust_params[2] (robust_params[1] is Scaled's height)."""
+    kind = int(kind)
+    if not ROBUST_USER0 <= kind <= ROBUST_USER0 + 7:
+        raise ValueError(f"user robust kernel {kind}: ids 8 .. 15")
+    if len(params) > 2 or (kind in USER_ROBUST and len(params) != USER_ROBUST[kind]):
+        raise ValueError(f"user robust kernel {kind}: {len(params)} parameters, the kernel takes {USER_ROBUST.get(kind, 'at most 2')}")
+    p = tuple(params) + (0.0,) * (2 - len(params))
+    return Robustifier(kind, (p[0], 0.0, p[1]))
