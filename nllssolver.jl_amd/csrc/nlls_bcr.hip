@@ -437,8 +437,8 @@ __global__ __launch_bounds__(BCR_T) void bcr_panel_kernel(BcrPanelArgs a) {
 // block as its X rows; every workgroup factors the 64 x 64 diagonal block itself (identical bits).  Out: L in place of the
 // panel (unit lower, Delta on the diagonal of the diagonal block), W = L Delta of the rows below into the panel workspace
 // (what the MFMA trailing update multiplies with), inv(L_JJ)' of the four diagonal tiles for the backward pass.
-// Replaces one ldlt_diag_kernel (64 dependent pivots with two barriers each: 73 us) + trsm_panel_kernel (one thread per row,
-// uncoalesced: 55 us) launch pair of round 1.
+// Replaces round 1's launch pair: an unblocked LDL' of the diagonal block in LDS (64 dependent pivots with two barriers each: 73 us) and a
+// triangular solve of the rows below it (one thread per row, uncoalesced: 55 us); both last in the tree at commit 18ea6f9.
 // ---------------------------------------------------------------------------------------------------
 struct DensePanelArgs { double* S; double* W; double* LiD; int npad, k, T; int* status; double* Dfac; int wq, wstrip; };   // wq >= 0: windowed -- logical X tile row q (T of them) is tile row  q < wq ? NT (k + 1) + q : wstrip + (q - wq)   // Dfac: scratch for the factored diagonal block (16 NT square, column-major)
 // NT tiles = 16 NT columns per panel (4: 64 columns; 8: 128 columns, the width of one pass of the trailing update -- then no narrow update and

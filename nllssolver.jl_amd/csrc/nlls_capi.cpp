@@ -46,7 +46,6 @@ int ensure_grad(nlls_ctx* ctx, int level) {
     ctx->lambda = lam; ctx->solved = false;
     return NLLS_OK;
 }
-int ensure_grad_current(nlls_ctx* ctx) { return ensure_grad(ctx, 2); }
 // a variable set is about to be written: a look-ahead sweep of it is stale, and so is a linearisation at it that is not (fully) formed yet
 int spec_note_write(nlls_ctx* ctx, int32_t which) {
     ctx->mf_step = false;                                       // (the last matrix-free trial's point and cost are of the sets as they were: its tail is not finished again)
@@ -87,10 +86,6 @@ int nlls_ctx_create(const int32_t* device_ids, int32_t ndev, nlls_ctx** out) { N
     { const char* e = getenv("NLLS_NO_LOOKAHEAD_SWEEP"); if (e && e[0] == '1') c->spec_on = false; }
     { const char* e = getenv("NLLS_MATERIALIZE"); if (e && e[0] == '1') c->mf_on = false; }
     { const char* e = getenv("NLLS_TINY_DENSE"); if (e && e[0] == '0') c->tiny_dense_on = false; }
-    { const char* e = getenv("NLLS_TINY_FIN_ROLE"); if (e && e[0] == '0') c->tiny_fin_role = false; }             // (A/B: the trial's finishing reduction always in a launch of its own)
-    { const char* e = getenv("NLLS_ELIM_TILED"); if (e && e[0] == '1') c->elim_mfma = false; }
-    { const char* e = getenv("NLLS_DENSE_T64"); if (e && e[0] == '1') c->dense_t128 = false; }
-    { const char* e = getenv("NLLS_EAGER_STAGE0"); if (e && e[0] == '1') c->lazy_stage0 = false; }
     { const char* e = getenv("NLLS_POST_SPLIT"); if (e && e[0] == '1') c->post_fuse = false; }
     { const char* e = getenv("NLLS_ELIM_SPLIT"); if (e && e[0] == '1') c->elim_split = true; }
     { const char* e = getenv("NLLS_DENSE_STEP_BACKWARD"); if (e && e[0] == '1') c->dense_fused_bwd = false; }
@@ -286,7 +281,7 @@ int nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out) { NLLS_API_BEGIN
     // discards it) -- the sweep is then only enqueued: no partial-sum kernel, no synchronisation
     if (ctx->reduce_fn) {
         // collective (include/nlls_amd.h): this rank's blocks, then ONE sum over ranks of [cost | reduced rows of A.data | reduced part of b]
-        const bool lazy = !cost_out && ctx->lazy_stage0 && ctx->info.is_sparse && !ctx->elim_slab;
+        const bool lazy = !cost_out && ctx->info.is_sparse && !ctx->elim_slab;
         if (ctx->phase_on && ctx->phase_ev.size() >= 8) {      // (the previous sweep's pair has long completed: the trials between synchronise)
             float ms = 0.f; if (ctx->phase_sweeps >= 0 && hipEventElapsedTime(&ms, ctx->phase_ev[6], ctx->phase_ev[7]) == hipSuccess) { ctx->phase_ms[5] += ms; ctx->phase_sweeps++; } else (void)hipGetLastError();
             (void)hipEventRecord(ctx->phase_ev[6], ctx->stream);
@@ -417,7 +412,7 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
         phase_mark(ctx, 5);
     } else if (ctx->tiny_dense) {
         const bool la = ctx->spec_on && ctx->spec_armed && from == NLLS_VARS_CURRENT;
-        TRY(enqueue_tiny_dense_trial(ctx, to, from, la && ctx->tiny_fin_role));
+        TRY(enqueue_tiny_dense_trial(ctx, to, from, la));
         if (la) { TRY(enqueue_sweep_gradhess(ctx, false, to)); ctx->spec_pending = true; ctx->spec_stale = false; }
         TRY(enqueue_tiny_trial_finish_pending(ctx));      // (no accumulate launch took the finishing reduction along)
     } else {

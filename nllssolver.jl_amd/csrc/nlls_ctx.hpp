@@ -249,9 +249,9 @@ struct nlls_ctx {
     // damping + factorisation + step statistics + retraction, then the cost sweep.  NLLS_TINY_DENSE=0 keeps the general kernels (A/B)
     bool tiny_dense = false, tiny_dense_on = true; nlls::DevBuf<double> dense_slab; int64_t dense_slab_wgs = 0, dense_slab_used = 0;
     // An LM trial followed by its look-ahead sweep is FOUR launches: [damped solve + statistics + retraction] (one wavefront), the cost sweep, [the finishing reduction as
-    // workgroup 0 + the look-ahead accumulate sweep], the gather.  dense_fin: a finishing reduction waiting for the accumulate launch that carries it (NLLS_TINY_FIN_ROLE=0:
-    // always a launch of its own, A/B)
-    nlls::DenseFin dense_fin{}; bool dense_fin_pending = false, tiny_fin_role = true;
+    // workgroup 0 + the look-ahead accumulate sweep], the gather.  dense_fin: a finishing reduction waiting for the accumulate launch that carries it (without a look-ahead
+    // sweep behind the trial -- the first trial from a new start, or the look-ahead off -- it runs in a launch of its own)
+    nlls::DenseFin dense_fin{}; bool dense_fin_pending = false;
     bool have_grad = false;
     // Device-timed NLLSResult buckets (round 6; src/structs.jl:37-50, filled at src/iterators.jl:152,157): the launches of an LM trial leave the constant clock (100 MHz) in the pinned
     // mirror -- h_scalars[40] start of the assembly launch, [41] of the back-substitution, [42] start of the cost launch (matrix-free trial: of the finishing workgroup; the cost rides in
@@ -282,10 +282,9 @@ struct nlls_ctx {
     // ---- sharding ------------------------------------------------------------------------------------
     bool replicate_xr = false;               // the step's reduced part is written on every rank (sharded LM trial without the stage-2 reduction)
     int ps_np = 0, ps_np2 = 0;                 // partial counts of the last enqueue_post_solve (for the trial's finishing launch)
-    int dense_t128_min = 16;                   // ... only while the trailing matrix has at least this many 128-blocks per side (fewer: the 64 x 64 kernel fills the chip better)
+    int dense_t128_min = 16;                   // dense LDL': 128 x 128 tiles in the trailing update only while it has at least this many 128-blocks per side (fewer: the 64 x 64 kernel fills the chip better)
     bool dense_pad128 = false;                 // the dense layout is padded to a multiple of 128 rows (windowed and look-ahead factorisations: 128-column panels only)
     bool dense_window = false;                 // dense LDL' restricted to the band of the (re-ordered) reduced system + the border strip: O(n w^2) instead of n^3 / 3 (build_schur decides)
-    bool dense_t128 = true;                    // dense LDL': 128 x 128 tiles in the two-panel trailing update (NLLS_DENSE_T64=1: the 64 x 64 kernel, for A/B runs)
     bool dense_fused_bwd = true;               // dense LDL': the backward substitution in one launch (NLLS_DENSE_STEP_BACKWARD=1: one launch per 64-column block, for A/B runs)
     // LM trial with the retraction inside the back-substitution launch and the step statistics / quadratic form inside the cost sweep's launch
     // (one rank, every eliminated block on the fast path, Euclidean eliminated variables): no launch of its own for them.  NLLS_POST_SPLIT=1: off (A/B)
@@ -293,7 +292,6 @@ struct nlls_ctx {
     nlls::DevBuf<uint32_t> d_rest_var; nlls::DevBuf<int32_t> d_rest_red;   // the other variables, and where their step starts in the reduced solution (-1: fixed)
     bool fast_all_euclid = false, post_fuse = true, retract_done = false; int trial_to = -1, trial_from = -1;
     bool elim_split = false;                   // NLLS_ELIM_SPLIT=1: the assembly of the reduced system in three launches (A/B)
-    bool elim_mfma = true;                     // narrow supernodes (nd + 1 <= 64) are eliminated on the matrix cores (NLLS_ELIM_TILED=1: the register-tiled kernel, for A/B runs)
     bool elim_selected = false;
     std::vector<int32_t> owner_of_block;
     int64_t local_ncost = 0, local_nnz_data = 0, local_ndof = 0;
@@ -325,7 +323,6 @@ struct nlls_ctx {
     nlls::DevBuf<uint8_t> d_blk_mask_lazy; nlls::DevBuf<double> d_dof_mask_lazy;
     bool reduced_summed = true;              // false between a lazy sweep and the first entry point that needs the summed rows (ensure_reduced_summed)
     int64_t n_stage0 = 0, n_lazy_trials = 0; // (diagnostics: nlls_get_solve_stats [11], [12])
-    bool lazy_stage0 = true;                 // NLLS_EAGER_STAGE0=1: sum the reduced rows behind every sweep, as round 2 did (A/B)
     nlls::DevBuf<double> tE;                 // E_v s of the last solve per fast member (s = reduced solution): reused by the quadratic form
     bool tE_valid = false; int64_t n_fast_members = 0;
     bool status_known_zero = false;          // the host has read the last solve's status and it was 0: the next solve need not reset it on the device

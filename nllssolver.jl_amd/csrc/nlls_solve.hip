@@ -333,25 +333,17 @@ __global__ __launch_bounds__(64) void schur_backsub_fast_kernel(const double* __
 // with HBM atomics (supernodes of different points overlap in S).
 constexpr int ELIM_PF = 4;                                    // members in flight per solver thread
 constexpr int ELIM_NDP = 76;                                  // columns of [E | b] rounded up to a multiple of 4 (nd + 1 <= 72)
-// NC: columns of [E | b] per lane of the solver wave (1: nd + 1 <= 64; 2: up to ELIM_NDP - 4).  TW: tile waves -- two hold
-// the 4x4 tiles of nd <= 60 (120 tiles on 128 lanes: the bundle-adjustment point seen by ten cameras), three the rest.
-// (EXT: the workgroup's LDS is handed in -- ext, 16-byte aligned, schur_elim_tiled_lds<DV, NC>() doubles -- so that a kernel that runs either this body or
-//  another one in a workgroup pays for the larger of the two, not for their sum)
-template <int DV, int NC> constexpr int schur_elim_tiled_lds() { constexpr int NDM = NC == 1 ? 63 : ELIM_NDP - 5; return 4 * DV * ELIM_NDP + ELIM_NDP + NDM * (NDM + 1) / 2 + NDM + 2; }
-template <int DV, int NC, int TW, bool EXT = false, class LAY = SLayout>
+// NC: columns of [E | b] per lane of the solver wave (2: up to ELIM_NDP - 4; the narrow supernodes, nd + 1 <= 64, take the matrix cores
+// below).  TW: tile waves -- three hold the 4x4 tiles.  (The narrow instances, NC = 1 with two or three tile waves, were measured slower
+// than the matrix cores; last in the tree at commit 18ea6f9.)
+template <int DV, int NC, int TW, class LAY = SLayout>
 __device__ __forceinline__ void schur_elim_tiled_body(const double* __restrict__ A, const double* __restrict__ b,
                                                       const ElimDesc* __restrict__ desc, const uint32_t* __restrict__ rcflat,
-                                                      const double* __restrict__ Cinv, const LAY& L, double* __restrict__ s, uint32_t bidx, double* ext = nullptr) {
-    double (*Es)[DV][ELIM_NDP]; double (*Ys)[DV][ELIM_NDP]; uint32_t* rc; uint32_t* rs; double* img;      // rc: reduced column of list column p (MEMORY order); rs: the list columns by ascending reduced column
-    if constexpr (EXT) {
-        Es = reinterpret_cast<double (*)[DV][ELIM_NDP]>(ext); Ys = reinterpret_cast<double (*)[DV][ELIM_NDP]>(ext + 2 * DV * ELIM_NDP);
-        rc = reinterpret_cast<uint32_t*>(ext + 4 * DV * ELIM_NDP); rs = rc + ELIM_NDP; img = ext + 4 * DV * ELIM_NDP + ELIM_NDP;
-    } else {
-        __shared__ __attribute__((aligned(16))) double Es_[2][DV][ELIM_NDP], Ys_[2][DV][ELIM_NDP];
-        __shared__ uint32_t rc_[ELIM_NDP], rs_[ELIM_NDP];
-        __shared__ double img_[(NC == 1 ? 63 : ELIM_NDP - 5) * ((NC == 1 ? 63 : ELIM_NDP - 5) + 1) / 2 + (NC == 1 ? 63 : ELIM_NDP - 5)];
-        Es = Es_; Ys = Ys_; rc = rc_; rs = rs_; img = img_;
-    }
+                                                      const double* __restrict__ Cinv, const LAY& L, double* __restrict__ s, uint32_t bidx) {
+    constexpr int NDMAX = ELIM_NDP - 5;
+    __shared__ __attribute__((aligned(16))) double Es[2][DV][ELIM_NDP], Ys[2][DV][ELIM_NDP];
+    __shared__ uint32_t rc[ELIM_NDP], rs[ELIM_NDP];           // rc: reduced column of list column p (MEMORY order); rs: the list columns by ascending reduced column
+    __shared__ double img[NDMAX * (NDMAX + 1) / 2 + NDMAX];
     const int tid = threadIdx.x; constexpr int NT = 64 * (1 + TW);
     const ElimDesc d = desc[bidx];                       // uniform: one scalar load (the run's structure is identical for all members)
     const uint32_t v0 = d.v0, v1 = d.v0 + d.nmem; const int nd = (int)d.nd;
@@ -373,7 +365,6 @@ __device__ __forceinline__ void schur_elim_tiled_body(const double* __restrict__
     // (the members of a supernode are consecutive block rows: constant stride in A.data and in b, nlls_structure.cpp)
     const int64_t dg0 = d.dg0, dstride = (int64_t)DV * nd + DV * DV; const uint32_t eb0 = d.eb0;
     auto member_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };   // LDS only: loads stay in flight
-    constexpr int NDMAX = NC == 1 ? 63 : ELIM_NDP - 5;
     double* const irhs = img + NDMAX * (NDMAX + 1) / 2; double* const rhs_out = irhs;   // (the flush image: used after the member loop)
     if (tid < 64) {
         // ---- solver wave.  Software pipeline: registers hold the column and the inverse diagonal block (schur_cinv_kernel)
@@ -695,161 +686,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     else schur_elim_tiled_body<DV, 2, 3>(A, b, desc, rcflat, Cinv, L, s, blockIdx.x);
 }
 
-template <int DV, int NC, int TW>
-__global__ __launch_bounds__(64 * (1 + TW)) void schur_elim_slab_kernel(const double* __restrict__ A, const double* __restrict__ b,
-                                                               const int64_t* __restrict__ eptr, const SchurNbr* __restrict__ enbr,
-                                                               const int64_t* __restrict__ ediag, const uint32_t* __restrict__ eboff,
-                                                               const uint32_t* __restrict__ egroup, const uint32_t* __restrict__ glist,
-                                                               const double* __restrict__ Cinv, double* __restrict__ slab, const uint32_t* __restrict__ slab_off) {
-    __shared__ __attribute__((aligned(16))) double Es[2][DV][ELIM_NDP], Ys[2][DV][ELIM_NDP];
-    __shared__ uint32_t rc[ELIM_NDP];
-    const int tid = threadIdx.x; constexpr int NT = 64 * (1 + TW);
-    const uint32_t g = glist[blockIdx.x];
-    const uint32_t v0 = egroup[g], v1 = egroup[g + 1];
-    // structure of the run (identical for all members): reduced column of every E column
-    const int64_t p0 = eptr[v0]; const int nnb = (int)(eptr[v0 + 1] - p0);
-    int nd = 0;
-    __shared__ uint8_t cblk[ELIM_NDP], coff[ELIM_NDP]; __shared__ uint16_t bdim[16], poff[16 * 17 / 2 + 1];
-    for (int p = 0; p < nnb; ++p) { const SchurNbr nb = enbr[p0 + p]; for (int c2 = tid; c2 < nb.dim; c2 += NT) { cblk[nd + c2] = (uint8_t)p; coff[nd + c2] = (uint8_t)c2; } if (tid == 0) bdim[p] = nb.dim; nd += nb.dim; }
-    if (tid == 0) { int acc0 = 0; for (int A2 = 0; A2 < nnb; ++A2) { const int dA = enbr[p0 + A2].dim; for (int B2 = 0; B2 <= A2; ++B2) { poff[A2 * (A2 + 1) / 2 + B2] = (uint16_t)acc0; acc0 += dA * enbr[p0 + B2].dim; } } poff[nnb * (nnb + 1) / 2] = (uint16_t)acc0; }
-    for (int i = tid; i < 2 * DV * ELIM_NDP; i += NT) { (&Es[0][0][0])[i] = 0.0; (&Ys[0][0][0])[i] = 0.0; }
-    __syncthreads();
-    // this thread's tile: t < ntile -> (tp, tq), tq <= tp, pairs (4 tp + i, 4 tq + j).  (The rhs column E' y_b is summed by the
-    // solver wave, which has every column of E in registers: the tile waves then carry no half-empty tiles.)
-    const int T = (nd + 3) >> 2, ntile = T * (T + 1) / 2;
-    // (tiles live on waves 1-3: wave 0 is the solver and runs one member ahead of them)
-    const int tt = tid - 64;
-    int tp = 0, tq = 0; const bool has_tile = tt >= 0 && tt < ntile;
-    if (has_tile) { tp = (int)((sqrt(8.0 * tt + 1.0) - 1.0) * 0.5); while (tp * (tp + 1) / 2 > tt) --tp; while ((tp + 1) * (tp + 2) / 2 <= tt) ++tp; tq = tt - tp * (tp + 1) / 2; }
-    double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    // (the members of a supernode are consecutive block rows: constant stride in A.data and in b, nlls_structure.cpp)
-    const int64_t dg0 = ediag[v0], dstride = (int64_t)DV * nd + DV * DV; const uint32_t eb0 = eboff[v0];
-    auto member_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };   // LDS only: loads stay in flight
-    constexpr int NDMAX = NC == 1 ? 63 : ELIM_NDP - 5;
-    __shared__ double img[NDMAX * (NDMAX + 1) / 2 + 16 * NDMAX + NDMAX];   // one column-major block per pair of neighbour blocks (diagonal pairs: lower triangle filled), then the rhs
-    double* const rhs_out = img + poff[nnb * (nnb + 1) / 2];
-    if (tid < 64) {
-        // ---- solver wave.  Software pipeline: registers hold the column and the inverse diagonal block (schur_cinv_kernel)
-        // of the next ELIM_PF members (HBM latency is a multiple of a member's processing time).  What keeps the pipeline
-        // alive in the compiled code: (a) every load is unconditional -- lanes beyond the last column and steps beyond the
-        // last member re-load a valid address -- so that a load writes the register it is consumed from and its wait sits at
-        // the use, one round later (a conditional load becomes a copy plus vmcnt(0) at the end of the round); (b) the
-        // inverse, although the same for every lane, does NOT come through scalar loads: they share lgkmcnt with the LDS
-        // traffic and return out of order, so the LDS wait of every member would also wait for the scalar load issued a
-        // moment ago for the member four ahead (`vz` hides the uniformity from the compiler).
-        uint32_t vz = 0; asm volatile("" : "+v"(vz));
-        double en[ELIM_PF][NC][DV], cn[ELIM_PF][DV * DV];
-        double racc[NC];                                          // entry tid (+ 64) of the rhs column E' y_b
-#pragma unroll
-        for (int k = 0; k < NC; ++k) racc[k] = 0.0;
-        const int kb = nd >> 6, lb = nd & 63;                     // where the rhs column sits: lane lb, slot kb
-        auto issue = [&](uint32_t v, int slot) {
-            const uint32_t m = (v < v1 ? v : v1 - 1) - v0;
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                const int col = tid + 64 * k < nd ? tid + 64 * k : nd;
-                const double* src = col < nd ? A + (dg0 + (int64_t)m * dstride - (int64_t)DV * nd + (int64_t)DV * col) : b + (eb0 + m * DV);
-#pragma unroll
-                for (int a2 = 0; a2 < DV; ++a2) en[slot][k][a2] = src[a2];
-            }
-#pragma unroll
-            for (int j = 0; j < DV; ++j)
-#pragma unroll
-                for (int i = j; i < DV; ++i) cn[slot][i + DV * j] = Cinv[(int64_t)(v0 + m) * (DV * DV) + i + DV * j + vz];   // symmetric: lower triangle
-        };
-#pragma unroll
-        for (int u = 0; u < ELIM_PF; ++u) issue(v0 + u, u);
-        int buf = 0;
-#pragma unroll 1
-        for (uint32_t vb = v0; vb < v1; vb += ELIM_PF) {
-#pragma unroll
-            for (int u = 0; u < ELIM_PF; ++u) {
-                const uint32_t v = vb + u;
-                if (v >= v1) break;
-                double e[NC][DV], C[DV * DV];
-#pragma unroll
-                for (int k = 0; k < NC; ++k)
-#pragma unroll
-                    for (int a2 = 0; a2 < DV; ++a2) e[k][a2] = en[u][k][a2];
-#pragma unroll
-                for (int j = 0; j < DV; ++j)
-#pragma unroll
-                    for (int i = j; i < DV; ++i) C[i + DV * j] = cn[u][i + DV * j];
-                issue(v + ELIM_PF, u);
-                double y[NC][DV];                              // y = (C_v + lambda I)^-1 e
-#pragma unroll
-                for (int k = 0; k < NC; ++k) {
-#pragma unroll
-                    for (int i = 0; i < DV; ++i) { double t = 0;
-#pragma unroll
-                        for (int j = 0; j < DV; ++j) t = fma(i >= j ? C[i + DV * j] : C[j + DV * i], e[k][j], t);
-                        y[k][i] = t; }
-                    if (tid + 64 * k <= nd) {
-#pragma unroll
-                        for (int a2 = 0; a2 < DV; ++a2) { Es[buf][a2][tid + 64 * k] = e[k][a2]; Ys[buf][a2][tid + 64 * k] = y[k][a2]; }
-                    }
-                }
-#pragma unroll
-                for (int a2 = 0; a2 < DV; ++a2) {              // the rhs column: y_b broadcast from its lane
-                    const double ysel = (NC == 2 && kb == 1) ? +y[NC - 1][a2] : +y[0][a2];
-                    const double yb = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ysel), lb), __builtin_amdgcn_readlane(__double2loint(ysel), lb));
-#pragma unroll
-                    for (int k = 0; k < NC; ++k) racc[k] = fma(e[k][a2], yb, racc[k]);
-                }
-                member_barrier();                              // member v published; the other buffer is free for v + 1
-                buf ^= 1;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < NC; ++k) if (tid + 64 * k < nd) rhs_out[tid + 64 * k] = racc[k];
-    } else {
-        // ---- tile waves: one barrier per member, then this thread's 4x4 tile of the rank-DV update
-        int buf = 0;
-#pragma unroll 1
-        for (uint32_t v = v0; v < v1; ++v) {
-            member_barrier();
-            if (has_tile) {
-                double ep[DV][4], yq[DV][4];
-#pragma unroll
-                for (int a2 = 0; a2 < DV; ++a2) {
-                    const double4_t ev = *reinterpret_cast<const double4_t*>(&Es[buf][a2][4 * tp]);
-                    ep[a2][0] = ev[0]; ep[a2][1] = ev[1]; ep[a2][2] = ev[2]; ep[a2][3] = ev[3];
-                    const double4_t yv = *reinterpret_cast<const double4_t*>(&Ys[buf][a2][4 * tq]); yq[a2][0] = yv[0]; yq[a2][1] = yv[1]; yq[a2][2] = yv[2]; yq[a2][3] = yv[3];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        double t = acc[i][j];
-#pragma unroll
-                        for (int a2 = 0; a2 < DV; ++a2) t = fma(ep[a2][i], yq[a2][j], t);
-                        acc[i][j] = t;
-                    }
-            }
-            buf ^= 1;
-        }
-    }
-    // Flush: the register tiles go into the block image in LDS, the image leaves for the supernode's own slab with plain
-    // coalesced stores -- no atomics; schur_gather_kernel sums the shares of all supernodes in a fixed order.
-    if (has_tile) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int p = 4 * tp + i; if (p >= nd) continue;
-            const int A2 = cblk[p], oa = coff[p], dA = bdim[A2];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { const int q = 4 * tq + j; if (q <= p) { const int B2 = cblk[q]; img[poff[A2 * (A2 + 1) / 2 + B2] + oa + dA * coff[q]] = acc[i][j]; } }
-        }
-    }
-    __syncthreads();
-    double* const out = slab + slab_off[blockIdx.x];
-    const int total = poff[nnb * (nnb + 1) / 2] + nd;
-    for (int t = tid; t < total; t += NT) out[t] = img[t];
-}
-
 // Elimination without a barrier per member: FOUR INDEPENDENT wavefronts per supernode, each taking every fourth member and
 // owning a full set of 4x4 register tiles of the supernode's share of S.  A wave loads its members' columns of [E | b] itself
 // (a few members ahead, one column per lane -- every byte of the point rows is requested once, by one wave, and with four
@@ -857,7 +693,8 @@ __global__ __launch_bounds__(64 * (1 + TW)) void schur_elim_slab_kernel(const do
 // in its own LDS buffer (LDS operations of one wave execute in order: no barrier between its stores and its loads) and applies
 // the rank-DV update to its tiles.  The four partial shares are summed through the block image in LDS in wave order
 // (deterministic) and leave for the supernode's slab with plain coalesced stores: one column-major block per pair of neighbour
-// blocks, then the rhs.
+// blocks, then the rhs.  (It replaced a slab variant of the register-tiled elimination above, with one barrier
+// per member; last in the tree at commit 18ea6f9.)
 constexpr int ELIM_NW = 2;
 template <int DV, int NC, int TPL>
 __global__ __launch_bounds__(64 * ELIM_NW) void schur_elim_wave_kernel(const double* __restrict__ A, const double* __restrict__ b,
@@ -1144,112 +981,14 @@ __global__ __launch_bounds__(64) void tiny_dense_trial_kernel(const double* __re
 // ---------------------------------------------------------------------------------------------------
 // blocked Cholesky of the (bordered) reduced system: S col-major, ld = npad, lower triangle
 // ---------------------------------------------------------------------------------------------------
-// diagonal block: unblocked right-looking LDL' in LDS, 256 threads.  On exit the block holds the unit-lower
-// L below the diagonal and D on it.  (LDL' rather than LL': the damped reduced system of a gauge-free
-// bundle adjustment is only barely definite; like the reference's LDLFactorizations, no pivot sign is required.)
-__global__ __launch_bounds__(256) void ldlt_diag_kernel(double* __restrict__ S, int npad, int k, int* __restrict__ status) {
-    __shared__ double M[NB * (NB + 1)];
-    double* D = S + (size_t)k * NB + (size_t)npad * k * NB;
-    const int t = threadIdx.x;
-    for (int e = t; e < NB * NB; e += 256) { const int i = e % NB, j = e / NB; M[i + (NB + 1) * j] = D[(size_t)i + (size_t)npad * j]; }
-    __syncthreads();
-    for (int j = 0; j < NB; ++j) {
-        double d = M[j + (NB + 1) * j];
-        if (d == 0.0 || d != d) { if (t == 0) atomicCAS(status, 0, 1 + k * NB + j); d = 1.0; }
-        const double id = 1.0 / d;
-        // trailing update with the un-scaled column u: M(i,c) -= u_i * u_c / d, j < c <= i
-        const int m = NB - 1 - j;
-        for (int e = t; e < m * m; e += 256) { const int i = j + 1 + e % m, c2 = j + 1 + e / m; if (i >= c2) M[i + (NB + 1) * c2] -= M[i + (NB + 1) * j] * M[c2 + (NB + 1) * j] * id; }
-        __syncthreads();
-        if (t > j && t < NB) M[t + (NB + 1) * j] *= id;
-        if (t == 0) M[j + (NB + 1) * j] = d;
-        __syncthreads();
-    }
-    for (int e = t; e < NB * NB; e += 256) { const int i = e % NB, j = e / NB; if (i >= j) D[(size_t)i + (size_t)npad * j] = M[i + (NB + 1) * j]; }
-}
-// panel: W = A_ik * L_kk^-T (unit diagonal) and L_ik = W * D_k^-1 for each 64-row block i > k; one workgroup
-// (64 threads, thread = row) per block.  L goes back into S, W (= L*D) into the panel workspace for the update.
-__global__ __launch_bounds__(64) void trsm_panel_kernel(double* __restrict__ S, double* __restrict__ W, int npad, int k) {
-    __shared__ double L[NB * (NB + 1)];
-    const double* D = S + (size_t)k * NB + (size_t)npad * k * NB;
-    const int t = threadIdx.x; const int ib = k + 1 + blockIdx.x;
-    for (int e = t; e < NB * NB; e += 64) { const int i = e % NB, j = e / NB; L[i + (NB + 1) * j] = D[(size_t)i + (size_t)npad * j]; }
-    __syncthreads();
-    double* P = S + (size_t)ib * NB + t + (size_t)npad * k * NB;   // row t of the block, stride npad between columns
-    double* Wr = W + (size_t)ib * NB + t;
-    double xr[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) xr[j] = P[(size_t)npad * j];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        double v = xr[j];
-#pragma unroll
-        for (int l = 0; l < j; ++l) v -= xr[l] * L[j + (NB + 1) * l];
-        xr[j] = v;
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) { Wr[(size_t)npad * j] = xr[j]; P[(size_t)npad * j] = xr[j] / L[j + (NB + 1) * j]; }
-}
-// trailing update on the matrix cores: C_ij -= W_i * L_j' (W = L*D) for all k < j <= i; one 64x64 tile per workgroup,
-// 4 waves x (2x2) v_mfma_f64_16x16x4_f64 accumulators.
-__global__ __launch_bounds__(256) void syrk_update_kernel(double* __restrict__ S, const double* __restrict__ W, int npad, int k, int nblk) {
-    __shared__ double Pi[NB * LDT];   // Pi[r + LDT*kk]
-    __shared__ double Pj[NB * LDT];
-    const int T = nblk - k - 1;
-    // linear tile index -> (ti >= tj)
-    int tix = blockIdx.x; int ti = (int)((sqrt(8.0 * tix + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > tix) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= tix) ++ti;
-    const int tj = tix - ti * (ti + 1) / 2;
-    (void)T;
-    const int ib = k + 1 + ti, jb = k + 1 + tj;
-    const double* Gi = W + (size_t)ib * NB;                       // W = L*D rows of block i
-    const double* Gj = S + (size_t)jb * NB + (size_t)npad * k * NB;
-    const int t = threadIdx.x;
-    for (int e = t; e < NB * NB; e += 256) { const int r = e % NB, c2 = e / NB; Pi[r + LDT * c2] = Gi[(size_t)r + (size_t)npad * c2]; Pj[r + LDT * c2] = Gj[(size_t)r + (size_t)npad * c2]; }
-    __syncthreads();
-    const int w = t >> 6, lane = t & 63;
-    const int r0 = (w & 1) * 32, c0 = (w >> 1) * 32;
-    double4_t acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2) acc[a][b2] = double4_t{0, 0, 0, 0};
-    const int li = lane & 15, lk = lane >> 4;
-#pragma unroll 4
-    for (int kk = 0; kk < NB; kk += 4) {
-        double av[2], bv[2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a) av[a] = Pi[r0 + 16 * a + li + LDT * (kk + lk)];
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2) bv[b2] = Pj[c0 + 16 * b2 + li + LDT * (kk + lk)];
-        // the product is formed TRANSPOSED (operands swapped): the accumulator then has the ROW of C on the lane index, and a store
-        // instruction covers 16 consecutive rows of one column of the column-major S (128 contiguous bytes) instead of 16 columns
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b2 = 0; b2 < 2; ++b2) acc[a][b2] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[b2], av[a], acc[a][b2], 0, 0, 0);
-    }
-    // C/D layout of the f64 MFMA: col = lane & 15, row = (lane >> 4) + 4*reg -- of the TRANSPOSED tile: C row = lane & 15
-    double* Cg = S + (size_t)ib * NB + (size_t)npad * jb * NB;
-    double cold[2][2][4];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cold[a][b2][r] = Cg[(size_t)(r0 + 16 * a + li) + (size_t)npad * (c0 + 16 * b2 + lk + 4 * r)];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b2 = 0; b2 < 2; ++b2)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Cg[(size_t)(r0 + 16 * a + li) + (size_t)npad * (c0 + 16 * b2 + lk + 4 * r)] = cold[a][b2][r] - acc[a][b2][r];
-}
+// (Round 1's factorisation -- an unblocked LDL' of the diagonal block, a one-thread-per-row panel solve, a one-panel 64 x 64 trailing update,
+//  and a backward pass of a gemv and a diagonal solve per block -- gave way to dense_panel_kernel and the dense_bwd_* kernels (nlls_bcr.hip)
+//  and the two updates below; last in the tree at commit 18ea6f9.)
 // The trailing update for ONE or TWO panels at a time (NK = 1, 2): C_ij -= sum_q W_{k0+q},i * L_{k0+q},j'.  With two panels per pass every tile of
 // the trailing matrix is read and written half as often -- that read-modify-write of S is what bounds the update (its operands, 3 MB per
 // panel, stay in L2).  narrow != 0: only the block column jb0 (the next panel: all that its factorisation waits for), one workgroup per
-// row block; else the triangle of blocks >= jb0.
+// row block; else the triangle of blocks >= jb0.  (The library launches NK = 2 over the triangle; NK = 1 and narrow served the pass of two
+// 64-column panels, measured slower than the 128-column panels and last in the tree at commit 18ea6f9.)
 template <int NK>
 __global__ __launch_bounds__(256) void syrk_update2_kernel(double* __restrict__ S, const double* __restrict__ W0, const double* __restrict__ W1, int npad, int k0, int jb0, int narrow, int wq = -1, int wstrip = 0) {
     __shared__ double Pi[NB * LDT];   // Pi[r + LDT*kk]
@@ -1287,7 +1026,8 @@ __global__ __launch_bounds__(256) void syrk_update2_kernel(double* __restrict__ 
             for (int a = 0; a < 2; ++a) av[a] = Pi[r0 + 16 * a + li + LDT * (kk + lk)];
 #pragma unroll
             for (int b2 = 0; b2 < 2; ++b2) bv[b2] = Pj[c0 + 16 * b2 + li + LDT * (kk + lk)];
-            // (formed TRANSPOSED, operands swapped: the accumulator then has the ROW of C on the lane index -- see syrk_update_kernel)
+            // the product is formed TRANSPOSED (operands swapped): the accumulator then has the ROW of C on the lane index, and a store
+            // instruction covers 16 consecutive rows of one column of the column-major S (128 contiguous bytes) instead of 16 columns
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -1398,31 +1138,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int r = 0; r < 4; ++r) Cg[(size_t)(16 * a + li) + (size_t)npad * (16 * b2 + lk + 4 * r)] = cold[a][r] - acc[a][b2][r];
     }
 }
-// backward substitution L' x = z (unit diagonal), block by block from the bottom.  z = D^-1 L^-1 s is row n of the factor.
-// step 1 (one workgroup per 64-column block kb, many row blocks): partial[kb][j] = sum_{i > kb block} L[i][kb*64+j] * x[i]
-__global__ __launch_bounds__(256) void bwd_gemv_kernel(const double* __restrict__ S, int npad, int kb, int n, const double* __restrict__ x, double* __restrict__ acc) {
-    // grid.x = number of row blocks below kb; each adds its 64-vector contribution atomically
-    __shared__ double red[4][NB];
-    const int ib = kb + 1 + blockIdx.x; const int t = threadIdx.x; const int j = t & 63, q = t >> 6;
-    const double* P = S + (size_t)ib * NB + (size_t)npad * ((size_t)kb * NB + j);
-    double v = 0;
-    for (int i = q * 16; i < q * 16 + 16; ++i) { const int gi = ib * NB + i; if (gi < n) v += P[i] * x[gi]; }
-    red[q][j] = v; __syncthreads();
-    if (q == 0) atomicAdd(&acc[kb * NB + j], red[0][j] + red[1][j] + red[2][j] + red[3][j]);
-}
-// step 2: x_k = L_kk^-T (y_k - acc_k), single wave
-__global__ __launch_bounds__(64) void bwd_diag_kernel(const double* __restrict__ S, int npad, int kb, int n, const double* __restrict__ acc, double* __restrict__ x) {
-    __shared__ double L[NB * (NB + 1)]; __shared__ double r[NB];
-    const double* D = S + (size_t)kb * NB + (size_t)npad * kb * NB; const int t = threadIdx.x;
-    for (int e = t; e < NB * NB; e += 64) { const int i = e % NB, j = e / NB; L[i + (NB + 1) * j] = D[(size_t)i + (size_t)npad * j]; }
-    const int g = kb * NB + t;
-    r[t] = (g < n) ? S[(size_t)n + (size_t)npad * g] - acc[g] : 0.0;   // y lives in row n of the factor
-    __syncthreads();
-    if (t == 0) for (int i = NB - 1; i >= 0; --i) { if (kb * NB + i >= n) { r[i] = 0; continue; } double v = r[i]; for (int l = i + 1; l < NB && kb * NB + l < n; ++l) v -= L[l + (NB + 1) * i] * r[l]; r[i] = v; }
-    __syncthreads();
-    if (g < n) x[g] = r[t];
-}
-
 // ---------------------------------------------------------------------------------------------------
 // fast_bAb(H + lambda I, v) and dot(b, v)   src/utils.jl:71-106, src/iterators.jl:52,163
 // ---------------------------------------------------------------------------------------------------
@@ -1747,7 +1462,7 @@ static int enqueue_solve_local_t(nlls_ctx* c) {
     // ONE launch for the whole assembly (schur_elim_all_kernel): every eliminated block on the fast path with both kinds of supernode present, one rank,
     // [S | s] carrying the right-hand side as a row (band / dense layouts).  NLLS_ELIM_SPLIT=1 keeps the three launches (A/B).
     const int64_t nfast_narrow = c->n_fast_narrow, nfast_wide = c->n_fast_groups - c->n_fast_narrow;
-    const bool all_in_one = one_prepare && !c->elim_split && c->nranks == 1 && c->elim_mfma && c->n_slow_groups == 0 && nfast_narrow > 0 && nfast_wide > 0 &&
+    const bool all_in_one = one_prepare && !c->elim_split && c->nranks == 1 && c->n_slow_groups == 0 && nfast_narrow > 0 && nfast_wide > 0 &&
                             c->solve_mode != SOLVE_SMALL && c->fast_dv >= 1 && c->fast_dv <= 3 && (int64_t)c->d_elim_diag.n == c->n_fast_members;
     if (all_in_one) {
         if (!c->status_known_zero) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
@@ -1794,15 +1509,11 @@ static int enqueue_solve_local_t(nlls_ctx* c) {
         }
 #define LAUNCH_TILED(DV) do { const int64_t nel = (int64_t)c->d_elim_diag.n; \
             hipLaunchKernelGGL((schur_cinv_kernel<DV>), dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_dim.p, nel, c->lambda, c->Cinv.p, c->d_status.p); \
-            const int64_t n60 = c->n_fast_n60, nnar = c->n_fast_narrow - c->n_fast_n60, nwid = c->n_fast_groups - c->n_fast_narrow;   /* d_fast_groups: nd <= 60, then the other narrow supernodes, then the wide ones */ \
-            if (c->elim_mfma && n60 + nnar > 0 && nwid > 0) { hipLaunchKernelGGL((schur_elim_fused_kernel<DV, LAY>), dim3((unsigned)(n60 + nnar + nwid)), dim3(256), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr(), (uint32_t)(n60 + nnar)); break; } \
-            if (c->elim_mfma) { if (n60 + nnar > 0) hipLaunchKernelGGL((schur_elim_mfma_kernel<DV, LAY>), dim3((unsigned)(n60 + nnar)), dim3(64 * ELIM_MFMA_NW), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); } else { \
-            if (n60 > 0) hipLaunchKernelGGL((schur_elim_tiled_kernel<DV, 1, 2, LAY>), dim3((unsigned)n60), dim3(192), 0, c->stream, c->A.p, c->b.p, \
+            const int64_t nnar = c->n_fast_narrow, nwid = c->n_fast_groups - c->n_fast_narrow;   /* d_fast_groups: the narrow supernodes, then the wide ones */ \
+            if (nnar > 0 && nwid > 0) { hipLaunchKernelGGL((schur_elim_fused_kernel<DV, LAY>), dim3((unsigned)(nnar + nwid)), dim3(256), 0, c->stream, c->A.p, c->b.p, \
+                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr(), (uint32_t)nnar); break; } \
+            if (nnar > 0) hipLaunchKernelGGL((schur_elim_mfma_kernel<DV, LAY>), dim3((unsigned)nnar), dim3(64 * ELIM_MFMA_NW), 0, c->stream, c->A.p, c->b.p, \
                 c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); \
-            if (nnar > 0) hipLaunchKernelGGL((schur_elim_tiled_kernel<DV, 1, 3, LAY>), dim3((unsigned)nnar), dim3(256), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_desc.p + n60, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); } \
             if (nwid > 0) hipLaunchKernelGGL((schur_elim_tiled_kernel<DV, 2, 3, LAY>), dim3((unsigned)nwid), dim3(256), 0, c->stream, c->A.p, c->b.p, \
                 c->d_elim_desc.p + c->n_fast_narrow, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); } while (0)
         if (c->n_fast_groups > 0) {
@@ -1866,7 +1577,7 @@ int enqueue_reduced_solve(nlls_ctx* c) {
             }
             launch_dense_dcopy_all(c->stream, c->S.p, Dfac, npad, NB128, 2 * NB128, 0);
             k = nblk;
-        } else if (c->dense_t128) {
+        } else {
             // 128-column panels (dense_panel_kernel<8, 2>: one launch factors what used to be panel k, a narrow update of block column k + 1 and
             // panel k + 1), each followed by ONE update of everything behind it with K = 128 (128 x 128 tiles; 64 x 64 for the small tail)
             for (; k + 1 < nblk; k += 2) {
@@ -1880,17 +1591,6 @@ int enqueue_reduced_solve(nlls_ctx* c) {
             const int nwide = k / 2;
             if (k < nblk) { launch_dense_panel(c->stream, c->S.p, W0, LiD, npad, k, c->d_status.p, 0, Dfac); ++k; }     // an odd last 64-column panel: nothing behind it
             launch_dense_dcopy_all(c->stream, c->S.p, Dfac, npad, nwide, 2 * nwide, nblk - 2 * nwide);
-        } else {
-            // two 64-column panels per pass: panel k, a NARROW update of block column k + 1 only, panel k + 1, then one update with both (K = 128)
-            for (; k < nblk; k += 2) {
-                launch_dense_panel(c->stream, c->S.p, W0, LiD, npad, k, c->d_status.p, 0, Dfac);
-                if (k + 1 >= nblk) break;
-                hipLaunchKernelGGL(syrk_update2_kernel<1>, dim3(nblk - k - 1), dim3(256), 0, c->stream, c->S.p, W0, W0, npad, k, k + 1, 1);
-                launch_dense_panel(c->stream, c->S.p, W1, LiD, npad, k + 1, c->d_status.p, 0, Dfac);
-                const int T = nblk - k - 2;
-                if (T > 0) hipLaunchKernelGGL(syrk_update2_kernel<2>, dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->S.p, W0, W1, npad, k, k + 2, 0);
-            }
-            launch_dense_dcopy_all(c->stream, c->S.p, Dfac, npad, 0, 0, nblk);
         }
         // backward substitution into acc / s (x)
         if (c->dense_fused_bwd) {

@@ -679,14 +679,14 @@ def test_tile_sparse_ab_switches_still_match_the_oracle(env, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tiny", ["0", "1", "nofinrole"])
+@pytest.mark.parametrize("tiny", ["0", "1"])
 def test_small_dense_system_switch(tiny, monkeypatch):
     """NLLS_TINY_DENSE (read by nlls_create): 1 (default) -- a dense system of fewer than 64 unknowns takes its own route (one image of [A | b] per sweep workgroup summed by
     one gathering launch, no atomics on HBM; the LM trial's damping, factorisation, step statistics and retraction in ONE single-wavefront launch); 0 -- the general dense
     kernels of rounds 1-4.  The same parity either way: a curve fit, a robustified one, and six free cameras over 5000 FIXED points (more variables than the trial launch
-    retracts itself: the retraction in a launch of its own)."""
-    if tiny == "nofinrole": monkeypatch.setenv("NLLS_TINY_FIN_ROLE", "0"); tiny = "1"    # (the trial's finishing reduction in a launch of its own instead of workgroup 0 of the look-ahead sweep)
-    else: monkeypatch.setenv("NLLS_TINY_DENSE", tiny)
+    retracts itself: the retraction in a launch of its own).  On the small-dense route the trial's finishing reduction rides as workgroup 0 of the look-ahead sweep, except on
+    the first trial of every optimisation (no look-ahead sweep behind it): there it takes a launch of its own."""
+    monkeypatch.setenv("NLLS_TINY_DENSE", tiny)
     c, _ = synthetic.create_curvefit_problem(3000, seed=5)
     check_problem(c, expect_sparse=0)
     p = synthetic.perturb_ba_problem(synthetic.create_ba_problem(6, 5000, 0.5, seed=9, robust=N.HuberKernel(0.05)), 1e-3, 1e-3)
@@ -719,12 +719,11 @@ def test_folded_sweep_switch(fold, monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"NLLS_DENSE_T64": "1"}, {"NLLS_DENSE_T128_MIN": "1"}, {"NLLS_ELIM_TILED": "1"}, {"NLLS_BCR_CHROWS_SLOTS": "0"},
+@pytest.mark.parametrize("env", [{"NLLS_DENSE_T128_MIN": "1"}, {"NLLS_BCR_CHROWS_SLOTS": "0"},
                                  {"NLLS_DENSE_STEP_BACKWARD": "1"}, {"NLLS_BCR_LEVEL_BACKWARD": "1"}, {"NLLS_ELIM_SPLIT": "1"}, {"NLLS_POST_SPLIT": "1"},
                                  {"NLLS_HEAVY_MAX_ENTRIES": "256"}, {"NLLS_SUPERNODE_PIECE": "128"}, {"NLLS_SUPERNODE_PIECE": "5"}])
 def test_ab_switches_select_paths_that_still_match_the_oracle(env, monkeypatch):
-    """The environment switches read by nlls_create (the register-tiled elimination instead of the matrix-core one, the
-    64 x 64-tile dense update instead of the 128 x 128 one, the 128 x 128 one from the first pass on, three X rows per panel workgroup at every
+    """The environment switches read by nlls_create (the 128 x 128-tile dense update from the first pass on, three X rows per panel workgroup at every
     level of the block cyclic reduction, one backward launch per block / per level instead of the one-launch substitutions, the assembly in three
     launches, the trial's retraction and step statistics in a launch of their own, the runs of eliminated blocks never cut / cut into pieces of five members) select kernels or launch shapes no default run of this size reaches:
     the same parity as every other path -- band mode and the dense reduced solve (NLLS_FLAG_NO_BAND) of a camera chain, 2100 reduced dof."""
