@@ -15,7 +15,7 @@ int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(wha
 // (every entry point launches on ctx->stream: make the context's device current first -- two contexts on different devices in one
 // process, or a caller that changed the current device, must not end up on a foreign stream)
 #define NEED_READY() do { if (!ctx) return NLLS_ERR_INVALID_ARG; if (!ctx->ready) return fail(ctx, NLLS_ERR_NOT_READY, "nlls_upload_structure has not succeeded"); (void)hipSetDevice(ctx->device); } while (0)
-#define NEED_GRAD_LAZY() do { NEED_READY(); if (!ctx->have_grad) return fail(ctx, NLLS_ERR_NOT_READY, "nlls_sweep_gradhess has not been run"); } while (0)
+#define NEED_GRAD_LAZY() do { NEED_READY(); if (!ctx->lin.have) return fail(ctx, NLLS_ERR_NOT_READY, "nlls_sweep_gradhess has not been run"); } while (0)
 // (... and with the reduced rows summed over ranks: every entry point but the LM trial itself reads them as if one GPU had swept all cost blocks)
 #define NEED_GRAD() do { NEED_GRAD_LAZY(); TRY(ensure_grad(ctx, 2)); TRY(ensure_reduced_summed(ctx)); } while (0)
 #define TRY(expr) do { int rc_ = (expr); if (rc_ != NLLS_OK) return rc_; } while (0)
@@ -27,44 +27,17 @@ int fetch_scalars(nlls_ctx* ctx, int slot, int count) {
     return NLLS_OK;
 }
 bool valid_set(int w) { return w >= 0 && w < 3; }
-// Look-ahead sweep (nlls_ctx::spec_pending): A and b may hold the linearisation at the last trial's point instead of the current one.  Whoever needs them for the
-// CURRENT point comes through here: after the swap of an accepted trial they simply ARE the current point's (a hit); otherwise the current point is swept again (a miss:
-// one accumulate launch, the damping kept) and the look-ahead stays off until the next sweep the caller asks for.
-// `level` (round 6, nlls_ctx::grad_level): 1 -- the reduced rows suffice (the matrix-free LM trial); 2 -- all of A.data and b.  A linearisation that holds less than is asked for
-// is swept (again) here, at CURRENT: the matrix-free trial never forms the eliminated rows, and nlls_sweep_gradhess(ctx, NULL) defers its sweep to the first call that says
-// which level it needs.
+// Whoever needs A and b for the CURRENT point comes through here.  `level` (nlls::Linearisation): 1 -- the reduced rows suffice (the matrix-free LM trial); 2 -- all of
+// A.data and b.  Less than is asked for is swept (again) here, at CURRENT: the matrix-free trial never forms the eliminated rows, and nlls_sweep_gradhess(ctx, NULL) defers it.
 int ensure_grad(nlls_ctx* ctx, int level) {
-    if (ctx->spec_pending) {
-        ctx->spec_pending = false;
-        if (!ctx->spec_stale && ctx->grad_phys == ctx->vars_slot[NLLS_VARS_CURRENT]) ctx->spec_hits++;
-        else { ctx->spec_misses++; ctx->spec_armed = false; ctx->grad_level = 0; }
-        ctx->spec_stale = false;
-    }
-    if (ctx->grad_level >= level && ctx->grad_phys == ctx->vars_slot[NLLS_VARS_CURRENT]) return NLLS_OK;
-    const double lam = ctx->lambda;
-    TRY(enqueue_sweep_gradhess(ctx, false, NLLS_VARS_CURRENT, level == 1 ? 1 : 0));
-    ctx->lambda = lam; ctx->solved = false;
-    return NLLS_OK;
-}
-// a variable set is about to be written: a look-ahead sweep of it is stale, and so is a linearisation at it that is not (fully) formed yet
-int spec_note_write(nlls_ctx* ctx, int32_t which) {
-    ctx->mf_step = false;                                       // (the last matrix-free trial's point and cost are of the sets as they were: its tail is not finished again)
-    if (ctx->vars_slot[which] != ctx->grad_phys) return NLLS_OK;
-    if (ctx->spec_pending) ctx->spec_stale = true;
-    else if (which == NLLS_VARS_CURRENT && ctx->have_grad && ctx->mf_ok) {
-        // CURRENT under the linearisation of the last nlls_sweep_gradhess (include/nlls_amd.h): the trial that follows takes A and b of the values BEFORE this write. What the
-        // matrix-free path has not formed yet is formed now, in stream order ahead of the write, and its trial -- the eliminated rows evaluated at CURRENT -- is off until the
-        // next sweep.  (No LM loop gets here: it writes NEXT, swaps, and sweeps again.)
-        if (ctx->grad_level < 2) { const double lam = ctx->lambda; TRY(enqueue_sweep_gradhess(ctx, false, NLLS_VARS_CURRENT, 0)); ctx->lambda = lam; ctx->solved = false; }
-        ctx->mf_stale_point = true;
-    }
-    else if (ctx->grad_level < 2) ctx->grad_level = 0;          // (what is formed on demand would be formed at the NEW values: the caller sweeps again after writing CURRENT -- every iterator does)
-    return NLLS_OK;
+    lookahead_consume(ctx, true);
+    if (ctx->lin.level >= level && ctx->lin.phys == ctx->vars_slot[NLLS_VARS_CURRENT]) return NLLS_OK;
+    return enqueue_sweep_gradhess(ctx, false, NLLS_VARS_CURRENT, level == 1 ? 1 : 0);
 }
 // phase events (nlls_ctx::phase_on): record event k on the stream
 void phase_mark(nlls_ctx* ctx, int k) { if (ctx->phase_on && (size_t)k < ctx->phase_ev.size()) (void)hipEventRecord(ctx->phase_ev[k], ctx->stream); }
 // is this trial matrix-free?  (nlls_ctx::mf_ok: the structure qualifies; mf_on: not switched off; the trial starts at CURRENT, one rank, no collective route)
-bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->mf_on && !ctx->mf_stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
+bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->mf_on && !ctx->lin.stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
 }  // namespace
 
 extern "C" {
@@ -218,8 +191,8 @@ int nlls_get_bsm_index(const nlls_ctx* ctx, int64_t* colptr, int64_t* rowval, in
 
 int nlls_set_variables(nlls_ctx* ctx, int32_t which, const double* packed) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(which) || !packed) return NLLS_ERR_INVALID_ARG;
-    TRY(spec_note_write(ctx, which));
-    if (which == NLLS_VARS_CURRENT) { ctx->sweeps_since_set = 0; ctx->tb_prev_end = 0.0; }         // (a new starting point: its first trial gets no look-ahead sweep, see nlls_sweep_gradhess)
+    TRY(vars_written(ctx, which));
+    if (which == NLLS_VARS_CURRENT) { new_starting_point(ctx); ctx->tb_prev_end = 0.0; }
     HIPCHK(hipMemcpyAsync(vars_ptr(ctx, which), packed, sizeof(double) * ctx->info.var_storage, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
@@ -239,7 +212,7 @@ int nlls_swap_variables(nlls_ctx* ctx, int32_t a, int32_t b) { NLLS_API_BEGIN
 }
 int nlls_copy_variables(nlls_ctx* ctx, int32_t dst, int32_t src) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(dst) || !valid_set(src)) return NLLS_ERR_INVALID_ARG;
-    if (dst != src) TRY(spec_note_write(ctx, dst));
+    if (dst != src) TRY(vars_written(ctx, dst));
     if (dst != src) HIPCHK(hipMemcpyAsync(vars_ptr(ctx, dst), vars_ptr(ctx, src), sizeof(double) * ctx->info.var_storage, hipMemcpyDeviceToDevice, ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
@@ -250,8 +223,8 @@ int nlls_copy_variables(nlls_ctx* ctx, int32_t dst, int32_t src) { NLLS_API_BEGI
 // the ranks' scalars), so the per-iteration all-reduce of [cost | reduced rows | reduced b] and its pack / unpack launches are skipped.  Whatever else
 // reads them (the initial damping's max |diag|, nlls_get_grad, nlls_solve, ...) sums them first, here: a collective -- every rank makes the same calls.
 static int ensure_reduced_summed(nlls_ctx* ctx) {
-    if (ctx->reduced_summed) return NLLS_OK;
-    ctx->reduced_summed = true;
+    if (ctx->lin.summed) return NLLS_OK;
+    new_linearisation(ctx, true, false);     // (the same linearisation, its reduced rows summed from here on)
     if (!ctx->reduce_fn || ctx->nranks <= 1) return NLLS_OK;
     ctx->n_stage0++;
     TRY(enqueue_pack_reduce0(ctx)); TRY(comm_reduce(ctx, ctx->redbuf.p, ctx->redbuf_len, NLLS_REDUCE_SUM)); TRY(enqueue_unpack_reduce0(ctx, false));
@@ -259,24 +232,8 @@ static int ensure_reduced_summed(nlls_ctx* ctx) {
 }
 int nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out) { NLLS_API_BEGIN
     NEED_READY();
-    // (a sweep the caller asks for: the look-ahead may try again behind the next trial -- but not behind the FIRST trial from a new starting point: the initial damping
-    //  (1e-6 of the largest diagonal entry, src/iterators.jl:131-137) is the one guess of the loop that is routinely rejected -- five times in a row at BASELINE config 5 --,
-    //  and a look-ahead behind it is a sweep thrown away plus the current point swept again)
-    ctx->spec_armed = ctx->sweeps_since_set >= 1; ctx->sweeps_since_set++;
-    ctx->mf_stale_point = false;                 // (a linearisation at CURRENT as it is now: the matrix-free trial applies again)
-    if (ctx->spec_pending) {
-        const bool hit = !cost_out && !ctx->spec_stale && ctx->grad_phys == ctx->vars_slot[NLLS_VARS_CURRENT];
-        ctx->spec_pending = false; ctx->spec_stale = false;
-        if (hit) { ctx->spec_hits++; ctx->lambda = 0.0; ctx->have_grad = true; ctx->solved = false; ctx->reduced_summed = true; return NLLS_OK; }   // already enqueued behind the trial
-        ctx->spec_misses++;
-    }
-    // Matrix-free LM trial (nlls_ctx::mf_ok): between two iterations nothing is enqueued here -- the first call that needs the linearisation says how much of it
-    // (ensure_grad: nlls_lm_trial the reduced rows, everything else all of A.data and b), and it is formed then, at CURRENT.
-    if (!cost_out && mf_trial(ctx, NLLS_VARS_CURRENT)) {
-        ctx->grad_level = 0; ctx->grad_phys = ctx->vars_slot[NLLS_VARS_CURRENT];
-        ctx->lambda = 0.0; ctx->have_grad = true; ctx->solved = false; ctx->reduced_summed = true; ctx->tE_valid = false; ctx->step_cached = false;
-        return NLLS_OK;
-    }
+    if (sweep_asked(ctx, cost_out != nullptr)) { new_linearisation(ctx); return NLLS_OK; }   // (already enqueued behind the trial)
+    if (!cost_out && mf_trial(ctx, NLLS_VARS_CURRENT)) { defer_linearisation(ctx); return NLLS_OK; }
     // cost_out == NULL: the caller does not want the cost (the outer loop between iterations, src/optimize.jl:167-170
     // discards it) -- the sweep is then only enqueued: no partial-sum kernel, no synchronisation
     if (ctx->reduce_fn) {
@@ -288,8 +245,7 @@ int nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out) { NLLS_API_BEGIN
         }
         TRY(enqueue_sweep_gradhess(ctx, !lazy));
         if (ctx->phase_on && ctx->phase_ev.size() >= 8) (void)hipEventRecord(ctx->phase_ev[7], ctx->stream);
-        ctx->lambda = 0.0; ctx->have_grad = true; ctx->solved = false;
-        ctx->reduced_summed = !lazy;
+        new_linearisation(ctx, !lazy);
         if (lazy) return NLLS_OK;                                            // nothing is summed now: ensure_reduced_summed, or never
         if (ctx->nranks > 1) { ctx->n_stage0++; TRY(enqueue_pack_reduce0(ctx)); TRY(comm_reduce(ctx, ctx->redbuf.p, ctx->redbuf_len, NLLS_REDUCE_SUM)); TRY(enqueue_unpack_reduce0(ctx, true)); }
         else TRY(comm_reduce(ctx, ctx->scalars.p, 1, NLLS_REDUCE_SUM));      // (one rank through the route: the same number of collectives)
@@ -301,7 +257,7 @@ int nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out) { NLLS_API_BEGIN
     const bool mfcost = cost_out && mf_trial(ctx, NLLS_VARS_CURRENT);
     TRY(enqueue_sweep_gradhess(ctx, cost_out != nullptr && !mfcost));
     if (mfcost) TRY(enqueue_mf_sweep_cost(ctx, NLLS_VARS_CURRENT));
-    ctx->lambda = 0.0; ctx->have_grad = true; ctx->solved = false; ctx->reduced_summed = true;
+    new_linearisation(ctx);
     if (!cost_out) return NLLS_OK;
     TRY(fetch_scalars(ctx, 0, 1));
     *cost_out = ctx->h_scalars[0];
@@ -363,16 +319,15 @@ int nlls_solve(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     TRY(enqueue_solve(ctx));
     // what the iterators ask about the step next -- max |x|, |x|, x'Hx, g'x (src/optimize.jl:149, src/iterators.jl:160-163) --
     // is computed behind the solve and comes back with the same synchronisation; the queries then answer from the host
-    ctx->step_cached = false;
+    drop(ctx->step.cached);
     const bool precompute = ctx->nranks == 1;
-    if (precompute) { TRY(enqueue_post_solve(ctx)); }
+    if (precompute) { TRY(enqueue_post_solve(ctx, ctx->stamp_ptr())); }
     int32_t status[4] = {0, 0, 0, 0};
     if (precompute) HIPCHK(hipMemcpyAsync(ctx->h_scalars + 1, ctx->scalars.p + 1, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->stream));   // ... and the status in [10]
     else HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     if (x_out) HIPCHK(hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->solved = true;
-    if (precompute) { status[0] = (int32_t)ctx->h_scalars[10]; ctx->step_cached = true; ctx->c_maxabs = ctx->h_scalars[1]; ctx->c_sumsq = ctx->h_scalars[2]; ctx->c_gx = ctx->h_scalars[5]; ctx->c_xAx = ctx->h_scalars[8]; ctx->c_xx = ctx->h_scalars[9]; }
+    if (precompute) { status[0] = (int32_t)ctx->h_scalars[10]; step_solved(ctx, false); }
     if (status[0] != 0) return status_error(ctx, status[0], "factorisation met a non-positive pivot");
     return NLLS_OK;
     NLLS_API_END(ctx)
@@ -387,12 +342,12 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
     if (!collective) TRY(ensure_reduced_summed(ctx));
     if (ctx->nranks != 1 && !collective) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_lm_trial under nlls_set_shard needs an all-reduce (nlls_comm_init_rccl / nlls_set_allreduce), or the *_local / *_finish pairs");
     ctx->lambda += dlambda;
-    ctx->step_cached = false;
+    drop(ctx->step.cached);
     if (collective) {
         // the sharded trial, end to end on this rank's stream: local elimination, ONE sum of [S | s] over ranks, the reduced system solved on
         // every rank (each then holds the reduced part of the step: x is never summed), own back-substitution, retraction, own cost blocks,
         // and one gather of the ranks' scalars -- combined on the device and published to the host mirror as the single-GPU trial does
-        if (ctx->nranks > 1 && !ctx->reduced_summed) ctx->n_lazy_trials++;
+        if (ctx->nranks > 1 && !ctx->lin.summed) ctx->n_lazy_trials++;
         phase_mark(ctx, 0);
         TRY(enqueue_solve_local(ctx));
         phase_mark(ctx, 1);
@@ -403,33 +358,31 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
             TRY(comm_reduce(ctx, ctx->S.p + ctx->s_elems, ctx->nred, NLLS_REDUCE_SUM));
         } else TRY(comm_reduce(ctx, ctx->S.p, (int64_t)ctx->s_elems + ctx->nred, NLLS_REDUCE_SUM));
         phase_mark(ctx, 2);
-        if (ctx->nranks == 1) { ctx->trial_to = to; ctx->trial_from = from; }      // (one rank through the route: the same launches as the unsharded trial)
-        ctx->replicate_xr = true; int rc = enqueue_solve_finish(ctx); ctx->replicate_xr = false; ctx->trial_to = ctx->trial_from = -1; TRY(rc);
+        // (one rank through the route: the same launches as the unsharded trial; no mirror: the host waits on the gathered scalars, not on this rank's)
+        const TrialArgs t{.to = to, .from = from, .replicate_xr = true};
+        TRY(enqueue_solve_finish(ctx, t));
         phase_mark(ctx, 4);
-        double* const mirror = ctx->h_scalars_dev; ctx->h_scalars_dev = nullptr;           // (the rank's own scalars are not what the host waits for)
-        rc = enqueue_lm_trial_tail(ctx, to, from); ctx->h_scalars_dev = mirror; TRY(rc);
+        TRY(enqueue_lm_trial_tail(ctx, t));
         TRY(comm_gather_trial_scalars(ctx, (double)ctx->trial_seq));
         phase_mark(ctx, 5);
     } else if (ctx->tiny_dense) {
-        const bool la = ctx->spec_on && ctx->spec_armed && from == NLLS_VARS_CURRENT;
-        TRY(enqueue_tiny_dense_trial(ctx, to, from, la));
-        if (la) { TRY(enqueue_sweep_gradhess(ctx, false, to)); ctx->spec_pending = true; ctx->spec_stale = false; }
-        TRY(enqueue_tiny_trial_finish_pending(ctx));      // (no accumulate launch took the finishing reduction along)
+        const bool la = ctx->spec_on && ctx->ahead.armed && from == NLLS_VARS_CURRENT;
+        TRY(enqueue_tiny_dense_trial(ctx, to, from));
+        if (la) TRY(enqueue_lookahead(ctx, to, 0));
+        TRY(enqueue_tiny_trial_finish_pending(ctx));      // (the finishing reduction, unless the look-ahead sweep's accumulate launch took it along)
     } else {
     { double* st = ctx->h_scalars + 40; st[0] = st[1] = st[2] = st[3] = 0.0; }       // (the launches of this trial stamp them: device-timed buckets)
-    ctx->trial_to = to; ctx->trial_from = from;    // (the back-substitution launch may take the retraction with it: enqueue_solve_finish)
-    ctx->mf_use = mf; if (mf) ctx->mf_trials++;
-    { const int rc = enqueue_solve(ctx); ctx->trial_to = ctx->trial_from = -1; ctx->mf_use = false; TRY(rc); }
-    const bool la = ctx->spec_on && ctx->spec_armed && ctx->nranks == 1 && ctx->info.is_sparse && from == NLLS_VARS_CURRENT;
-    ctx->tail_zero_for_lookahead = la; ctx->heavy_rows_zeroed = false;
+    TrialArgs t{.to = to, .from = from, .mf = mf, .mirror = ctx->h_scalars_dev}; ctx->mf_trials += mf;    // (the back-substitution launch may take the retraction with it)
+    TRY(enqueue_solve(ctx, t));
+    const bool la = ctx->spec_on && ctx->ahead.armed && ctx->nranks == 1 && ctx->info.is_sparse && from == NLLS_VARS_CURRENT;
     // (matrix-free trial with a look-ahead sweep behind it: the trial's finishing workgroup rides in that sweep's launch -- nlls_sweep.hip -- unless rows have to be zeroed in between)
-    ctx->mf_fin_defer = mf && la && ctx->nzero == 0; ctx->mf_fin_pending = false;
-    { const int rc = enqueue_lm_trial_tail(ctx, to, from); ctx->tail_zero_for_lookahead = false; ctx->mf_fin_defer = false; TRY(rc); }     // step statistics + quadratic form (+ retraction) and the cost sweep, one finishing launch
-    // the look-ahead sweep: the gradient sweep of the trial point, enqueued behind the finishing launch (the host reads the trial's scalars while it runs)
-    if (la) { const int rc = enqueue_sweep_gradhess(ctx, false, to, mf ? 1 : 0); ctx->heavy_rows_zeroed = false; TRY(rc); ctx->spec_pending = true; ctx->spec_stale = false; }
-    if (ctx->mf_fin_pending) TRY(enqueue_mf_trial_finish_now(ctx));      // (no launch of the sweep took the finishing workgroup along)
+    t.zero_for_lookahead = la; t.defer_fin = mf && la && ctx->nzero == 0;
+    drop(ctx->zero.heavy_rows); drop(ctx->fin.mf_pending);   // (left over only by a trial that failed in between)
+    TRY(enqueue_lm_trial_tail(ctx, t));            // step statistics + quadratic form (+ retraction) and the cost sweep, one finishing launch
+    if (la) TRY(enqueue_lookahead(ctx, to, mf ? 1 : 0));
+    if (take(ctx->fin.mf_pending)) TRY(enqueue_mf_trial_finish_now(ctx, t));      // (no launch of the sweep took the finishing workgroup along)
     }
-    // (sparse systems: the finishing launch has written the scalars -- in [10] the factorisation status -- to the pinned host mirror itself)
+    // (sparse systems: the finishing launch -- TrialArgs::mirror, or comm_gather_trial_scalars -- has written the scalars, in [10] the status, to the pinned host mirror)
     if ((!ctx->info.is_sparse && !ctx->tiny_dense) || !ctx->h_scalars_dev) {
         HIPCHK(hipMemcpyAsync(ctx->h_scalars, ctx->scalars.p, sizeof(double) * 12, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -466,9 +419,7 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
     const int32_t status[1] = {(int32_t)ctx->h_scalars[10]};
     ctx->comm_gathered = collective;
     if (collective) ctx->comm_agreed = ctx->h_scalars[11];      // the ranks' posted termination flags, combined by maximum in the same gather (nlls_comm_agreed_flag)
-    ctx->status_known_zero = status[0] == 0;       // (nothing has touched the device's status word since: the next solve need not reset it)
-    ctx->solved = true;
-    ctx->step_cached = true; ctx->c_maxabs = ctx->h_scalars[1]; ctx->c_sumsq = ctx->h_scalars[2]; ctx->c_gx = ctx->h_scalars[5]; ctx->c_xAx = ctx->h_scalars[8]; ctx->c_xx = ctx->h_scalars[9];
+    step_solved(ctx, true);
     if (status[0] != 0) return status_error(ctx, status[0], "factorisation met a non-positive pivot");
     if (cost_out) *cost_out = ctx->h_scalars[0];
     return NLLS_OK;
@@ -480,7 +431,7 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
 // nlls_set_shard the first three are this rank's PARTIAL sums (the caller adds them over ranks), the last two are global.
 int nlls_trial_local(nlls_ctx* ctx, int32_t to, int32_t from, double* out) { NLLS_API_BEGIN
     NEED_GRAD(); if (!valid_set(to) || !valid_set(from) || to == from) return NLLS_ERR_INVALID_ARG;
-    TRY(enqueue_lm_trial_tail(ctx, to, from));     // step statistics + quadratic form + retraction in one launch, the cost sweep, one finishing launch
+    TRY(enqueue_lm_trial_tail(ctx, TrialArgs{.to = to, .from = from, .mirror = ctx->h_scalars_dev}));     // step statistics + quadratic form + retraction in one launch, the cost sweep, one finishing launch
     if (!out) return NLLS_OK;                      // enqueue only: the eleven scalars stay on the device (reduce buffer 3) for a device-side gather
     HIPCHK(hipMemcpyAsync(ctx->h_scalars, ctx->scalars.p, sizeof(double) * 11, hipMemcpyDeviceToHost, ctx->stream));   // [10]: the factorisation status
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -498,9 +449,7 @@ int nlls_trial_local(nlls_ctx* ctx, int32_t to, int32_t from, double* out) { NLL
 }
 // nlls_solve_finish_async for a sharded LM trial: the reduced part of the step stays on every rank (no stage-2 reduction afterwards)
 int nlls_solve_finish_replicated(nlls_ctx* ctx) { NLLS_API_BEGIN
-    NEED_GRAD(); ctx->replicate_xr = true; const int rc = enqueue_solve_finish(ctx); ctx->replicate_xr = false;
-    if (rc != NLLS_OK) return rc;
-    ctx->solved = true; ctx->step_cached = false; return NLLS_OK;
+    NEED_GRAD(); TRY(enqueue_solve_finish(ctx, TrialArgs{.replicate_xr = true})); drop(ctx->step.cached); return NLLS_OK;
     NLLS_API_END(ctx)
 }
 // this rank's share of a variable set: its own eliminated blocks' variables, on rank 0 also everything else; zeros elsewhere --
@@ -570,8 +519,7 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
     if (nloc > 0) { HIPCHK(d_sel.upload(sel)); HIPCHK(d_cptr.upload(cp)); HIPCHK(d_cgroup.upload(cg)); HIPCHK(d_cslot.upload(cs)); HIPCHK(d_cidx.upload(cidx)); HIPCHK(d_iters.alloc((size_t)nloc)); }
     HIPCHK(d_groups.upload(gbuf));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->have_grad = false; ctx->solved = false; ctx->step_cached = false; ctx->tE_valid = false;   // the variables change under the linear system
-    TRY(spec_note_write(ctx, NLLS_VARS_CURRENT)); ctx->spec_pending = false; ctx->spec_stale = false; ctx->grad_level = 0;   // (... and under a look-ahead sweep of this very set: its A and b are of the point before the relaxation)
+    vars_written(ctx, NLLS_VARS_CURRENT, true);
     if (nloc > 0) TRY(enqueue_optimize_singles(ctx, nloc, d_sel.p, d_cptr.p, d_cgroup.p, d_cidx.p, d_cslot.p, d_groups.p, iterator, maxiters, maxfails, reldcost, absdcost, dstep, d_iters.p));
     if (!sharded) {
         if (iters_out) HIPCHK(hipMemcpyAsync(iters_out, d_iters.p, sizeof(int64_t) * nsel, hipMemcpyDeviceToHost, ctx->stream));      // (unsharded: nloc == nsel, the caller's order)
@@ -630,7 +578,7 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
-                              ctx->spec_hits, ctx->spec_misses /* look-ahead sweeps used / thrown away */,
+                              ctx->ahead.hits, ctx->ahead.misses /* look-ahead sweeps used / thrown away */,
                               ctx->mf_trials, ctx->mf_reduced_sweeps, ctx->full_sweeps /* matrix-free LM trials, sweeps of the reduced rows only, full accumulate sweeps since the upload */,
                               ctx->bcr.ready ? 16 * ctx->bcr.NT : 0 /* unknowns per block of the block cyclic reduction */};
     for (int i = 0; i < n && i < 27; ++i) out[i] = vals[i];
@@ -639,7 +587,7 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
 }
 int nlls_set_step(nlls_ctx* ctx, const double* x) { NLLS_API_BEGIN
     NEED_READY(); if (!x) return NLLS_ERR_INVALID_ARG;
-    ctx->tE_valid = false; ctx->step_cached = false; ctx->mf_step = false;   // the step is no longer the one the last solve produced (nor are the matrix-free trial's partials of it)
+    step_replaced(ctx);
     HIPCHK(hipMemcpyAsync(ctx->x.p, x, sizeof(double) * ctx->info.ndof, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
@@ -653,20 +601,20 @@ int nlls_get_step(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     NLLS_API_END(ctx)
 }
 int nlls_step_maxabs(nlls_ctx* ctx, double* out) { NLLS_API_BEGIN
-    NEED_READY(); if (ctx->step_cached) { if (out) *out = ctx->c_maxabs; return NLLS_OK; }
+    NEED_READY(); if (ctx->step.cached) { if (out) *out = ctx->step.maxabs; return NLLS_OK; }
     TRY(enqueue_step_stats(ctx)); TRY(fetch_scalars(ctx, 1, 2));
     if (out) *out = ctx->h_scalars[1]; return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_step_norm(nlls_ctx* ctx, double* out) { NLLS_API_BEGIN
-    NEED_READY(); if (ctx->step_cached) { if (out) *out = std::sqrt(ctx->c_sumsq); return NLLS_OK; }
+    NEED_READY(); if (ctx->step.cached) { if (out) *out = std::sqrt(ctx->step.sumsq); return NLLS_OK; }
     TRY(enqueue_step_stats(ctx)); TRY(fetch_scalars(ctx, 1, 2));
     if (out) *out = std::sqrt(ctx->h_scalars[2]); return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_quadform(nlls_ctx* ctx, double* xHx_out, double* gx_out) { NLLS_API_BEGIN
     NEED_GRAD_LAZY();
-    if (ctx->step_cached) { if (xHx_out) *xHx_out = ctx->c_xAx + ctx->lambda * ctx->c_xx; if (gx_out) *gx_out = ctx->c_gx; return NLLS_OK; }   // damping may have changed since
+    if (ctx->step.cached) { if (xHx_out) *xHx_out = ctx->step.xAx + ctx->lambda * ctx->step.xx; if (gx_out) *gx_out = ctx->step.gx; return NLLS_OK; }   // damping may have changed since
     TRY(ensure_grad(ctx, 2)); TRY(ensure_reduced_summed(ctx));
     TRY(enqueue_quadform(ctx, ctx->x.p, 4)); TRY(comm_reduce(ctx, ctx->scalars.p + 4, 2, NLLS_REDUCE_SUM)); TRY(fetch_scalars(ctx, 4, 2));
     if (xHx_out) *xHx_out = ctx->h_scalars[4]; if (gx_out) *gx_out = ctx->h_scalars[5];
@@ -675,7 +623,7 @@ int nlls_quadform(nlls_ctx* ctx, double* xHx_out, double* gx_out) { NLLS_API_BEG
 }
 int nlls_retract(nlls_ctx* ctx, int32_t to, int32_t from) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(to) || !valid_set(from) || to == from) return NLLS_ERR_INVALID_ARG;
-    TRY(spec_note_write(ctx, to));
+    TRY(vars_written(ctx, to));
     return enqueue_retract(ctx, to, from);
     NLLS_API_END(ctx)
 }
@@ -684,8 +632,8 @@ int nlls_retract(nlls_ctx* ctx, int32_t to, int32_t from) { NLLS_API_BEGIN
 //   nlls_sweep_cost / nlls_quadform / nlls_max_abs_diag / nlls_grad_* return this rank's PARTIAL values (the caller
 //   sums, or takes the max of, them over ranks); the *_local / *_finish pairs bracket the buffer reductions.
 int nlls_sweep_gradhess_local(nlls_ctx* ctx) { NLLS_API_BEGIN
-    NEED_READY(); ctx->spec_pending = false; ctx->spec_stale = false; ctx->mf_stale_point = false; TRY(enqueue_sweep_gradhess(ctx));
-    ctx->lambda = 0.0; ctx->have_grad = true; ctx->solved = false; ctx->reduced_summed = true;     // (the caller sums the reduce buffer)
+    NEED_READY(); drop_lookahead(ctx, true); TRY(enqueue_sweep_gradhess(ctx));
+    new_linearisation(ctx);                          // (the caller sums the reduce buffer)
     if (ctx->nranks > 1) TRY(enqueue_pack_reduce0(ctx));
     return NLLS_OK;                                  // enqueue only: the reduce buffer is complete in stream order
     NLLS_API_END(ctx)
@@ -710,13 +658,12 @@ int nlls_solve_finish(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     if (x_out) HIPCHK(hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->solved = true;
     if (status[0] != 0) return status_error(ctx, status[0], "factorisation met a zero pivot");
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_solve_finish_async(nlls_ctx* ctx) { NLLS_API_BEGIN           // enqueue only: the status comes home with nlls_trial_local's scalars
-    NEED_GRAD(); TRY(enqueue_solve_finish(ctx)); ctx->solved = true; ctx->step_cached = false; return NLLS_OK;
+    NEED_GRAD(); TRY(enqueue_solve_finish(ctx)); drop(ctx->step.cached); return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_get_reduce_buffer(nlls_ctx* ctx, int32_t stage, void** dev_ptr, int64_t* count) { NLLS_API_BEGIN
@@ -770,16 +717,12 @@ static int time_loop(nlls_ctx* ctx, int reps, float* ms_avg, int (*fn)(nlls_ctx*
     return NLLS_OK;
 }
 
+// (the timed sweeps leave A and b the linearisation at CURRENT, outside the look-ahead protocol and with the damping kept)
+static int time_sweeps(nlls_ctx* ctx, int reps, float* ms_avg, int (*fn)(nlls_ctx*)) { drop_lookahead(ctx, false); int rc = time_loop(ctx, reps, ms_avg, fn); new_linearisation(ctx, true, false); return rc; }
 int nlls_time_sweep_gradhess(nlls_ctx* ctx, int32_t reps, float* ms_avg) { NLLS_API_BEGIN
-    NEED_READY(); ctx->spec_pending = false; ctx->spec_stale = false; int rc = time_loop(ctx, reps, ms_avg, [](nlls_ctx* c) { return enqueue_sweep_gradhess(c); });
-    ctx->have_grad = true; ctx->reduced_summed = true; return rc;
-    NLLS_API_END(ctx)
-}
+    NEED_READY(); return time_sweeps(ctx, reps, ms_avg, [](nlls_ctx* c) { return enqueue_sweep_gradhess(c); }); NLLS_API_END(ctx) }
 int nlls_time_sweep_accumulate(nlls_ctx* ctx, int32_t reps, float* ms_avg) { NLLS_API_BEGIN
-    NEED_READY(); ctx->spec_pending = false; ctx->spec_stale = false; int rc = time_loop(ctx, reps, ms_avg, [](nlls_ctx* c) { return enqueue_sweep_gradhess(c, false); });
-    ctx->have_grad = true; ctx->reduced_summed = true; return rc;
-    NLLS_API_END(ctx)
-}
+    NEED_READY(); return time_sweeps(ctx, reps, ms_avg, [](nlls_ctx* c) { return enqueue_sweep_gradhess(c, false); }); NLLS_API_END(ctx) }
 int nlls_time_sweep_cost(nlls_ctx* ctx, int32_t reps, float* ms_avg) { NLLS_API_BEGIN
     NEED_READY(); return time_loop(ctx, reps, ms_avg, [](nlls_ctx* c) { return enqueue_sweep_cost(c, NLLS_VARS_CURRENT); });
     NLLS_API_END(ctx)
@@ -886,14 +829,14 @@ int nlls_time_reduced_solve(nlls_ctx* ctx, int32_t reps, float* ms_avg) { NLLS_A
         // block cyclic reduction copies [S | s] into its own tiles: assemble once, then time the factorisation + backward pass alone
         TRY(enqueue_solve_local(ctx));
         const int rc = time_loop(ctx, reps, ms_avg, [](nlls_ctx* c) { return enqueue_reduced_solve(c); });
-        ctx->S_zeroed = false; ctx->solved = false;
+        drop(ctx->zero.S);
         return rc;
     }
     // the dense, one-wave and chain solvers factor S IN PLACE: every repetition assembles it again, and the assembly alone is timed and subtracted
     float ms_both = 0.f, ms_asm = 0.f;
-    int rc = time_loop(ctx, reps, &ms_both, [](nlls_ctx* c) { c->S_zeroed = false; int r = enqueue_solve_local(c); return r != NLLS_OK ? r : enqueue_reduced_solve(c); });
-    if (rc == NLLS_OK) rc = time_loop(ctx, reps, &ms_asm, [](nlls_ctx* c) { c->S_zeroed = false; return enqueue_solve_local(c); });
-    ctx->S_zeroed = false; ctx->solved = false;
+    int rc = time_loop(ctx, reps, &ms_both, [](nlls_ctx* c) { drop(c->zero.S); int r = enqueue_solve_local(c); return r != NLLS_OK ? r : enqueue_reduced_solve(c); });
+    if (rc == NLLS_OK) rc = time_loop(ctx, reps, &ms_asm, [](nlls_ctx* c) { drop(c->zero.S); return enqueue_solve_local(c); });
+    drop(ctx->zero.S);
     if (ms_avg) *ms_avg = ms_both > ms_asm ? ms_both - ms_asm : 0.f;
     return rc;
     NLLS_API_END(ctx)

@@ -180,6 +180,22 @@ struct GatherJob {
 // (rhs segments: b_v at b + aux), the inverse at Cinv + cinv
 struct GatherCon { uint32_t off, ld, aux, cinv; };
 
+// ---- what the device buffers are known to hold (nlls_state.hpp: the events that change it) ------------------------------------------------------------
+// A and b are the linearisation at physical variable slot `phys`, formed to `level` (0 nothing, 1 the reduced rows, the matrix-free trial's share, 2 everything); `have`:
+// the caller asked for one since the upload; `summed`: the reduced rows are summed over ranks (not after a lazy collective sweep); `stale_point`: CURRENT was written since.
+struct Linearisation { bool have = false; int phys = -1; int level = 0; bool summed = true; bool stale_point = false; };
+// Look-ahead sweep (round 5): nlls_lm_trial sweeps the TRIAL point behind its own launches, so that an accepted trial finds A and b already computed.  `pending`: A and b
+// are that sweep's; `stale`: its set was written since; `armed`: a look-ahead may follow the next trial; sweeps_since_set: since nlls_set_variables(CURRENT).
+struct Lookahead { bool pending = false, stale = false, armed = true; int64_t hits = 0, misses = 0, sweeps_since_set = 0; };
+// The step in x: `cached` -- the host holds its statistics (max|x|, x'x, g'x, x'Ax, x'x over this rank's share); `tE_valid` -- tE holds E_v s of it; `mf` -- a matrix-free
+// trial's, retracted mf_from_phys -> mf_to_phys, its cost and statistics left as rows of partials in mf_q; `retract_done` -- the back-substitution launch retracted it.
+struct StepState { bool cached = false; double maxabs = 0, sumsq = 0, gx = 0, xAx = 0, xx = 0; bool tE_valid = false, mf = false; int mf_to_phys = -1, mf_from_phys = -1; bool retract_done = false; };
+// Scratch known to be zero, so that its next writer skips the memset: S and the tiles the gather writes into (the last back-substitution zero-filled them), the
+// status word (read as 0 by the host, untouched since), the rows of a look-ahead sweep (zero-filled by the trial's finishing launch in front of it).
+struct KnownZero { bool S = false, tiles = false, status = false, heavy_rows = false; };
+// Finishing work waiting for the look-ahead sweep's launch to carry it: the small dense system's finishing reduction `dense`, a matrix-free trial's finishing workgroup.
+struct Deferred { DenseFin dense{}; bool dense_pending = false, mf_pending = false; };
+
 }  // namespace nlls
 
 struct nlls_ctx {
@@ -236,23 +252,13 @@ struct nlls_ctx {
     double* h_scalars_dev = nullptr;         // ... as the device sees it (the trial's finishing launch writes the scalars there itself)
     int64_t npartials = 0;
     double lambda = 0.0;                     // accumulated uniformscaling! (src/iterators.jl:149,162)
-    // Look-ahead sweep (round 5): nlls_lm_trial enqueues the gradient sweep of the TRIAL point behind the trial's own launches, before the host has seen the trial's cost --
-    // the accepted path (swap CURRENT <-> NEXT, nlls_sweep_gradhess(ctx, NULL)) then finds A and b already being computed and the GPU does not idle through the host's
-    // turn-around; a rejected trial (the next nlls_lm_trial without a swap) sweeps the current point again first.  Transparent: same kernels, same data, same results.
-    int grad_phys = -1;                      // physical variable slot A and b are the linearisation of
-    bool spec_on = true, spec_pending = false, spec_stale = false, spec_armed = true;   // spec_on: NLLS_NO_LOOKAHEAD_SWEEP unset; pending: A, b belong to grad_phys, not (yet) to CURRENT; stale: that slot was written since; armed: the last look-ahead was used (a miss disarms until the next real sweep)
-    int64_t spec_hits = 0, spec_misses = 0;  // nlls_get_solve_stats
-    int64_t sweeps_since_set = 0;            // gradient sweeps the caller has asked for since nlls_set_variables(CURRENT)
-    bool tail_zero_for_lookahead = false, heavy_rows_zeroed = false;   // the look-ahead sweep's zero fill in the trial's finishing launch (trial_finish_kernel)
+    // validity state (nlls_ctx.hpp above; assigned by nlls_state.hpp alone)
+    nlls::Linearisation lin; nlls::Lookahead ahead; nlls::StepState step; nlls::KnownZero zero; nlls::Deferred fin;
+    bool spec_on = true;                     // the look-ahead sweep (nlls::Lookahead): NLLS_NO_LOOKAHEAD_SWEEP unset, NLLS_OPT_LOOKAHEAD
     // the small dense system (fewer than 64 unknowns, nothing eliminated, one rank: curve fits, Rosenbrock): the sweep leaves one image of [A | b] per workgroup in
     // dense_slab and ONE gathering launch sums them (no zero fill, no atomics on HBM, no mirror launch); an LM trial is one single-workgroup launch for
     // damping + factorisation + step statistics + retraction, then the cost sweep.  NLLS_TINY_DENSE=0 keeps the general kernels (A/B)
     bool tiny_dense = false, tiny_dense_on = true; nlls::DevBuf<double> dense_slab; int64_t dense_slab_wgs = 0, dense_slab_used = 0;
-    // An LM trial followed by its look-ahead sweep is FOUR launches: [damped solve + statistics + retraction] (one wavefront), the cost sweep, [the finishing reduction as
-    // workgroup 0 + the look-ahead accumulate sweep], the gather.  dense_fin: a finishing reduction waiting for the accumulate launch that carries it (without a look-ahead
-    // sweep behind the trial -- the first trial from a new start, or the look-ahead off -- it runs in a launch of its own)
-    nlls::DenseFin dense_fin{}; bool dense_fin_pending = false;
-    bool have_grad = false;
     // Device-timed NLLSResult buckets (round 6; src/structs.jl:37-50, filled at src/iterators.jl:152,157): the launches of an LM trial leave the constant clock (100 MHz) in the pinned
     // mirror -- h_scalars[40] start of the assembly launch, [41] of the back-substitution, [42] start of the cost launch (matrix-free trial: of the finishing workgroup; the cost rides in
     // the back-substitution), [43] end of the finishing workgroup -- one thread each, off every critical path.  nlls_lm_trial turns them into nanoseconds: solver [40]..[42], cost
@@ -264,23 +270,17 @@ struct nlls_ctx {
     double* stamp_ptr() const { return h_scalars_dev ? h_scalars_dev + 40 : nullptr; }
     // Matrix-free LM trial (round 6; nlls_mf.hip).  Two-slot Schur problems whose eliminated blocks all sit on the fast path: nlls_lm_trial evaluates the cost blocks of every
     // supernode inside the elimination launch and again inside the back-substitution launch -- the point rows of A.data (151 of its 151.5 MB at BASELINE config 4) are never
-    // written or read by the loop.  What stays materialised is the reduced rows (camera diagonal blocks, their part of b: what `grad_level` 1 means) -- the gradient sweep between
+    // written or read by the loop.  What stays materialised is the reduced rows (camera diagonal blocks, their part of b: what `lin.level` 1 means) -- the gradient sweep between
     // two iterations shrinks to the reduced slot's pass; b's eliminated part is written by the elimination launch itself.  A.data in the reference's layout is formed on demand:
     // every entry point that reads it (nlls_get_bsm_data, nlls_solve, nlls_max_abs_diag, ...) sweeps in full first (ensure_grad level 2).  NLLS_FLAG_MATERIALIZE / NLLS_MATERIALIZE=1 /
     // nlls_set_option(NLLS_OPT_MATERIALIZE): the round-5 path.
     bool mf_ok = false, mf_on = true; int mf_group = -1, mf_ps = -1;     // eligibility (build_mf), run-time switch, the cost group and its eliminated slot
-    int grad_level = 0;                      // what A and b hold of the linearisation at grad_phys: 0 nothing, 1 the reduced rows, 2 everything
-    bool mf_stale_point = false;             // CURRENT was written after the linearisation the caller asked for: A and b hold it whole (formed before the write), the matrix-free
-                                             // trial -- which evaluates the eliminated rows at CURRENT -- stays off until the next nlls_sweep_gradhess
-    int mf_to_phys = -1, mf_from_phys = -1;  // (with mf_step: the physical variable slots that back-substitution retracted from / into)
-    bool mf_step = false;                    // the last solve was matrix-free: its back-substitution launch has left the trial's cost and the step statistics as rows of partials in mf_q (mf_rows of them)
-    nlls::DevBuf<double> mf_q; int mf_rows = 0; bool mf_fin_defer = false, mf_fin_pending = false;   // (the finishing workgroup may ride in the look-ahead sweep's launch)
-    nlls::DevBuf<nlls::MfDesc> d_mf_desc; int64_t mf_nbig = 0; size_t mf_lds = 0; uint32_t mf_ecap = 0, mf_wsz = 0; bool mf_use = false;    // per-supernode partials of the step's quadratic form; dynamic LDS of the two launches
+    nlls::DevBuf<double> mf_q; int mf_rows = 0;   // the back-substitution launch's rows of partials (nlls::StepState::mf)
+    nlls::DevBuf<nlls::MfDesc> d_mf_desc; int64_t mf_nbig = 0; size_t mf_lds = 0; uint32_t mf_ecap = 0, mf_wsz = 0;    // per-supernode partials of the step's quadratic form; dynamic LDS of the two launches
     int64_t mf_trials = 0, mf_reduced_sweeps = 0, full_sweeps = 0;   // diagnostics (nlls_get_solve_stats [23..25])
     std::vector<int64_t> h_erow; std::vector<int64_t> h_eptr; std::vector<int64_t> h_enbr_block; std::vector<nlls::ElimDesc> h_elim_desc; std::vector<uint32_t> h_fast_voff;   // host copies kept between build_schur and build_mf
 
     // ---- sharding ------------------------------------------------------------------------------------
-    bool replicate_xr = false;               // the step's reduced part is written on every rank (sharded LM trial without the stage-2 reduction)
     int ps_np = 0, ps_np2 = 0;                 // partial counts of the last enqueue_post_solve (for the trial's finishing launch)
     int dense_t128_min = 16;                   // dense LDL': 128 x 128 tiles in the trailing update only while it has at least this many 128-blocks per side (fewer: the 64 x 64 kernel fills the chip better)
     bool dense_pad128 = false;                 // the dense layout is padded to a multiple of 128 rows (windowed and look-ahead factorisations: 128-column panels only)
@@ -290,7 +290,7 @@ struct nlls_ctx {
     // (one rank, every eliminated block on the fast path, Euclidean eliminated variables): no launch of its own for them.  NLLS_POST_SPLIT=1: off (A/B)
     nlls::DevBuf<uint32_t> d_fast_voff;      // where the variable of each eliminated member is stored (elimination order)
     nlls::DevBuf<uint32_t> d_rest_var; nlls::DevBuf<int32_t> d_rest_red;   // the other variables, and where their step starts in the reduced solution (-1: fixed)
-    bool fast_all_euclid = false, post_fuse = true, retract_done = false; int trial_to = -1, trial_from = -1;
+    bool fast_all_euclid = false, post_fuse = true;
     bool elim_split = false;                   // NLLS_ELIM_SPLIT=1: the assembly of the reduced system in three launches (A/B)
     bool elim_selected = false;
     std::vector<int32_t> owner_of_block;
@@ -321,13 +321,9 @@ struct nlls_ctx {
     // of the reduced rows -- the compact list with the reduced-reduced blocks on every rank, the all-blocks mask, and the dof mask of g'x
     nlls::DevBuf<nlls::SchurCopy> d_blk_slow_lazy; int64_t nblk_slow_lazy = 0;
     nlls::DevBuf<uint8_t> d_blk_mask_lazy; nlls::DevBuf<double> d_dof_mask_lazy;
-    bool reduced_summed = true;              // false between a lazy sweep and the first entry point that needs the summed rows (ensure_reduced_summed)
     int64_t n_stage0 = 0, n_lazy_trials = 0; // (diagnostics: nlls_get_solve_stats [11], [12])
     nlls::DevBuf<double> tE;                 // E_v s of the last solve per fast member (s = reduced solution): reused by the quadratic form
-    bool tE_valid = false; int64_t n_fast_members = 0;
-    bool status_known_zero = false;          // the host has read the last solve's status and it was 0: the next solve need not reset it on the device
-    bool S_zeroed = false;                   // the last solve's back-substitution left S zero-filled for the next one (saves the memset launches)
-    bool step_cached = false; double c_maxabs = 0, c_sumsq = 0, c_gx = 0, c_xAx = 0, c_xx = 0;   // host copies of the last solve's step statistics
+    int64_t n_fast_members = 0;
     nlls::DevBuf<double> Cinv;               // (C_v + lambda I)^-1 of the fast-path members, fast_dv^2 doubles per eliminated block
     int fast_dv = 0, fast_maxk = 0, fast_maxk_narrow = 0;
     int64_t n_fast_narrow = 0;               // fast supernodes with nd + 1 <= 64 come first in d_fast_groups
@@ -342,7 +338,7 @@ struct nlls_ctx {
     int solve_mode = 0, band_CH = 0, band_H = 0, band_SEG = 0, band_NSEG = 0;
     bool band_blocked = true;                // blocked (MFMA) band factorisation when the bandwidth allows
     bool band_twisted = true;               // factor the band from both ends at once (two workgroups) when the layout allows
-    bool gather_ready = false, tiles_zeroed = false; std::vector<uint32_t> h_slab_off;   // the gather index (d_gjobs / d_gcons / slab) exists; the tiles the gather writes into are zero
+    bool gather_ready = false; std::vector<uint32_t> h_slab_off;   // the gather index (d_gjobs / d_gcons / slab) exists
     bool elim_slab = false;                 // slab + gather assembly straight into the block cyclic reduction's tiles (single rank, fast-path supernodes only)
     nlls::DevBuf<double> slab; nlls::DevBuf<uint32_t> d_slab_off, d_slab_groups; int64_t n_slab60 = 0, n_slabnar = 0, n_slabwide = 0; nlls::DevBuf<nlls::GatherJob> d_gjobs; nlls::DevBuf<nlls::GatherCon> d_gcons; int64_t n_gjobs = 0;
     nlls::TspSolver tsp;                    // tile-sparse LDL' of a reduced system that is neither a narrow band nor small (nlls_tsp.hip)
@@ -363,5 +359,4 @@ struct nlls_ctx {
     nlls::DevBuf<char> arena, arena_pre;
     int64_t hot_bytes = 0;                   // bytes of the hot set (what an LM iteration reads or writes): nlls_get_memory_info
     nlls::DevBuf<char> flushbuf;             // nlls_flush_cache: foreign traffic for cold-cache timings
-    bool solved = false;
 };

@@ -30,6 +30,12 @@ int select_elimination(nlls_ctx* c, int32_t flags);
 int build_schur(nlls_ctx* c, int32_t flags);
 std::vector<int32_t> rcm_order(const std::vector<std::vector<int32_t>>& adj);   // reverse Cuthill-McKee: perm[new position] = node (nlls_structure.cpp)
 
+// One LM trial's solve and tail (default: a plain solve).  to / from: it retracts vars[from] + x into vars[to]; mf: matrix-free; replicate_xr: every rank writes the step's
+// reduced part; zero_for_lookahead: the finishing launch zero-fills the rows of the look-ahead sweep behind it; defer_fin: matrix-free, the finishing workgroup rides in that
+// sweep's launch; mirror: the pinned host mirror as the device sees it, where the tail publishes scalars and stamps -- set it by name where the host waits on them
+struct TrialArgs { int to = -1, from = -1; bool mf = false, replicate_xr = false, zero_for_lookahead = false, defer_fin = false; double* mirror = nullptr;
+                   double* stamps() const { return mirror ? mirror + 40 : nullptr; } };
+
 // sweeps (nlls_sweep.hip): enqueue on c->stream; cost lands in c->scalars[0]
 struct PostSolveArgs;
 int enqueue_sweep_cost(nlls_ctx* c, int which, int64_t pofs = 0, int64_t* count = nullptr, const PostSolveArgs* post = nullptr, bool* post_taken = nullptr);   // post: the step-statistics roles of an LM trial ride in the first launch (nlls_post.hpp)
@@ -39,7 +45,7 @@ int enqueue_dyn_gradhess(nlls_ctx* c, const Group& G, const double* vars, int64_
 int enqueue_reduce_partials(nlls_ctx* c, int64_t n);
 int enqueue_check_analytic(nlls_ctx* c, double* d_out, int64_t* nblocks_out);   // closed-form block maths against the dual-number statement (nlls_check_analytic)
 int enqueue_robustify(nlls_ctx* c, const RobustSpec& rk, int64_t n, const double* d_cost, double* d_out);   // out[4 i ..] = robustify, rho, rho', rho'' at cost[i] (nlls_robustify)
-int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost = true, int which = NLLS_VARS_CURRENT, int mode = 0);   // mode 1: the reduced rows only (the matrix-free trial's gradient sweep: nlls_ctx::grad_level 1)   // which: the variable set to linearise at (the look-ahead sweep of an LM trial: NLLS_VARS_NEXT)
+int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost = true, int which = NLLS_VARS_CURRENT, int mode = 0);   // mode 1: the reduced rows only (the matrix-free trial's gradient sweep: nlls::Linearisation::level 1)   // which: the variable set to linearise at (the look-ahead sweep of an LM trial: NLLS_VARS_NEXT)
 // vector helpers (nlls_sweep.hip)
 int enqueue_retract(nlls_ctx* c, int to, int from);
 int enqueue_step_stats(nlls_ctx* c);          // scalars[1] = max|x|, scalars[2] = x'x
@@ -52,8 +58,8 @@ int enqueue_iters_to_double(nlls_ctx* c, const int64_t* d_it, const int64_t* d_p
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);
 int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot /* scalars[out], scalars[out+1] = v'Hv, b'v */);
-int enqueue_post_solve(nlls_ctx* c, int retract_to = -1, int retract_from = -1, bool finish = true);
-int enqueue_lm_trial_tail(nlls_ctx* c, int to, int from);   // post-solve statistics + retraction, cost sweep, and ONE finishing launch for both reductions   // enqueue_step_stats + enqueue_quadform(x, 4) for the step of the last solve, fewer launches; optionally the retraction rides along
+int enqueue_post_solve(nlls_ctx* c, double* stamps, int retract_to = -1, int retract_from = -1, bool finish = true);
+int enqueue_lm_trial_tail(nlls_ctx* c, const TrialArgs& t);   // post-solve statistics + retraction, cost sweep, and ONE finishing launch for both reductions   // enqueue_step_stats + enqueue_quadform(x, 4) for the step of the last solve, fewer launches; optionally the retraction rides along
 
 #if defined(__HIPCC__)
 // to[var i] = update(from[var i], x[its block])   (src/linearsystem.jl:206-213); fixed variables are copied
@@ -110,13 +116,13 @@ __device__ __forceinline__ void retract_one(const int32_t* __restrict__ kind, co
 }
 #endif
 // solve (nlls_solve.hip)
-int enqueue_solve(nlls_ctx* c);
-int enqueue_solve_local(nlls_ctx* c);
-int enqueue_solve_finish(nlls_ctx* c);
-int enqueue_tiny_dense_trial(nlls_ctx* c, int to, int from, bool lookahead_follows);
+int enqueue_solve(nlls_ctx* c, const TrialArgs& t = {});
+int enqueue_solve_local(nlls_ctx* c, bool mf = false);
+int enqueue_solve_finish(nlls_ctx* c, const TrialArgs& t = {});
+int enqueue_tiny_dense_trial(nlls_ctx* c, int to, int from);
 int enqueue_tiny_trial_finish_pending(nlls_ctx* c);   // the finishing reduction no accumulate launch has carried   // nlls_ctx::tiny_dense: damped solve + step statistics + retraction in one launch, then the cost sweep
 int enqueue_chain_solve(nlls_ctx* c, int n_band, int bw, int nbd, int H);   // the banded reduced system by the chain kernels (nlls_chain.hip)
-int enqueue_reduced_solve(nlls_ctx* c);   // the factorisation + backward pass of the assembled reduced system alone (timing)
+int enqueue_reduced_solve(nlls_ctx* c, bool mf = false);   // the factorisation + backward pass of the assembled reduced system alone (timing)
 int enqueue_pack_reduce0(nlls_ctx* c);      // [cost | reduced rows | reduced b] -> redbuf
 int enqueue_unpack_reduce0(nlls_ctx* c, bool with_cost = true);
 
@@ -125,7 +131,7 @@ int enqueue_unpack_reduce0(nlls_ctx* c, bool with_cost = true);
 struct BsfRetract;
 int enqueue_mf_solve_local(nlls_ctx* c);
 int enqueue_mf_backsub(nlls_ctx* c, const BsfRetract& rt, int write_red, double* zptr, int64_t zcount, unsigned nextra, unsigned nrestwg);
-int enqueue_mf_trial_finish(nlls_ctx* c); int enqueue_mf_trial_finish_now(nlls_ctx* c); struct MfFin; MfFin mf_fin_args(nlls_ctx* c); size_t mf_part_doubles(int64_t nsupernodes, int64_t nrest_wg_max);
+int enqueue_mf_trial_finish(nlls_ctx* c, const TrialArgs& t); int enqueue_mf_trial_finish_now(nlls_ctx* c, const TrialArgs& t); struct MfFin; MfFin mf_fin_args(nlls_ctx* c, double* mirror); size_t mf_part_doubles(int64_t nsupernodes, int64_t nrest_wg_max);
 int enqueue_mf_sweep_cost(nlls_ctx* c, int which);   // cost(vars[which]) summed as the matrix-free trial sums its cost
 int enqueue_gather(nlls_ctx* c);   // (nlls_solve.hip) schur_gather_kernel: slabs -> the block cyclic reduction's tiles
 uint32_t mf_wave_doubles(uint32_t ecap, int dp); int mf_batch_max(); int mf_elim_waves(); uint32_t mf_slab_doubles(int B, int dp, int tr);
@@ -139,3 +145,4 @@ void comm_release(nlls_ctx* c);
 inline double* vars_ptr(nlls_ctx* c, int which) { return c->vars[c->vars_slot[which]].p; }
 
 }  // namespace nlls
+#include "nlls_state.hpp"

@@ -336,8 +336,7 @@ static int launch_mf_elim(nlls_ctx* c, const Group& G) {
 int enqueue_mf_solve_local(nlls_ctx* c) {
     const int n = (int)c->nred; if (n == 0 || !c->mf_ok) return NLLS_ERR_NOT_READY;
     const Group& G = c->groups[c->mf_group];
-    if (!c->status_known_zero) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
-    c->status_known_zero = false;
+    if (!take(c->zero.status)) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
     int rc = NLLS_ERR_UNSUPPORTED;
     switch (G.res_kind) {
 #define X(K) case K: rc = c->mf_ps == 0 ? launch_mf_elim<K, 0>(c, G) : launch_mf_elim<K, 1>(c, G); break;

@@ -296,18 +296,18 @@ int enqueue_mf_backsub(nlls_ctx* c, const BsfRetract& rt, int write_red, double*
     return NLLS_ERR_UNSUPPORTED;
 }
 // the end of the trial whose back-substitution launch has left the rows of partials (nlls_ctx::mf_rows): one finishing workgroup, nothing else -- as a launch of its own, or
-// (nlls_ctx::mf_fin_defer) as the first workgroup of the look-ahead sweep's launch behind it (nlls_sweep.hip takes mf_fin_pending along)
-MfFin mf_fin_args(nlls_ctx* c) { return MfFin{c->mf_q.p, c->mf_rows, c->lambda, c->scalars.p, c->d_status.p, c->h_scalars_dev, (double)c->trial_seq, c->stamp_ptr()}; }
-int enqueue_mf_trial_finish(nlls_ctx* c) {
+// (TrialArgs::defer_fin) as the first workgroup of the look-ahead sweep's launch behind it (nlls_sweep.hip takes it along: nlls::Deferred::mf_pending)
+MfFin mf_fin_args(nlls_ctx* c, double* mirror) { return MfFin{c->mf_q.p, c->mf_rows, c->lambda, c->scalars.p, c->d_status.p, mirror, (double)c->trial_seq, mirror ? mirror + 40 : nullptr}; }
+int enqueue_mf_trial_finish(nlls_ctx* c, const TrialArgs& t) {
     ++c->trial_seq;
-    if (c->mf_fin_defer) { c->mf_fin_pending = true; return NLLS_OK; }
-    return enqueue_mf_trial_finish_now(c);
+    if (t.defer_fin) { defer_mf_fin(c); return NLLS_OK; }
+    return enqueue_mf_trial_finish_now(c, t);
 }
-int enqueue_mf_trial_finish_now(nlls_ctx* c) {
-    c->mf_fin_pending = false;
+int enqueue_mf_trial_finish_now(nlls_ctx* c, const TrialArgs& t) {
+    drop(c->fin.mf_pending);
     MfZero zr{};
-    if (c->tail_zero_for_lookahead && c->nzero > 0) { zr = MfZero{c->A.p, c->d_zero_off.p, c->d_zero_len.p, c->b.p, c->d_zero_b_off.p, c->d_zero_b_len.p, (int)c->nzero}; c->heavy_rows_zeroed = true; }
-    hipLaunchKernelGGL(mf_trial_finish_kernel, dim3(1 + (unsigned)zr.n), dim3(256), 0, c->stream, mf_fin_args(c), zr);
+    if (t.zero_for_lookahead && c->nzero > 0) { zr = MfZero{c->A.p, c->d_zero_off.p, c->d_zero_len.p, c->b.p, c->d_zero_b_off.p, c->d_zero_b_len.p, (int)c->nzero}; heavy_rows_zeroed(c); }
+    hipLaunchKernelGGL(mf_trial_finish_kernel, dim3(1 + (unsigned)zr.n), dim3(256), 0, c->stream, mf_fin_args(c, t.mirror), zr);
     HIPCHK(hipGetLastError());
     return NLLS_OK;
 }
@@ -324,7 +324,7 @@ static int launch_mf_cost(nlls_ctx* c, const Group& G, int which) {
 }
 int enqueue_mf_sweep_cost(nlls_ctx* c, int which) {
     const Group& G = c->groups[c->mf_group];
-    c->mf_step = false;                       // (its rows of mf_q overwrite the last trial's: that trial's tail is no longer there to be finished)
+    drop(c->step.mf);                         // (its rows of mf_q overwrite the last trial's: that trial's tail is no longer there to be finished)
     switch (G.res_kind) {
 #define X(K) case K: return c->mf_ps == 0 ? launch_mf_cost<K, 0>(c, G, which) : launch_mf_cost<K, 1>(c, G, which);
         NLLS_FOR_EACH_RES(X)

@@ -1323,7 +1323,7 @@ int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot) {
     int np = 0;
     if (c->info.is_sparse) {
         // the step of the last solve: the rows of fast-path members come from E_v s, which the back-substitution kept
-        const bool reuse = d_vec == c->x.p && c->tE_valid && c->n_fast_members > 0;
+        const bool reuse = d_vec == c->x.p && c->step.tE_valid && c->n_fast_members > 0;
         np = (int)std::min<int64_t>((c->nblk * QF_COLS + 255) / 256, 768); if (np < 1) np = 1;
         hipLaunchKernelGGL(quadform_blocks_kernel, dim3(np), dim3(256), 0, c->stream, c->A.p, c->d_blk.p, c->nblk, d_vec,
                            reuse ? c->d_blk_slowmask.p : (c->nranks > 1 ? c->d_blk_mask.p : (const uint8_t*)nullptr), c->partials.p);
@@ -1348,10 +1348,10 @@ int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot) {
 }
 
 // the arguments of the step-statistics roles (nlls_post.hpp) for the step of the last solve; retract_to >= 0: with the retraction role
-PostSolveArgs post_solve_args(nlls_ctx* c, int retract_to, int retract_from) {
-    const bool reuse = c->tE_valid && c->n_fast_members > 0;
+PostSolveArgs post_solve_args(nlls_ctx* c, int retract_to, int retract_from, double* stamps) {
+    const bool reuse = c->step.tE_valid && c->n_fast_members > 0;
     PostSolveArgs a{};
-    const bool lazy = c->nranks > 1 && !c->reduced_summed;      // the reduced rows of A.data and b hold this rank's share only: they count on every rank
+    const bool lazy = c->nranks > 1 && !c->lin.summed;      // the reduced rows of A.data and b hold this rank's share only: they count on every rank
     a.A = c->A.p; a.blk = reuse ? (lazy ? c->d_blk_slow_lazy.p : c->d_blk_slow.p) : c->d_blk.p; a.nblk = reuse ? (lazy ? c->nblk_slow_lazy : c->nblk_slow) : c->nblk;
     a.blkmask = reuse ? (const uint8_t*)nullptr : (c->nranks > 1 ? (lazy ? c->d_blk_mask_lazy.p : c->d_blk_mask.p) : (const uint8_t*)nullptr);
     a.ediag = c->d_elim_diag.p; a.eboff = c->d_elim_boff.p; a.members = c->n_fast_members == (int64_t)c->d_elim_diag.n ? (const uint32_t*)nullptr : c->d_fast_members.p; a.nm = c->n_fast_members; a.tE = c->tE.p;
@@ -1360,7 +1360,7 @@ PostSolveArgs post_solve_args(nlls_ctx* c, int retract_to, int retract_from) {
     a.np3 = reuse ? (int)std::max<int64_t>(1, std::min<int64_t>((c->n_fast_members + 255) / 256, 256)) : 0;
     a.np2 = (int)std::max<int64_t>(1, std::min<int64_t>((c->info.ndof + 255) / 256, 512));      // (5 partials each, behind the quadratic form's at 1024: ends at 3584 < TRIAL_COST_POFS)
     a.partials = c->partials.p; a.part2 = c->partials.p + 1024;
-    a.stamps = c->stamp_ptr();
+    a.stamps = stamps;
     a.nretract = 0;
     if (retract_to >= 0 && c->info.nvar > 0) {
         a.nretract = (int)((c->info.nvar + 255) / 256); a.vkind = c->d_var_kind.p; a.vdim = c->d_var_dim.p; a.voff = c->d_var_off.p; a.vboff = c->d_var_boff.p;
@@ -1372,7 +1372,7 @@ PostSolveArgs post_solve_args(nlls_ctx* c, int retract_to, int retract_from) {
 __global__ void status_to_scalar_kernel(const int* __restrict__ status, double* __restrict__ out) { *out = (double)status[0]; }
 // step statistics + quadratic form of the step of the last solve (what nlls_solve / nlls_lm_trial / nlls_trial_local
 // precompute): one launch + one finishing workgroup on sparse systems, the separate kernels otherwise
-int enqueue_post_solve(nlls_ctx* c, int retract_to, int retract_from, bool finish) {
+int enqueue_post_solve(nlls_ctx* c, double* stamps, int retract_to, int retract_from, bool finish) {
     if (!c->info.is_sparse) {
         if (retract_to >= 0) { int rc0 = enqueue_retract(c, retract_to, retract_from); if (rc0 != NLLS_OK) return rc0; }
         int rc = enqueue_step_stats(c); if (rc != NLLS_OK) return rc;
@@ -1380,7 +1380,7 @@ int enqueue_post_solve(nlls_ctx* c, int retract_to, int retract_from, bool finis
         hipLaunchKernelGGL(status_to_scalar_kernel, dim3(1), dim3(1), 0, c->stream, c->d_status.p, c->scalars.p + 10);
         return NLLS_OK;
     }
-    PostSolveArgs a = post_solve_args(c, retract_to, retract_from);
+    PostSolveArgs a = post_solve_args(c, retract_to, retract_from, stamps);
     const dim3 grid((unsigned)(a.np + a.np3 + a.np2 + a.nretract));
     if (c->fast_dv == 3) hipLaunchKernelGGL((post_solve_kernel<3>), grid, dim3(256), 0, c->stream, a);
     else if (c->fast_dv == 2) hipLaunchKernelGGL((post_solve_kernel<2>), grid, dim3(256), 0, c->stream, a);
@@ -1390,27 +1390,24 @@ int enqueue_post_solve(nlls_ctx* c, int retract_to, int retract_from, bool finis
     return NLLS_OK;
 }
 // what follows the solve in an LM trial (src/iterators.jl:155-163)
-int enqueue_lm_trial_tail(nlls_ctx* c, int to, int from) {
-    // (matrix-free trial: the back-substitution launch has retracted, taken the trial point's cost and left the step statistics -- one finishing launch sums its rows)
-    // (... but only for the sets it retracted: the tail of the same step between other sets -- or after a set was written, which clears mf_step -- takes the path below)
-    if (c->mf_step) { c->retract_done = false; if (c->vars_slot[to] == c->mf_to_phys && c->vars_slot[from] == c->mf_from_phys) return enqueue_mf_trial_finish(c); c->mf_step = false; }
-    if (!c->info.is_sparse) { int rc = enqueue_post_solve(c, to, from); if (rc != NLLS_OK) return rc; return enqueue_sweep_cost(c, to); }
+int enqueue_lm_trial_tail(nlls_ctx* c, const TrialArgs& t) {
+    if (take_mf_tail(c, t.to, t.from)) return enqueue_mf_trial_finish(c, t);
+    if (!c->info.is_sparse) { int rc = enqueue_post_solve(c, t.stamps(), t.to, t.from); if (rc != NLLS_OK) return rc; return enqueue_sweep_cost(c, t.to); }
     int rc; int64_t ncp = 0;
-    if (c->retract_done) {
+    if (take(c->step.retract_done)) {
         // the retraction went with the back-substitution launch: the statistics roles ride in the cost sweep's (first) launch -- no launch of their own
-        c->retract_done = false;
-        PostSolveArgs a = post_solve_args(c, -1, -1); a.dv = c->fast_dv; bool taken = false;
-        rc = enqueue_sweep_cost(c, to, TRIAL_COST_POFS, &ncp, &a, &taken); if (rc != NLLS_OK) return rc;
-        if (!taken) { rc = enqueue_post_solve(c, -1, -1, false); if (rc != NLLS_OK) return rc; }      // (no launch of the cost sweep could carry them)
+        PostSolveArgs a = post_solve_args(c, -1, -1, t.stamps()); a.dv = c->fast_dv; bool taken = false;
+        rc = enqueue_sweep_cost(c, t.to, TRIAL_COST_POFS, &ncp, &a, &taken); if (rc != NLLS_OK) return rc;
+        if (!taken) { rc = enqueue_post_solve(c, t.stamps(), -1, -1, false); if (rc != NLLS_OK) return rc; }      // (no launch of the cost sweep could carry them)
     } else {
-    rc = enqueue_post_solve(c, to, from, false); if (rc != NLLS_OK) return rc;
-    rc = enqueue_sweep_cost(c, to, TRIAL_COST_POFS, &ncp); if (rc != NLLS_OK) return rc;
+    rc = enqueue_post_solve(c, t.stamps(), t.to, t.from, false); if (rc != NLLS_OK) return rc;
+    rc = enqueue_sweep_cost(c, t.to, TRIAL_COST_POFS, &ncp); if (rc != NLLS_OK) return rc;
     }
     // (the look-ahead sweep follows: its zero fill rides here -- enqueue_sweep_gradhess skips the launch once)
     ZeroRanges zr{};
-    if (c->tail_zero_for_lookahead && c->nzero > 0) { zr = ZeroRanges{c->A.p, c->d_zero_off.p, c->d_zero_len.p, c->b.p, c->d_zero_b_off.p, c->d_zero_b_len.p, (int)c->nzero}; c->heavy_rows_zeroed = true; }
+    if (t.zero_for_lookahead && c->nzero > 0) { zr = ZeroRanges{c->A.p, c->d_zero_off.p, c->d_zero_len.p, c->b.p, c->d_zero_b_off.p, c->d_zero_b_len.p, (int)c->nzero}; heavy_rows_zeroed(c); }
     hipLaunchKernelGGL(trial_finish_kernel, dim3(2 + (unsigned)zr.n), dim3(256), 0, c->stream, c->partials.p + TRIAL_COST_POFS, ncp, c->partials.p, c->ps_np, c->partials.p + 1024, c->ps_np2,
-                       c->lambda, c->scalars.p, c->d_status.p, c->h_scalars_dev, (double)(++c->trial_seq), zr, c->stamp_ptr());
+                       c->lambda, c->scalars.p, c->d_status.p, t.mirror, (double)(++c->trial_seq), zr, t.stamps());
     HIPCHK(hipGetLastError());
     return NLLS_OK;
 }
@@ -1419,8 +1416,7 @@ int enqueue_lm_trial_tail(nlls_ctx* c, int to, int from) {
 int enqueue_gather(nlls_ctx* c) {
     if (!c->gather_ready || !c->bcr.ready) { c->err = "gather index missing"; return NLLS_ERR_NOT_READY; }
     const BcrGeom& g = c->bcr.geom;
-    if (!c->tiles_zeroed) HIPCHK(hipMemsetAsync(g.ws + g.oD, 0, sizeof(double) * (g.oBR + (size_t)g.N * g.NT * 256 - g.oD), c->stream));
-    c->tiles_zeroed = false;
+    if (!take(c->zero.tiles)) HIPCHK(hipMemsetAsync(g.ws + g.oD, 0, sizeof(double) * (g.oBR + (size_t)g.N * g.NT * 256 - g.oD), c->stream));
     GatherArgs ga{c->d_gjobs.p, c->d_gcons.p, c->n_gjobs, c->slab.p, c->A.p, c->b.p, c->Cinv.p, c->fast_dv, c->lambda, c->bcr.geom, c->d_status.p};
     hipLaunchKernelGGL(schur_gather_kernel, dim3((unsigned)((c->n_gjobs + 3) / 4)), dim3(256), 0, c->stream, ga);
     HIPCHK(hipGetLastError());
@@ -1430,14 +1426,14 @@ int enqueue_gather(nlls_ctx* c) {
 // local phase: assemble this rank's share of [S | s] (rank 0 also contributes the reduced-reduced blocks,
 // lambda*I and b_R); under sharding the buffer is then summed over ranks
 template <bool TSP>
-static int enqueue_solve_local_t(nlls_ctx* c) {
+static int enqueue_solve_local_t(nlls_ctx* c, bool mf) {
     using LAY = SLayoutT<TSP>;
     const int n = (int)c->nred; if (n == 0) return NLLS_OK;
-    if (c->mf_use) return enqueue_mf_solve_local(c);               // the matrix-free trial: the supernodes evaluate their cost blocks themselves (nlls_mf.hip)
+    if (mf) return enqueue_mf_solve_local(c);               // the matrix-free trial: the supernodes evaluate their cost blocks themselves (nlls_mf.hip)
     const LAY L = make_layout<TSP>(c); const int npad = TSP ? 0 : L.npad;
     // lazy stage 0 (collective route, reduced rows not summed over ranks): EVERY rank adds its share of the reduced-reduced blocks and of b_R to its
     // share of [S | s] -- the one sum over ranks that follows completes both; the damping is rank 0's
-    const bool lazy = c->nranks > 1 && !c->reduced_summed;
+    const bool lazy = c->nranks > 1 && !c->lin.summed;
     const bool band = c->solve_mode == SOLVE_BAND; const bool lead = c->nranks == 1 || c->rank == 0 || lazy;
     const double lambda_rr = (c->nranks == 1 || c->rank == 0) ? c->lambda : 0.0;
     if (c->elim_slab) {
@@ -1465,10 +1461,8 @@ static int enqueue_solve_local_t(nlls_ctx* c) {
     const bool all_in_one = one_prepare && !c->elim_split && c->nranks == 1 && c->n_slow_groups == 0 && nfast_narrow > 0 && nfast_wide > 0 &&
                             c->solve_mode != SOLVE_SMALL && c->fast_dv >= 1 && c->fast_dv <= 3 && (int64_t)c->d_elim_diag.n == c->n_fast_members;
     if (all_in_one) {
-        if (!c->status_known_zero) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
-        c->status_known_zero = false;
-        if (!c->S_zeroed) HIPCHK(hipMemsetAsync(c->S.p, 0, sizeof(double) * (c->s_elems + (size_t)((band || TSP) ? n : npad)), c->stream));
-        c->S_zeroed = false;
+        if (!take(c->zero.status)) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
+        if (!take(c->zero.S)) HIPCHK(hipMemsetAsync(c->S.p, 0, sizeof(double) * (c->s_elems + (size_t)((band || TSP) ? n : npad)), c->stream));
         const int ninit = (std::max(npad, n) + 255) / 256;
         PrepArgs pa{c->d_red_boff.p, c->d_copy.p, c->lambda, ninit, (uint32_t)c->n_fast_groups, c->d_status.p, c->stamp_ptr()};
         const dim3 grid((unsigned)(c->n_fast_groups + ninit + c->ncopy));
@@ -1478,10 +1472,9 @@ static int enqueue_solve_local_t(nlls_ctx* c) {
         HIPCHK(hipGetLastError());
         return NLLS_OK;
     }
-    c->status_known_zero = false;
+    drop(c->zero.status);
     if (!one_prepare) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
-    if (!c->S_zeroed) HIPCHK(hipMemsetAsync(c->S.p, 0, sizeof(double) * (c->s_elems + (size_t)((band || TSP) ? n : npad)), c->stream));
-    c->S_zeroed = false;
+    if (!take(c->zero.S)) HIPCHK(hipMemsetAsync(c->S.p, 0, sizeof(double) * (c->s_elems + (size_t)((band || TSP) ? n : npad)), c->stream));
     if (c->nranks > 1) HIPCHK(hipMemsetAsync(c->x.p, 0, sizeof(double) * c->info.ndof, c->stream));
     if (one_prepare) {
         const int ninit = (std::max(npad, n) + 255) / 256;
@@ -1525,10 +1518,10 @@ static int enqueue_solve_local_t(nlls_ctx* c) {
     return NLLS_OK;
 }
 
-int enqueue_solve_local(nlls_ctx* c) { return c->solve_mode == SOLVE_TSPARSE ? enqueue_solve_local_t<true>(c) : enqueue_solve_local_t<false>(c); }
+int enqueue_solve_local(nlls_ctx* c, bool mf) { return c->solve_mode == SOLVE_TSPARSE ? enqueue_solve_local_t<true>(c, mf) : enqueue_solve_local_t<false>(c, mf); }
 
 // the reduced system itself: factorisation + both substitutions; its solution lands in s (c->s_ptr())
-int enqueue_reduced_solve(nlls_ctx* c) {
+int enqueue_reduced_solve(nlls_ctx* c, bool mf) {
     const int n = (int)c->nred; if (n == 0) return NLLS_OK;
     const SLayout L = make_layout(c); const int npad = L.npad, nblk = npad / NB;
     const bool band = c->solve_mode == SOLVE_BAND;
@@ -1548,8 +1541,8 @@ int enqueue_reduced_solve(nlls_ctx* c) {
         // gauge directions are rounding noise of either sign, the step along them noise / noise, and whether the trial is accepted a coin toss: at BASELINE config 4
         // 29-31 damped solves for 20 iterations (the oracle's LDL': 24) against 20 with the rule, ending at the oracle's cost to 12 digits.
         const double pivot_floor = c->lambda == 0.0 ? 1e-11 : c->damped_floor;
-        const bool tiles_direct = c->elim_slab || c->mf_use;          // (slab + gather assembly: the tiles are in place, no conversion from band storage)
-        if (!tiles_direct) c->tiles_zeroed = false;
+        const bool tiles_direct = c->elim_slab || mf;          // (slab + gather assembly: the tiles are in place, no conversion from band storage)
+        if (!tiles_direct) drop(c->zero.tiles);
         if (c->bcr.enqueue(c->stream, tiles_direct ? (const double*)nullptr : c->S.p, c->s_ptr(), c->d_status.p, pivot_floor) != NLLS_OK) return herr(c, hipGetLastError(), "block cyclic reduction launch");
     } else if (band) {
         // bands wider than block cyclic reduction takes (more than 80 columns), and NLLS_FLAG_NO_BCR: the chain kernels of round 1 (nlls_chain.hip)
@@ -1613,15 +1606,15 @@ int enqueue_reduced_solve(nlls_ctx* c) {
 }
 
 // finish: factor the (summed) reduced system, solve it, back-substitute this rank's eliminated blocks
-int enqueue_solve_finish(nlls_ctx* c) {
-    c->retract_done = false;
+int enqueue_solve_finish(nlls_ctx* c, const TrialArgs& t) {
+    drop(c->step.retract_done);
     const int n = (int)c->nred; if (n == 0) return NLLS_OK;
-    { const int rc = enqueue_reduced_solve(c); if (rc != NLLS_OK) return rc; }
+    { const int rc = enqueue_reduced_solve(c, t.mf); if (rc != NLLS_OK) return rc; }
     if (c->phase_on && c->phase_ev.size() >= 6) (void)hipEventRecord(c->phase_ev[3], c->stream);      // (phase timing: the reduced solve ends)
     // x = -solution (folded into the fast back-substitution launch when there is one)
     // (replicate_xr: a sharded LM trial keeps the reduced part of the step on every rank -- each retracts the cameras and its own
     //  points itself, no all-reduce of x)
-    const int write_red = (c->nranks == 1 || c->rank == 0 || c->replicate_xr) ? 1 : 0;
+    const int write_red = (c->nranks == 1 || c->rank == 0 || t.replicate_xr) ? 1 : 0;
     if (c->n_fast_groups == 0) hipLaunchKernelGGL(scatter_reduced_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->s_ptr(), c->d_red_boff.p, n, c->x.p, write_red);
     const int64_t nel_local = (int64_t)(c->d_elim_diag.n);
     if (nel_local > 0) {
@@ -1637,27 +1630,25 @@ int enqueue_solve_finish(nlls_ctx* c) {
         const unsigned nextra = zero_S ? 160 : 32;
         // what the spare workgroups zero-fill for the next solve: the band storage of S, or (slab + gather assembly) the tiles the gather writes into
         double* zptr = c->S.p; int64_t zcount = zero_S ? (int64_t)c->s_elems : (int64_t)0;
-        const bool tiles_direct = c->elim_slab || c->mf_use;
+        const bool tiles_direct = c->elim_slab || t.mf;
         if (tiles_direct) { const BcrGeom& g = c->bcr.geom; zptr = g.ws + g.oD; zcount = (int64_t)(g.oBR + (size_t)g.N * g.NT * 256 - g.oD); }
-        // an LM trial (nlls_lm_trial sets trial_to / trial_from): the retraction in this launch
+        // an LM trial (TrialArgs::to / from): the retraction in this launch
         BsfRetract rt{}; unsigned nrestwg = 0; rt.stamps = c->stamp_ptr();
-        c->retract_done = false;
-        if (c->trial_to >= 0 && (c->post_fuse || c->mf_use) && c->fast_all_euclid && c->nranks == 1 && nslow == 0 && c->info.is_sparse && c->n_fast_groups > 0 && c->info.nvar > 0) {
+        if (t.to >= 0 && (c->post_fuse || t.mf) && c->fast_all_euclid && c->nranks == 1 && nslow == 0 && c->info.is_sparse && c->n_fast_groups > 0 && c->info.nvar > 0) {
             rt.on = 1; rt.nrest = (int)c->d_rest_var.n; rt.fast_voff = c->d_fast_voff.p; rt.rest_var = c->d_rest_var.p; rt.rest_red = c->d_rest_red.p;
-            rt.vkind = c->d_var_kind.p; rt.vdim = c->d_var_dim.p; rt.voff = c->d_var_off.p; rt.vfrom = vars_ptr(c, c->trial_from); rt.vto = vars_ptr(c, c->trial_to);
-            nrestwg = (unsigned)((rt.nrest + 63) / 64); c->retract_done = true;
+            rt.vkind = c->d_var_kind.p; rt.vdim = c->d_var_dim.p; rt.voff = c->d_var_off.p; rt.vfrom = vars_ptr(c, t.from); rt.vto = vars_ptr(c, t.to);
+            nrestwg = (unsigned)((rt.nrest + 63) / 64);
         }
-        if (c->mf_use) {
+        if (t.mf) {
             if (!rt.on) { c->err = "matrix-free trial without the fused retraction"; return NLLS_ERR_NOT_READY; }
             const int rc = enqueue_mf_backsub(c, rt, write_red, zptr, zcount, nextra, nrestwg); if (rc != NLLS_OK) return rc;
-            c->tE_valid = false; c->mf_step = true; c->tiles_zeroed = true; c->mf_to_phys = c->vars_slot[c->trial_to]; c->mf_from_phys = c->vars_slot[c->trial_from];
+            mf_backsub_done(c, t.to, t.from);
             return NLLS_OK;
         }
-        c->mf_step = false;
 #define LAUNCH_BSF(DV) hipLaunchKernelGGL((schur_backsub_fast_kernel<DV>), dim3((unsigned)c->n_fast_groups + nextra + nrestwg), dim3(64), 0, c->stream, c->A.p, c->b.p, c->d_elim_desc.p, c->d_elim_rc.p, \
                 c->Cinv.p, c->s_ptr(), c->x.p, c->tE.p, (uint32_t)c->n_fast_groups, c->d_red_boff.p, n, write_red, zptr, zcount, nextra, rt)
-        if (c->n_fast_groups > 0) { if (c->fast_dv == 3) LAUNCH_BSF(3); else if (c->fast_dv == 2) LAUNCH_BSF(2); else if (c->fast_dv == 1) LAUNCH_BSF(1); c->tE_valid = true; if (tiles_direct) c->tiles_zeroed = true; else c->S_zeroed = zero_S; }
-        else c->retract_done = false;
+        if (c->n_fast_groups > 0) { if (c->fast_dv == 3) LAUNCH_BSF(3); else if (c->fast_dv == 2) LAUNCH_BSF(2); else if (c->fast_dv == 1) LAUNCH_BSF(1); }
+        backsub_done(c, c->n_fast_groups > 0, tiles_direct, zero_S, rt.on);
 #undef LAUNCH_BSF
     }
     HIPCHK(hipGetLastError());
@@ -1671,30 +1662,28 @@ __global__ __launch_bounds__(TPB) void tiny_trial_finish_kernel(DenseFin fin) {
 }
 // the small dense system's LM trial: damped solve + statistics (+ retraction) in one launch, then the cost sweep; scalars[0..10] as enqueue_lm_trial_tail leaves them
 int enqueue_tiny_trial_finish_pending(nlls_ctx* c) {
-    if (!c->dense_fin_pending) return NLLS_OK;
-    c->dense_fin_pending = false;
-    hipLaunchKernelGGL(tiny_trial_finish_kernel, dim3(1), dim3(TPB), 0, c->stream, c->dense_fin);
+    if (!take(c->fin.dense_pending)) return NLLS_OK;
+    hipLaunchKernelGGL(tiny_trial_finish_kernel, dim3(1), dim3(TPB), 0, c->stream, c->fin.dense);
     HIPCHK(hipGetLastError());
     return NLLS_OK;
 }
-int enqueue_tiny_dense_trial(nlls_ctx* c, int to, int from, bool lookahead_follows) {
+int enqueue_tiny_dense_trial(nlls_ctx* c, int to, int from) {
     const int n = (int)c->info.ndof; const int64_t nvar = c->info.nvar;
     const bool fused_retract = nvar <= TINY_RETRACT_MAX;
-    c->status_known_zero = false; c->retract_done = false;
+    drop(c->zero.status); drop(c->step.retract_done);
     hipLaunchKernelGGL(tiny_dense_trial_kernel, dim3(1), dim3(64), 0, c->stream, c->A.p, c->b.p, c->d_red_boff.p, c->lambda, n, c->x.p, c->scalars.p, c->d_status.p,
                        c->d_var_kind.p, c->d_var_dim.p, c->d_var_off.p, c->d_var_boff.p, fused_retract ? nvar : (int64_t)0, vars_ptr(c, from), vars_ptr(c, to));
     HIPCHK(hipGetLastError());
     if (!fused_retract) { const int rc = enqueue_retract(c, to, from); if (rc != NLLS_OK) return rc; }
     int64_t ncp = 0;
     { const int rc = enqueue_sweep_cost(c, to, TRIAL_COST_POFS, &ncp); if (rc != NLLS_OK) return rc; }
-    c->dense_fin = DenseFin{c->partials.p + TRIAL_COST_POFS, ncp, c->scalars.p, c->h_scalars_dev, (double)(++c->trial_seq)}; c->dense_fin_pending = true;
-    if (lookahead_follows) return NLLS_OK;                        // (the look-ahead sweep's accumulate launch carries the finishing reduction; nlls_lm_trial launches what is left)
-    return enqueue_tiny_trial_finish_pending(c);
+    defer_dense_fin(c, DenseFin{c->partials.p + TRIAL_COST_POFS, ncp, c->scalars.p, c->h_scalars_dev, (double)(++c->trial_seq)});   // (nlls_lm_trial: the look-ahead sweep carries it, or a launch of its own)
+    return NLLS_OK;
 }
 
-int enqueue_solve(nlls_ctx* c) {
-    int rc = enqueue_solve_local(c); if (rc != NLLS_OK) return rc;
-    return enqueue_solve_finish(c);
+int enqueue_solve(nlls_ctx* c, const TrialArgs& t) {
+    int rc = enqueue_solve_local(c, t.mf); if (rc != NLLS_OK) return rc;
+    return enqueue_solve_finish(c, t);
 }
 
 }  // namespace nlls

@@ -207,8 +207,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
                     int32_t ngroups, const nlls_cost_group* groups, int32_t flags) {
     c->rank = c->shard_rank; c->nranks = c->shard_nranks; c->replicated = false;      // what nlls_set_shard asked for (a problem that does not shard falls back to replicas below)
     c->presharded = (flags & NLLS_FLAG_PRESHARDED) != 0 && c->nranks > 1;
-    c->ready = false; c->solved = false; c->have_grad = false; c->lambda = 0; c->reduced_summed = true; c->n_stage0 = 0; c->n_lazy_trials = 0;
-    c->mf_stale_point = false; c->spec_pending = false; c->spec_stale = false; c->spec_armed = true; c->grad_phys = -1; c->grad_level = 0; c->sweeps_since_set = 0; c->dense_fin_pending = false; c->heavy_rows_zeroed = false; c->tail_zero_for_lookahead = false;   // (a re-upload starts from a clean look-ahead state)
+    c->ready = false; c->n_stage0 = 0; c->n_lazy_trials = 0; upload_started(c);
     { std::vector<HotItem> v; hot_set(c, v); for (HotItem& it : v) if (!*it.owned) { *it.pp = nullptr; *it.owned = true; } }   // what lived in the previous upload's arena is gone with it
     c->arena.release(); c->arena_pre.release();     // ... so release it NOW: a re-upload would otherwise hold two arenas (and every buffer once more) at its peak
     c->groups.clear();
@@ -338,7 +337,6 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     HIPCHK(c->d_diag_off.upload(c->diag_off)); HIPCHK(c->d_blocksizes.upload(c->blocksizes));
     if (!c->h_scalars) { HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_scalars), 64 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)); memset(c->h_scalars, 0, 64 * sizeof(double));
         if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_scalars_dev), c->h_scalars, 0) != hipSuccess) c->h_scalars_dev = nullptr; }
-    c->S_zeroed = false;
     HIPCHK(c->scalars.alloc(64));
 
     // ---- observation sharding: costs are owned by the rank that owns their eliminated block ----------
@@ -605,7 +603,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
 // slot's all reduced, no fixed variable, exactly one block per (eliminated block, neighbour) pair -- i.e. the member's blocks ARE the column blocks of its [E], one each.
 // Leaves c->mf_ok false (and nothing else changed) whenever the problem does not qualify: nlls_lm_trial then takes the materialised path.
 int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const uint64_t* bi, int32_t flags) {
-    c->mf_ok = false; c->mf_group = -1; c->mf_ps = -1; c->mf_step = false; c->mf_use = false; c->mf_q.release(); c->d_mf_desc.release(); c->mf_nbig = 0;
+    c->mf_ok = false; c->mf_group = -1; c->mf_ps = -1; c->mf_q.release(); c->d_mf_desc.release(); c->mf_nbig = 0;
     for (Group& G : c->groups) { G.mf_data.release(); G.mf_voff.release(); }
     // (the gather index of build_schur was built for this trial: without it -- or when the problem turns out not to qualify below -- it goes again, unless the flag asked for it)
     struct Drop { nlls_ctx* c; bool keep; ~Drop() { if (!c->mf_ok && !keep) { c->gather_ready = false; c->slab.release(); c->d_slab_off.release(); c->d_slab_groups.release(); c->d_gjobs.release(); c->d_gcons.release(); c->n_gjobs = 0; } } } drop{c, (flags & NLLS_FLAG_DETERMINISTIC) != 0};
@@ -758,9 +756,8 @@ int build_schur(nlls_ctx* c, int32_t flags) {
     // (a re-upload -- or the retry without Schur elimination after an unsupported shape -- must not see the previous
     // attempt's supernode lists: the solve dispatches on these counters)
     c->n_fast_groups = 0; c->n_slow_groups = 0; c->n_fast_members = 0; c->n_fast_narrow = 0; c->n_fast_n60 = 0; c->fast_dv = 0;
-    c->h_elim_desc.clear(); c->h_erow.clear(); c->h_eptr.clear(); c->h_enbr_block.clear(); c->mf_ok = false; c->mf_step = false; c->mf_use = false;
-    c->tE_valid = false; c->S_zeroed = false; c->status_known_zero = false; c->step_cached = false; c->bcr.release();
-    c->elim_slab = false; c->gather_ready = false; c->h_slab_off.clear(); c->tiles_zeroed = false; c->slab.release(); c->d_slab_off.release(); c->d_slab_groups.release(); c->d_gjobs.release(); c->d_gcons.release(); c->n_gjobs = 0;
+    c->h_elim_desc.clear(); c->h_erow.clear(); c->h_eptr.clear(); c->h_enbr_block.clear(); c->mf_ok = false; c->bcr.release();
+    c->elim_slab = false; c->gather_ready = false; c->h_slab_off.clear(); c->slab.release(); c->d_slab_off.release(); c->d_slab_groups.release(); c->d_gjobs.release(); c->d_gcons.release(); c->n_gjobs = 0;
     // (the solve also dispatches on the SIZE of these lists: an upload without elimination must not inherit them)
     c->d_elim_ptr.release(); c->d_elim_nbr.release(); c->d_elim_diag.release(); c->d_elim_boff.release(); c->d_elim_dim.release(); c->d_elim_group.release();
     c->d_fast_groups.release(); c->d_elim_desc.release(); c->d_elim_rc.release(); c->d_slow_groups.release(); c->d_slow_blocks.release(); c->d_fast_members.release(); c->Cinv.release(); c->tE.release();

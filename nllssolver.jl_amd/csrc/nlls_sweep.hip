@@ -739,10 +739,9 @@ static void launch_gh_slot(nlls_ctx* c, const Group& G, const double* vars, int6
                                gh_args<KIND>(c, G, E, vars, false, c->partials.p + pbase));
             pbase += E.nlight;
         }
-        if (E.nheavy > 0 && c->mf_fin_pending && c->nzero == 0) {      // (a matrix-free trial's finishing workgroup rides in front: nlls_lm_trial deferred it)
-            c->mf_fin_pending = false;
+        if (E.nheavy > 0 && c->nzero == 0 && take(c->fin.mf_pending)) {      // (a matrix-free trial's finishing workgroup rides in front: nlls_lm_trial deferred it)
             hipLaunchKernelGGL((gh_heavy_fin_kernel<KIND, SLOT>), dim3(1 + (unsigned)((E.nheavy + HROWS - 1) / HROWS)), dim3(TPB), gh_heavy_lds(E.heavy_lds) * sizeof(double), c->stream,
-                               gh_args<KIND>(c, G, E, vars, true, c->partials.p + pbase), E.heavy_lds, mf_fin_args(c));
+                               gh_args<KIND>(c, G, E, vars, true, c->partials.p + pbase), E.heavy_lds, mf_fin_args(c, c->h_scalars_dev));
             pbase += E.nheavy;
         } else if (E.nheavy > 0) {
             hipLaunchKernelGGL((gh_heavy_kernel<KIND, SLOT>), dim3((unsigned)((E.nheavy + HROWS - 1) / HROWS)), dim3(TPB), gh_heavy_lds(E.heavy_lds) * sizeof(double), c->stream,
@@ -805,7 +804,7 @@ static bool launch_gh_fold(nlls_ctx* c, const Group& G, const double* vars, int6
     }
     return true;
 }
-// the reduced slot's pass alone (the gradient sweep of the matrix-free LM trial, nlls_ctx::grad_level 1: the eliminated rows of A.data are never formed)
+// the reduced slot's pass alone (the gradient sweep of the matrix-free LM trial, nlls::Linearisation::level 1: the eliminated rows of A.data are never formed)
 template <int KIND>
 static void launch_gh_reduced(nlls_ctx* c, const Group& G, const double* vars, int64_t& pbase) {
     if constexpr (Res<KIND>::NDEPS == 2) { if (c->mf_ps == 0) launch_gh_slot<KIND, 1>(c, G, vars, pbase); else launch_gh_slot<KIND, 0>(c, G, vars, pbase); }
@@ -824,7 +823,7 @@ static int launch_gh(nlls_ctx* c, const Group& G, const double* vars, int64_t& p
         int grid = (int)std::min<int64_t>((G.dense.n + TPB - 1) / TPB, c->tiny_dense ? TINY_DENSE_MAX_WGS : 1024);
         double* slab = nullptr; DenseFin fin{};
         if (c->tiny_dense) { slab = c->dense_slab.p + (size_t)c->dense_slab_used * (size_t)(ndof * ndof + ndof); c->dense_slab_used += grid; }
-        if (c->dense_fin_pending) { fin = c->dense_fin; c->dense_fin_pending = false; }
+        if (take(c->fin.dense_pending)) fin = c->fin.dense;
         hipLaunchKernelGGL(gh_dense_kernel<KIND>, dim3(grid + (fin.cpart ? 1 : 0)), dim3(TPB), use_lds ? (size_t)(ndof * ndof + ndof) * sizeof(double) : 0, c->stream,
                            vars, G.dense.data.p, G.dense.voff.p, G.dense.brow.p, G.dense.n, G.rk, ndof, use_lds, c->A.p, c->b.p, c->partials.p + pbase, slab, fin);
         pbase += grid;
@@ -834,9 +833,7 @@ static int launch_gh(nlls_ctx* c, const Group& G, const double* vars, int64_t& p
 
 int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost, int which, int mode) {
     if (mode == 1 && (!c->mf_ok || want_cost)) mode = 0;
-    c->grad_level = mode == 1 ? 1 : 2; if (mode == 1) c->mf_reduced_sweeps++; else c->full_sweeps++;
-    c->tE_valid = false; c->step_cached = false; c->mf_step = false;  // A and b change: what the last solve kept of them is stale
-    c->grad_phys = c->vars_slot[which];           // the variable set (physical slot) A and b are the linearisation of
+    sweep_enqueued(c, which, mode == 1 ? 1 : 2); if (mode == 1) c->mf_reduced_sweeps++; else c->full_sweeps++;
     const double* vars = vars_ptr(c, which); int64_t pbase = 0;
     c->dense_slab_used = 0;
     if (c->tiny_dense) {
@@ -844,9 +841,7 @@ int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost, int which, int mode) {
     } else if (!c->info.is_sparse) {
         HIPCHK(hipMemsetAsync(c->A.p, 0, sizeof(double) * std::max<int64_t>(c->info.nnz_data, 1), c->stream));
         HIPCHK(hipMemsetAsync(c->b.p, 0, sizeof(double) * std::max<int64_t>(c->info.ndof, 1), c->stream));
-    } else if (c->nzero > 0 && c->heavy_rows_zeroed) {
-        c->heavy_rows_zeroed = false;          // (the finishing launch of the trial in front of this look-ahead sweep has done it)
-    } else if (c->nzero > 0) {
+    } else if (c->nzero > 0 && !take(c->zero.heavy_rows)) {      // (zeroed: the finishing launch of the trial in front of this look-ahead sweep has done it)
         hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)c->nzero), dim3(64), 0, c->stream, c->A.p, c->d_zero_off.p, c->d_zero_len.p, c->b.p, c->d_zero_b_off.p, c->d_zero_b_len.p);
     }
     const bool prof = c->prof_sweep && !c->prof_ev.empty() && mode == 0;      // (the in-situ profile is of the full accumulate launch)
