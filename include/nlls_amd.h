@@ -45,6 +45,7 @@ typedef struct nlls_ctx nlls_ctx;
 #define NLLS_MAX_ARGS        10
 #define NLLS_MAX_BLOCK_SZ    32
 #define NLLS_MAX_STATIC_VAR  64
+#define NLLS_SINGLES_MAX_DOF 12   /* widest variable nlls_optimize_singles relaxes (the largest storage a fixed-size kind may have) */
 
 /* ---- variable kinds: nvars()/update() of src/variable.jl:3-32, src/robustadaptive.jl:3-23 --- */
 #define NLLS_VAR_EUCLIDEAN              1 /* EuclideanVector{N} / Number (N=1): dof N, storage N, v+d       */
@@ -323,7 +324,8 @@ int  nlls_solve(nlls_ctx* ctx, double* x_out);
  * Tile-sparse solver (solve_mode 3): [16] tiles of 128 unknowns, [17] levels of the tile elimination tree (the dependent chain of the factorisation),
  * [18] lower tiles stored (fill included), [19] kernel launches per reduced solve, [20] 128^3 tile products per factorisation (updates + panels).
  * [21], [22] look-ahead sweeps used / thrown away; [23] matrix-free LM trials, [24] gradient sweeps of the reduced rows only, [25] full accumulate sweeps since the upload;
- * [26] unknowns per block of the block cyclic reduction (the smallest multiple of 16 that keeps the band block tridiagonal: may be below the bandwidth [5]). */
+ * [26] unknowns per block of the block cyclic reduction (the smallest multiple of 16 that keeps the band block tridiagonal: may be below the bandwidth [5]);
+ * [27], [28] variables the last nlls_optimize_singles call relaxed one per wavefront / one per thread (on this rank). */
 int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
 /* Run-time switches of a context (A/B measurements, parity tests through both paths on ONE upload):
  *   NLLS_OPT_MATERIALIZE  value != 0: nlls_lm_trial eliminates from the materialised A.data (the round-5 path) although the structure qualifies for the
@@ -358,7 +360,9 @@ int  nlls_retract(nlls_ctx* ctx, int32_t to, int32_t from);
  * sets, in the reference's order (the Python host and the shim do).  iterator: 0 Newton, 1 Levenberg-Marquardt, 2 dogleg,
  * 3 gradient descent (src/iterators.jl), each reset per variable, with the outer loop and termination rules of
  * src/optimize.jl:109-180; operates on NLLS_VARS_CURRENT in place; iters_out (nsel, may be NULL) receives the iterations each
- * variable took.  Variables of at most 6 dof. */
+ * variable took.  Variables of at most NLLS_SINGLES_MAX_DOF dof.  A variable of more than 6 dof, or of at least 64 cost blocks (NLLS_SINGLES_WAVE_MIN=n in the environment of
+ * nlls_ctx_create: n), is relaxed by one wavefront, whose lanes deal its blocks; every other one by one thread.  The result of a variable does not depend on which others the
+ * call lists. */
 int  nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices, const int64_t* cptr, const int32_t* cgroup, const int64_t* cindex,
                            const int32_t* cslot, int32_t iterator, int32_t maxiters, int32_t maxfails, double reldcost, double absdcost, double dstep, int64_t* iters_out);
 /* The Levenberg-Marquardt outer loop itself, on the host side of this ABI (csrc/nlls_lm.cpp): up to `niter` passes of the while-loop body

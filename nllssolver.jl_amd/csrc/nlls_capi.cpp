@@ -63,6 +63,7 @@ int nlls_ctx_create(const int32_t* device_ids, int32_t ndev, nlls_ctx** out) { N
     { const char* e = getenv("NLLS_ELIM_SPLIT"); if (e && e[0] == '1') c->elim_split = true; }
     { const char* e = getenv("NLLS_DENSE_STEP_BACKWARD"); if (e && e[0] == '1') c->dense_fused_bwd = false; }
     { const char* e = getenv("NLLS_DENSE_T128_MIN"); if (e) c->dense_t128_min = atoi(e); }
+    { const char* e = getenv("NLLS_SINGLES_WAVE_MIN"); const long long v = e ? atoll(e) : 0; if (v > 0) c->singles_wave_min = (int64_t)v; }
     if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return NLLS_ERR_HIP; }
     c->own_stream = true;
     if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -483,12 +484,16 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
     for (int64_t i = 0; i < nsel; ++i) {
         const int64_t v = varindices[i] - 1;
         if (v < 0 || v >= ctx->info.nvar || cptr[i + 1] < cptr[i]) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_optimize_singles: bad variable index or cost list");
-        if (var_dof(ctx->var_kind[v], ctx->var_dim[v]) > 6) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_optimize_singles: variable with more than 6 degrees of freedom");
+        if (var_dof(ctx->var_kind[v], ctx->var_dim[v]) > (ctx->var_kind[v] == NLLS_VAR_DYNAMIC ? 6 : NLLS_SINGLES_MAX_DOF)) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_optimize_singles: variable with more than 12 degrees of freedom (NLLS_SINGLES_MAX_DOF; a dynamic-size one: 6)");
     }
-    // this rank's share: the variables all of whose blocks are local, with the blocks' LOCAL indices
-    std::vector<int64_t> sel, cp(1, 0), pos; std::vector<uint32_t> cidx; std::vector<int32_t> cg, cs; double spread = 0.0;
+    // this rank's share: the variables all of whose blocks are local, with the blocks' LOCAL indices -- in three runs, one per kernel: a variable of more than 6 dof, or of
+    // at least singles_wave_min blocks, gets a wavefront (below that a wavefront has idle lanes in its only pass, while the thread kernel packs 64 variables into one)
+    std::vector<int64_t> sel, cp(1, 0), pos; std::vector<uint32_t> cidx; std::vector<int32_t> cg, cs; double spread = 0.0; int64_t nrun[3] = {0, 0, 0};
     sel.reserve((size_t)nsel); cidx.reserve((size_t)nc); cg.reserve((size_t)nc); cs.reserve((size_t)nc);
+    for (int run = 0; run < 3; ++run)
     for (int64_t i = 0; i < nsel; ++i) {
+        const int dof = var_dof(ctx->var_kind[varindices[i] - 1], ctx->var_dim[varindices[i] - 1]);
+        if (run != (dof > 6 ? 2 : std::max<int64_t>(cptr[i + 1] - cptr[i], 1) >= ctx->singles_wave_min ? 1 : 0)) continue;      // (an empty list counts as one block: NLLS_SINGLES_WAVE_MIN=1 sends everything to the wavefront kernel)
         int64_t mine = 0; const size_t mark = cidx.size();
         for (int64_t e = cptr[i]; e < cptr[i + 1]; ++e) {
             if (cgroup[e] < 0 || cgroup[e] >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_optimize_singles: bad cost group");
@@ -502,7 +507,7 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
         }
         const int64_t all = cptr[i + 1] - cptr[i];
         // a variable without any block is relaxed (trivially) by rank 0
-        if (mine == all && (all > 0 || ctx->rank == 0 || !sharded)) { sel.push_back(varindices[i] - 1); pos.push_back(i); cp.push_back((int64_t)cidx.size()); }
+        if (mine == all && (all > 0 || ctx->rank == 0 || !sharded)) { sel.push_back(varindices[i] - 1); pos.push_back(i); cp.push_back((int64_t)cidx.size()); ++nrun[run]; }
         else { cidx.resize(mark); cg.resize(mark); cs.resize(mark); if (mine != 0) spread = 1.0; }
     }
     if (sharded) {          // a variable whose blocks are spread over ranks: declined everywhere (one small collective, so that no rank is left in the gather below)
@@ -520,10 +525,13 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
     HIPCHK(d_groups.upload(gbuf));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     vars_written(ctx, NLLS_VARS_CURRENT, true);
-    if (nloc > 0) TRY(enqueue_optimize_singles(ctx, nloc, d_sel.p, d_cptr.p, d_cgroup.p, d_cidx.p, d_cslot.p, d_groups.p, iterator, maxiters, maxfails, reldcost, absdcost, dstep, d_iters.p));
+    ctx->singles_thread = nrun[0]; ctx->singles_wave = nrun[1] + nrun[2];
+    if (nloc > 0) TRY(enqueue_optimize_singles(ctx, nrun[0], nrun[1], nrun[2], d_sel.p, d_cptr.p, d_cgroup.p, d_cidx.p, d_cslot.p, d_groups.p, iterator, maxiters, maxfails, reldcost, absdcost, dstep, d_iters.p));
     if (!sharded) {
-        if (iters_out) HIPCHK(hipMemcpyAsync(iters_out, d_iters.p, sizeof(int64_t) * nsel, hipMemcpyDeviceToHost, ctx->stream));      // (unsharded: nloc == nsel, the caller's order)
+        std::vector<int64_t> hit((size_t)nsel);                                                                        // (unsharded: nloc == nsel, in the order of the runs)
+        if (iters_out) HIPCHK(hipMemcpyAsync(hit.data(), d_iters.p, sizeof(int64_t) * nsel, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (iters_out) for (int64_t i = 0; i < nsel; ++i) iters_out[pos[(size_t)i]] = hit[(size_t)i];
         return NLLS_OK;
     }
     // the gather: [storage of the variables this rank relaxed, zero elsewhere | their iteration counts at the caller's positions] summed over ranks; then every listed
@@ -574,14 +582,15 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
     int32_t status[16] = {0};
     HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    const int64_t vals[27] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
+    const int64_t vals[29] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
                               ctx->ahead.hits, ctx->ahead.misses /* look-ahead sweeps used / thrown away */,
                               ctx->mf_trials, ctx->mf_reduced_sweeps, ctx->full_sweeps /* matrix-free LM trials, sweeps of the reduced rows only, full accumulate sweeps since the upload */,
-                              ctx->bcr.ready ? 16 * ctx->bcr.NT : 0 /* unknowns per block of the block cyclic reduction */};
-    for (int i = 0; i < n && i < 27; ++i) out[i] = vals[i];
+                              ctx->bcr.ready ? 16 * ctx->bcr.NT : 0 /* unknowns per block of the block cyclic reduction */,
+                              ctx->singles_wave, ctx->singles_thread /* variables the last nlls_optimize_singles call relaxed one per wavefront / one per thread */};
+    for (int i = 0; i < n && i < 29; ++i) out[i] = vals[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

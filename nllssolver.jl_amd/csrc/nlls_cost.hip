@@ -191,10 +191,19 @@ __global__ __launch_bounds__(TPB) void max_finish_kernel(const double* __restric
 // ================================================================================================
 struct SinglesGroup { int kind; const double* data; const uint32_t* voff; RobustSpec rk; };
 struct SinglesOpt { int maxiters, maxfails; double reldcost, absdcost, dstep; int iterator; };   // iterator: 0 Newton, 1 Levenberg-Marquardt, 2 dogleg, 3 gradient descent
-constexpr int SGL_MAXD = 6;                                   // dof of a variable optimised this way (registry maximum)
+constexpr int SGL_MAXD = 6;                                   // dof of a variable the thread kernel takes
+constexpr int SGL_WAVE_MAXD = NLLS_SINGLES_MAX_DOF;           // dof of a variable the wavefront kernel takes (MAXST: every fixed-size kind)
+static_assert(SGL_WAVE_MAXD <= MAXST && SGL_MAXD <= SGL_WAVE_MAXD);
+
+// What one subproblem keeps between its evaluations: the sums over its blocks (g, H in full, column-major with stride MAXD), the step, the factor.  The thread kernel has
+// one per lane in private memory.  The wavefront kernel has one per wavefront in LDS: its 64 lanes hold identical values, and arrays that the solver indexes at run time
+// would otherwise live in scratch memory (12 dof: 90 doubles of sums, as many of the factor).
+template <int MAXD> struct SinglesWork { double g[MAXD], H[MAXD * MAXD], x[MAXD], Ld[MAXD * MAXD], y[MAXD], cauchy[MAXD]; };
+// a loop over a variable's storage: the wavefront kernel keeps the three points of the subproblem in registers, so its loops are unrolled under a wave-uniform guard
+#define SGL_FOR_ST(q) _Pragma("unroll") for (int q = 0; q < (WAVE ? MAXST : ns); ++q) if (!WAVE || q < ns)
 
 // one cost block of the subproblem: the variable's storage comes from `vloc`, everything else from `vars`
-template <int KIND>
+template <int KIND, int MAXD, bool WAVE>
 NLLS_DEV void singles_block(const SinglesGroup& G, uint32_t k, int slot, const double* __restrict__ vars, const double* vloc,
                             bool want_gh, double& cost, double* g, double* H) {
     using R = Res<KIND>; using I = ResInfo<KIND>;
@@ -217,67 +226,81 @@ NLLS_DEV void singles_block(const SinglesGroup& G, uint32_t k, int slot, const d
     if (!want_gh) return;
     static_for<R::NDEPS>([&](auto Sc) {
         constexpr int S = decltype(Sc)::value;
-        if (S == slot) {
-            constexpr int DS = I::dof(S);
+        constexpr int DS = I::dof(S);
+        if constexpr (DS > MAXD) return;                      // (a wider slot never reaches this kernel: nlls_optimize_singles)
+        else if constexpr (WAVE) {
+            // (no branch on the slot around these stores: the compiler merges the ends of such branches into ONE store through a selected address, and an array whose
+            //  address is selected at run time stays in scratch memory)
+            const bool mine = S == slot;
 #pragma unroll
             for (int j = 0; j < DS; ++j) {
-                g[j] += g_elem<KIND, S>(B, j);
+                g[j] += mine ? g_elem<KIND, S>(B, j) : 0.0;
 #pragma unroll
-                for (int i = 0; i < DS; ++i) H[i + SGL_MAXD * j] += h_elem<KIND, S, S>(B, i, j);
+                for (int i = j; i < DS; ++i) H[i + MAXD * j] += mine ? h_elem<KIND, S, S>(B, i, j) : 0.0;
+            }
+        } else {
+            if (S == slot) {
+#pragma unroll
+                for (int j = 0; j < DS; ++j) {
+                    g[j] += g_elem<KIND, S>(B, j);
+#pragma unroll
+                    for (int i = 0; i < DS; ++i) H[i + MAXD * j] += h_elem<KIND, S, S>(B, i, j);
+                }
             }
         }
     });
 }
 
-__global__ __launch_bounds__(64) void singles_lm_kernel(const SinglesGroup* __restrict__ groups, const int64_t* __restrict__ selvar, int64_t nsel,
-                                                        const int64_t* __restrict__ cptr, const int32_t* __restrict__ cgroup, const uint32_t* __restrict__ cidx,
-                                                        const int32_t* __restrict__ cslot, const int32_t* __restrict__ vkind, const int32_t* __restrict__ vdim,
-                                                        const uint32_t* __restrict__ voffs, SinglesOpt opt, double* __restrict__ vars, int64_t* __restrict__ iters_out) {
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= nsel) return;
-    const int64_t v = selvar[t];
-    const int kind = vkind[v], dim = vdim[v], nd = var_dof(kind, dim), ns = var_storage(kind, dim);
-    const uint32_t off = voffs[v];
-    double vcur[MAXST], vnext[MAXST], vbest[MAXST];
-    for (int q = 0; q < ns; ++q) { vcur[q] = vars[off + q]; vbest[q] = vcur[q]; }
-    double g[SGL_MAXD], H[SGL_MAXD * SGL_MAXD];
-    auto evaluate = [&](const double* vloc, bool want_gh) {
-        double cost = 0;
-        if (want_gh) { for (int i = 0; i < SGL_MAXD; ++i) g[i] = 0; for (int i = 0; i < SGL_MAXD * SGL_MAXD; ++i) H[i] = 0; }
-        for (int64_t e = cptr[t]; e < cptr[t + 1]; ++e) {
-            const SinglesGroup G = groups[cgroup[e]];
-            switch (G.kind) {
-#define X(K) case K: singles_block<K>(G, cidx[e], cslot[e], vars, vloc, want_gh, cost, g, H); break;
-                NLLS_FOR_EACH_RES(X)
+// update(var, step) without a run-time index into the wavefront kernel's per-lane arrays: var_update_real, the kind a constant in every call
+template <int MAXD>
+NLLS_DEV void singles_update_static(int kind, int dim, const double* in, const double* d, double* out) {
+    switch (kind) {
+    case NLLS_VAR_EUCLIDEAN:
+#pragma unroll
+        for (int i = 0; i < MAXD; ++i) if (i < dim) out[i] = in[i] + d[i];
+        break;
+#define X(K) case K: if constexpr (var_dof(K, 0) <= MAXD) var_update_real(K, dim, in, d, out); break;
+    X(NLLS_VAR_ZERO_TO_INF) X(NLLS_VAR_ZERO_TO_ONE) X(NLLS_VAR_CONTAMINATED_GAUSSIAN) X(NLLS_VAR_POSE_SO3) NLLS_USER_VAR(X)
 #undef X
-            }
-        }
-        return cost;
-    };
+    }
+}
+
+// The subproblem of ONE variable, from the point in vcur: src/optimize.jl:109-180 with the iterators of src/iterators.jl.  evaluate(vloc, want_gh) returns the cost at
+// vloc and, with want_gh, leaves the gradient and the Hessian (both triangles) in w.g and w.H.  The result is left in vcur; returns the iterations taken.  The thread
+// kernel runs it in one lane; the wavefront kernel in all 64 in lockstep on identical sums: every branch in here is wave-uniform, and every store to `w` is the same
+// value from every lane.
+template <int MAXD, bool WAVE, class Eval>
+NLLS_DEV int singles_iterate(const int kind, const int dim, const int nd, const int ns, const SinglesOpt& opt, double* vcur, SinglesWork<MAXD>& w, Eval&& evaluate) {
+    double* const g = w.g; double* const H = w.H; double* const x = w.x; double* const cauchy = w.cauchy;
+    double vnext[MAXST], vbest[MAXST];
+    SGL_FOR_ST(q) vbest[q] = vcur[q];
     double bestcost = evaluate(vcur, true), cost = bestcost;   // src/optimize.jl:118
     double lambda = 0.0, trust = 0.0, stepsize = 1.0;          // reset!(iteratedata): every subproblem starts from the iterator's initial state
     int fails = 0, iter = 0;
-    double x[SGL_MAXD];
     // (H + lam I) x = -g by LDL' (the univariate system; src/linearsolver.jl:20-32)
     auto solve = [&](double lam) {
-        double Ld[SGL_MAXD * SGL_MAXD], y[SGL_MAXD];
-        for (int j = 0; j < nd; ++j) for (int i = j; i < nd; ++i) Ld[i + SGL_MAXD * j] = H[i + SGL_MAXD * j] + (i == j ? lam : 0.0);
+        double* const Ld = w.Ld; double* const y = w.y;
+        for (int j = 0; j < nd; ++j) for (int i = j; i < nd; ++i) Ld[i + MAXD * j] = H[i + MAXD * j] + (i == j ? lam : 0.0);
         for (int j = 0; j < nd; ++j) {
-            double dj = Ld[j + SGL_MAXD * j];
-            for (int k = 0; k < j; ++k) dj -= Ld[j + SGL_MAXD * k] * Ld[j + SGL_MAXD * k] * Ld[k + SGL_MAXD * k];
-            Ld[j + SGL_MAXD * j] = dj;
-            for (int i = j + 1; i < nd; ++i) { double s2 = Ld[i + SGL_MAXD * j];
-                for (int k = 0; k < j; ++k) s2 -= Ld[i + SGL_MAXD * k] * Ld[j + SGL_MAXD * k] * Ld[k + SGL_MAXD * k];
-                Ld[i + SGL_MAXD * j] = s2 / dj; }
+            double dj = Ld[j + MAXD * j];
+            for (int k = 0; k < j; ++k) dj -= Ld[j + MAXD * k] * Ld[j + MAXD * k] * Ld[k + MAXD * k];
+            Ld[j + MAXD * j] = dj;
+            for (int i = j + 1; i < nd; ++i) { double s2 = Ld[i + MAXD * j];
+                for (int k = 0; k < j; ++k) s2 -= Ld[i + MAXD * k] * Ld[j + MAXD * k] * Ld[k + MAXD * k];
+                Ld[i + MAXD * j] = s2 / dj; }
         }
-        for (int i = 0; i < nd; ++i) { double s2 = g[i]; for (int k = 0; k < i; ++k) s2 -= Ld[i + SGL_MAXD * k] * y[k]; y[i] = s2; }
-        for (int i = 0; i < nd; ++i) y[i] /= Ld[i + SGL_MAXD * i];
-        for (int i = nd - 1; i >= 0; --i) { double s2 = y[i]; for (int k = i + 1; k < nd; ++k) s2 -= Ld[k + SGL_MAXD * i] * y[k]; y[i] = s2; }
-        for (int i = 0; i < nd; ++i) x[i] = -y[i];                             // negate!
+        for (int i = 0; i < nd; ++i) { double s2 = g[i];
+            for (int k = 0; k < i; ++k) s2 -= Ld[i + MAXD * k] * y[k];
+            y[i] = s2; }
+        for (int i = 0; i < nd; ++i) y[i] /= Ld[i + MAXD * i];
+        for (int i = nd - 1; i >= 0; --i) { double s2 = y[i]; for (int k = i + 1; k < nd; ++k) s2 -= Ld[k + MAXD * i] * y[k]; y[i] = s2; }
+        for (int i = 0; i < nd; ++i) x[i] = -y[i];                                  // negate!
     };
     auto maxabs_x = [&]() { double m = 0; for (int i = 0; i < nd; ++i) m = is_nan_bits(x[i]) ? x[i] : (is_nan_bits(m) ? m : fmax(m, fabs(x[i]))); return m; };
-    auto trial = [&]() { var_update_real(kind, dim, vcur, x, vnext); return evaluate(vnext, false); };   // update! + cost(varnext)
-    auto quad = [&](const double* u) { double q = 0; for (int j = 0; j < nd; ++j) for (int i = 0; i < nd; ++i) q += u[i] * H[i + SGL_MAXD * j] * u[j]; return q; };   // fast_bAb
+    auto trial = [&]() {                                                       // update! + cost(varnext)
+        if constexpr (WAVE) singles_update_static<MAXD>(kind, dim, vcur, x, vnext); else var_update_real(kind, dim, vcur, x, vnext);
+        return evaluate(vnext, false); };
+    auto quad = [&](const double* u) { double q = 0; for (int j = 0; j < nd; ++j) for (int i = 0; i < nd; ++i) q += u[i] * H[i + MAXD * j] * u[j]; return q; };   // fast_bAb
     while (true) {
         ++iter;
         double maxstep = 0;
@@ -286,7 +309,7 @@ __global__ __launch_bounds__(64) void singles_lm_kernel(const SinglesGroup* __re
             solve(0.0); cost = trial();
         } else if (opt.iterator == 1) {
             // ---- iterate!(LevMarData)   src/iterators.jl:139-172
-            if (lambda == 0.0) { double m = 0; for (int i = 0; i < nd; ++i) m = fmax(m, fabs(H[i + SGL_MAXD * i])); lambda = m * 1e-6; }
+            if (lambda == 0.0) { double m = 0; for (int i = 0; i < nd; ++i) m = fmax(m, fabs(H[i + MAXD * i])); lambda = m * 1e-6; }
             double mu = 2.0;
             while (true) {
                 solve(lambda);                                                     // :149-153
@@ -306,7 +329,7 @@ __global__ __launch_bounds__(64) void singles_lm_kernel(const SinglesGroup* __re
             // ---- iterate!(DoglegData)   src/iterators.jl:47-115
             double gnorm2 = 0; for (int i = 0; i < nd; ++i) gnorm2 += g[i] * g[i];
             const double a = gnorm2 / (quad(g) + 2.2250738585072014e-308);         // floatmin
-            double cauchy[SGL_MAXD]; for (int i = 0; i < nd; ++i) cauchy[i] = -a * g[i];
+            for (int i = 0; i < nd; ++i) cauchy[i] = -a * g[i];
             const double alpha2 = a * a * gnorm2, alpha = sqrt(alpha2); double beta = 0;
             if (trust == 0.0) trust = alpha;                                       // first step: the Cauchy point
             if (alpha < trust) { solve(0.0); double s2 = 0; for (int i = 0; i < nd; ++i) s2 += x[i] * x[i]; beta = sqrt(s2); }
@@ -347,8 +370,8 @@ __global__ __launch_bounds__(64) void singles_lm_kernel(const SinglesGroup* __re
         // ---- src/optimize.jl:128-160
         double dcost = bestcost - cost;
         if (dcost >= 0) { bestcost = cost; fails = 0; }
-        else { dcost = cost; ++fails; if (fails == 1) for (int q = 0; q < ns; ++q) vbest[q] = vcur[q]; }
-        for (int q = 0; q < ns; ++q) vcur[q] = vnext[q];                       // updatefromnext!
+        else { dcost = cost; ++fails; if (fails == 1) SGL_FOR_ST(q) vbest[q] = vcur[q]; }
+        SGL_FOR_ST(q) vcur[q] = vnext[q];                           // updatefromnext!
         int conv = 0;
         conv |= (fabs(cost) == INFINITY) << 0; conv |= (int)is_nan_bits(cost) << 1;
         conv |= (dcost < bestcost * opt.reldcost) << 2; conv |= (dcost < opt.absdcost) << 3;
@@ -357,10 +380,95 @@ __global__ __launch_bounds__(64) void singles_lm_kernel(const SinglesGroup* __re
         if (conv) break;
         evaluate(vcur, true);                                                  // :167-170
     }
-    if (!(bestcost >= cost)) for (int q = 0; q < ns; ++q) vcur[q] = vbest[q];  // updatefrombest!  :173-176
+    if (!(bestcost >= cost)) SGL_FOR_ST(q) vcur[q] = vbest[q];      // updatefrombest!  :173-176
+    return iter;
+}
+
+// ---- one THREAD per variable: many variables of a few blocks each (the points of a bundle adjustment)
+__global__ __launch_bounds__(64) void singles_lm_kernel(const SinglesGroup* __restrict__ groups, const int64_t* __restrict__ selvar, int64_t nsel,
+                                                        const int64_t* __restrict__ cptr, const int32_t* __restrict__ cgroup, const uint32_t* __restrict__ cidx,
+                                                        const int32_t* __restrict__ cslot, const int32_t* __restrict__ vkind, const int32_t* __restrict__ vdim,
+                                                        const uint32_t* __restrict__ voffs, SinglesOpt opt, double* __restrict__ vars, int64_t* __restrict__ iters_out) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= nsel) return;
+    const int64_t v = selvar[t];
+    const int kind = vkind[v], dim = vdim[v], nd = var_dof(kind, dim), ns = var_storage(kind, dim);
+    const uint32_t off = voffs[v];
+    double vcur[MAXST];
+    for (int q = 0; q < ns; ++q) vcur[q] = vars[off + q];
+    SinglesWork<SGL_MAXD> w; double* const g = w.g; double* const H = w.H;
+    auto evaluate = [&](const double* vloc, bool want_gh) {
+        double cost = 0;
+        if (want_gh) { for (int i = 0; i < SGL_MAXD; ++i) g[i] = 0; for (int i = 0; i < SGL_MAXD * SGL_MAXD; ++i) H[i] = 0; }
+        for (int64_t e = cptr[t]; e < cptr[t + 1]; ++e) {
+            const SinglesGroup G = groups[cgroup[e]];
+            switch (G.kind) {
+#define X(K) case K: singles_block<K, SGL_MAXD, false>(G, cidx[e], cslot[e], vars, vloc, want_gh, cost, g, H); break;
+                NLLS_FOR_EACH_RES(X)
+#undef X
+            }
+        }
+        return cost;
+    };
+    const int iter = singles_iterate<SGL_MAXD, false>(kind, dim, nd, ns, opt, vcur, w, evaluate);
     for (int q = 0; q < ns; ++q) vars[off + q] = vcur[q];
     iters_out[t] = iter;
 }
+
+// ---- one WAVEFRONT per variable: a variable of many blocks (a camera), or one wider than the thread kernel's 6 dof.  Lane l evaluates entries l, l + 64, ... of the
+// variable's list and keeps private sums of the cost, g and the lower triangle of H in that order, in registers; the 64 partial sums are added in the fixed order of
+// wave_sum_dpp63 and the total is read back from lane 63 by every lane: the result depends on nothing but the variable's own list (bit-reproducible, whatever else the
+// launch holds).  Every lane then runs singles_iterate on the identical sums -- no divergence, no broadcast of the trial point -- and lane 0 writes the variable.  No atomics.
+// MAXD: the bucket of the variable's dof (6 or SGL_WAVE_MAXD); every per-lane array is indexed at compile time (no scratch memory).
+NLLS_DEV double wave_total(double v) {
+    v = wave_sum_dpp63(v);
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+template <int MAXD>
+__global__ __launch_bounds__(64) void singles_wave_kernel(const SinglesGroup* __restrict__ groups, const int64_t* __restrict__ selvar,
+                                                          const int64_t* __restrict__ cptr, const int32_t* __restrict__ cgroup, const uint32_t* __restrict__ cidx,
+                                                          const int32_t* __restrict__ cslot, const int32_t* __restrict__ vkind, const int32_t* __restrict__ vdim,
+                                                          const uint32_t* __restrict__ voffs, SinglesOpt opt, double* __restrict__ vars, int64_t* __restrict__ iters_out) {
+    constexpr bool WAVE = true;
+    __shared__ SinglesWork<MAXD> w;                            // (one wavefront per workgroup)
+    const int64_t t = blockIdx.x; const int lane = threadIdx.x;
+    const int64_t v = selvar[t];
+    const int kind = vkind[v], dim = vdim[v], nd = var_dof(kind, dim), ns = var_storage(kind, dim);
+    const uint32_t off = voffs[v];
+    const int64_t e0 = cptr[t], e1 = cptr[t + 1];
+    double vcur[MAXST];
+    SGL_FOR_ST(q) vcur[q] = vars[off + q];
+    auto evaluate = [&](const double* vloc, bool want_gh) {
+        double cost = 0, g[MAXD], H[MAXD * MAXD];              // this lane's sums (of H only i >= j is ever touched)
+        if (want_gh) {
+#pragma unroll
+            for (int j = 0; j < MAXD; ++j) { g[j] = 0;
+#pragma unroll
+                for (int i = j; i < MAXD; ++i) H[i + MAXD * j] = 0; }
+        }
+        for (int64_t e = e0 + lane; e < e1; e += 64) {
+            const SinglesGroup G = groups[cgroup[e]];
+            switch (G.kind) {
+#define X(K) case K: singles_block<K, MAXD, true>(G, cidx[e], cslot[e], vars, vloc, want_gh, cost, g, H); break;
+                NLLS_FOR_EACH_RES(X)
+#undef X
+            }
+        }
+        cost = wave_total(cost);
+        if (want_gh) {
+#pragma unroll
+            for (int j = 0; j < MAXD; ++j) if (j < nd) {
+                w.g[j] = wave_total(g[j]);
+#pragma unroll
+                for (int i = j; i < MAXD; ++i) if (i < nd) { const double h = wave_total(H[i + MAXD * j]); w.H[i + MAXD * j] = h; w.H[j + MAXD * i] = h; }
+            }
+        }
+        return cost;
+    };
+    const int iter = singles_iterate<MAXD, true>(kind, dim, nd, ns, opt, vcur, w, evaluate);
+    if (lane == 0) { SGL_FOR_ST(q) vars[off + q] = vcur[q]; iters_out[t] = iter; }
+}
+#undef SGL_FOR_ST
 
 // ================================================================================================
 // host-side enqueue
@@ -554,12 +662,22 @@ int enqueue_iters_to_double(nlls_ctx* c, const int64_t* d_it, const int64_t* d_p
     if (n > 0) hipLaunchKernelGGL(iters_to_double_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_it, d_pos, n, d_out);
     return hipGetLastError() == hipSuccess ? NLLS_OK : NLLS_ERR_HIP;
 }
-int enqueue_optimize_singles(nlls_ctx* c, int64_t nsel, const int64_t* d_selvar, const int64_t* d_cptr, const int32_t* d_cgroup, const uint32_t* d_cidx,
+// The listed variables come in three runs: [0, nthread) one per thread, then nwave6 of at most 6 dof and nwave12 of up to SGL_WAVE_MAXD dof, one per wavefront.  The
+// variables of one call are independent, so the launches commute.
+int enqueue_optimize_singles(nlls_ctx* c, int64_t nthread, int64_t nwave6, int64_t nwave12, const int64_t* d_selvar, const int64_t* d_cptr, const int32_t* d_cgroup, const uint32_t* d_cidx,
                              const int32_t* d_cslot, const void* d_groups, int iterator, int maxiters, int maxfails, double reldcost, double absdcost, double dstep, int64_t* d_iters) {
-    if (nsel <= 0) return NLLS_OK;
     SinglesOpt o{maxiters, maxfails, reldcost, absdcost, dstep, iterator};
-    hipLaunchKernelGGL(singles_lm_kernel, dim3((unsigned)((nsel + 63) / 64)), dim3(64), 0, c->stream, (const SinglesGroup*)d_groups, d_selvar, nsel, d_cptr, d_cgroup, d_cidx, d_cslot,
-                       c->d_var_kind.p, c->d_var_dim.p, c->d_var_off.p, o, vars_ptr(c, NLLS_VARS_CURRENT), d_iters);
+    if (nthread > 0)
+        hipLaunchKernelGGL(singles_lm_kernel, dim3((unsigned)((nthread + 63) / 64)), dim3(64), 0, c->stream, (const SinglesGroup*)d_groups, d_selvar, nthread, d_cptr, d_cgroup, d_cidx, d_cslot,
+                           c->d_var_kind.p, c->d_var_dim.p, c->d_var_off.p, o, vars_ptr(c, NLLS_VARS_CURRENT), d_iters);
+    int64_t first = nthread;                                   // (cptr holds absolute entry numbers: a run starts at its own slice of the three per-variable arrays)
+    if (nwave6 > 0)
+        hipLaunchKernelGGL(singles_wave_kernel<SGL_MAXD>, dim3((unsigned)nwave6), dim3(64), 0, c->stream, (const SinglesGroup*)d_groups, d_selvar + first, d_cptr + first, d_cgroup, d_cidx, d_cslot,
+                           c->d_var_kind.p, c->d_var_dim.p, c->d_var_off.p, o, vars_ptr(c, NLLS_VARS_CURRENT), d_iters + first);
+    first += nwave6;
+    if (nwave12 > 0)
+        hipLaunchKernelGGL(singles_wave_kernel<SGL_WAVE_MAXD>, dim3((unsigned)nwave12), dim3(64), 0, c->stream, (const SinglesGroup*)d_groups, d_selvar + first, d_cptr + first, d_cgroup, d_cidx, d_cslot,
+                           c->d_var_kind.p, c->d_var_dim.p, c->d_var_off.p, o, vars_ptr(c, NLLS_VARS_CURRENT), d_iters + first);
     HIPCHK(hipGetLastError());
     return NLLS_OK;
 }

@@ -278,6 +278,8 @@ struct nlls_ctx {
     nlls::DevBuf<double> mf_q; int mf_rows = 0;   // the back-substitution launch's rows of partials (nlls::StepState::mf)
     nlls::DevBuf<nlls::MfDesc> d_mf_desc; int64_t mf_nbig = 0; size_t mf_lds = 0; uint32_t mf_ecap = 0, mf_wsz = 0;    // per-supernode partials of the step's quadratic form; dynamic LDS of the two launches
     int64_t mf_trials = 0, mf_reduced_sweeps = 0, full_sweeps = 0;   // diagnostics (nlls_get_solve_stats [23..25])
+    int64_t singles_wave_min = 64;           // nlls_optimize_singles: cost blocks from which a variable of at most 6 dof gets a wavefront instead of a thread (NLLS_SINGLES_WAVE_MIN)
+    int64_t singles_wave = 0, singles_thread = 0;   // variables of the last nlls_optimize_singles call per kernel (nlls_get_solve_stats [27], [28])
     std::vector<int64_t> h_erow; std::vector<int64_t> h_eptr; std::vector<int64_t> h_enbr_block; std::vector<nlls::ElimDesc> h_elim_desc; std::vector<uint32_t> h_fast_voff;   // host copies kept between build_schur and build_mf
 
     // ---- sharding ------------------------------------------------------------------------------------

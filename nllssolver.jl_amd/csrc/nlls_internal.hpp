@@ -50,8 +50,9 @@ int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost = true, int which = NLLS_
 int enqueue_retract(nlls_ctx* c, int to, int from);
 int enqueue_step_stats(nlls_ctx* c);          // scalars[1] = max|x|, scalars[2] = x'x
 int enqueue_max_abs_diag(nlls_ctx* c);        // scalars[3]
-// optimizesingles! (nlls_sweep.hip): all arrays on the device; d_groups = singles_group_size() bytes per cost group
-int enqueue_optimize_singles(nlls_ctx* c, int64_t nsel, const int64_t* d_selvar, const int64_t* d_cptr, const int32_t* d_cgroup, const uint32_t* d_cidx,
+// optimizesingles! (nlls_cost.hip): all arrays on the device; d_groups = singles_group_size() bytes per cost group.  The variables in three runs: one per thread, then
+// one per wavefront of at most 6 dof and of at most NLLS_SINGLES_MAX_DOF
+int enqueue_optimize_singles(nlls_ctx* c, int64_t nthread, int64_t nwave6, int64_t nwave12, const int64_t* d_selvar, const int64_t* d_cptr, const int32_t* d_cgroup, const uint32_t* d_cidx,
                              const int32_t* d_cslot, const void* d_groups, int iterator, int maxiters, int maxfails, double reldcost, double absdcost, double dstep, int64_t* d_iters);
 int enqueue_copy_var_storage(nlls_ctx* c, const int64_t* d_sel, int64_t nsel, const double* src, double* dst);      // the listed variables' storage, src -> dst (same layout)
 int enqueue_iters_to_double(nlls_ctx* c, const int64_t* d_it, const int64_t* d_pos, int64_t n, double* d_out);

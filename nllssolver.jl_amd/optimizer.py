@@ -249,12 +249,18 @@ def optimize(problem, options=None, unfixed=None, callback=nullcallback, flags=0
     return NLLSResult(data)
 
 
+SINGLES_MAX_DOF = 12          # NLLS_SINGLES_MAX_DOF (include/nlls_amd.h)
+last_singles_stats = dict(singles_wave=0, singles_thread=0)
+
+
 def optimizesingles(problem, options=None, indices=None, kind=None, dim=None, device=0):
     """optimizesingles!(problem, options, indices | type)   src/optimize.jl:60-76,183-205: every listed variable is
     optimised on its own (all others fixed) against the cost blocks that depend on it.  `indices` 1-based, or select by
-    variable kind (and dimension), like the reference's `type` argument.  Any of the four iterators; one GPU thread per variable.
-    Listed variables that share a cost block are relaxed one after the other, as the reference does: in launches of independent sets
-    (NLLSProblem.singles_levels).  Returns the iterations each variable took, in the order of `indices`."""
+    variable kind (and dimension), like the reference's `type` argument.  Any of the four iterators.  On the device a variable of more than 6
+    degrees of freedom, or of at least 64 cost blocks (a camera), is relaxed by one wavefront whose lanes deal its blocks, every other one (a
+    point) by one thread (nlls_optimize_singles).  Listed variables that share a cost block are relaxed one after the other, as the reference
+    does: in launches of independent sets (NLLSProblem.singles_levels).  Returns the iterations each variable took, in the order of `indices`.
+    `last_singles_stats` (this module) keeps how many variables the last device call relaxed per wavefront and per thread."""
     options = options or NLLSOptions()
     if indices is None:
         sel = problem.var_kind == kind
@@ -269,7 +275,7 @@ def optimizesingles(problem, options=None, indices=None, kind=None, dim=None, de
     order = np.argsort(dof, kind="stable")
     ordered = indices[order]
     iters = np.zeros(indices.size, np.int64)
-    # What the one-thread-per-variable kernel takes: at most 6 degrees of freedom, fixed-size blocks, not the adaptive kernel's variable.  Anything else -- a
+    # What the per-variable kernels take: at most 12 degrees of freedom (NLLS_SINGLES_MAX_DOF), fixed-size blocks, not the adaptive kernel's variable.  Anything else -- a
     # DynamicVector of run-time length, the kernel variable -- is relaxed the way the reference relaxes EVERY listed variable (src/optimize.jl:183-205): the
     # sub-problem of the cost blocks that depend on it, only that variable free, through the ordinary device path (a univariate dense system).  The listed
     # order is kept: runs of kernel-sized variables go in launches of independent sets, a wide variable in between is a sub-problem of its own.
@@ -278,7 +284,7 @@ def optimizesingles(problem, options=None, indices=None, kind=None, dim=None, de
     # (the kernel variables of the adaptive groups, gathered ONCE: a scan of every adaptive group per listed variable was O(listed x blocks) -- 37 s of host time on ba_so3_500x50k)
     kernelvars = np.unique(np.concatenate([gl[gi].arrays()[0][:, 0] for gi in adaptive_first])) if adaptive_first else np.zeros(0, np.int64)
     if ordered.size:
-        is_wide = (dof[order] > 6) | (vkind[ordered - 1] == K.VAR_DYNAMIC) | np.isin(ordered, kernelvars)
+        is_wide = (dof[order] > SINGLES_MAX_DOF) | (vkind[ordered - 1] == K.VAR_DYNAMIC) | np.isin(ordered, kernelvars)
     else:
         is_wide = np.zeros(0, bool)
     ls = makesymmvls(problem, np.ones(problem.nvariables, bool), 0, device)
@@ -309,6 +315,7 @@ def optimizesingles(problem, options=None, indices=None, kind=None, dim=None, de
                 it = ls.ctx.optimize_singles(run[pick], cptr, cgroup, cindex, cslot, options.maxiters, options.maxfails,
                                              options.reldcost, options.absdcost, options.dstep, iterator=int(options.iterator))
                 iters[order[q + pick]] = it
+                st = ls.ctx.solve_stats(); last_singles_stats.update(singles_wave=st["singles_wave"], singles_thread=st["singles_thread"])
             q = r
         problem.variables[:] = ls.variables(VARS_CURRENT)
     finally:
