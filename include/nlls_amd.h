@@ -295,6 +295,29 @@ int  nlls_copy_variables(nlls_ctx* ctx, int32_t dst, int32_t src);/* deepcopy, s
 int  nlls_sweep_gradhess(nlls_ctx* ctx, double* cost_out);
 /* replaces: cost(vars, costs)  src/cost.jl:10-13, src/residual.jl:49-55 */
 int  nlls_sweep_cost(nlls_ctx* ctx, int32_t which, double* cost_out);
+/* replaces: computeresidual (src/NLLSsolver.jl:16), cost(residual, vars) before the kernel (src/residual.jl:52), robustify and the rho' of
+ * robustifydcost (src/robust.jl), per cost block.  For the ncost blocks of cost group `group` (0-based index of the nlls_cost_group at upload), IN THE
+ * CALLER'S UPLOAD ORDER, at variable set `which`:
+ *   r_out[i * nres .. ]  the residual (nres = nlls_res_nres of the kind; dynamic kinds: the group's run-time n, 1 for NLLS_RES_DYN_LINEAR),
+ *   sqerr_out[i]         r'r,
+ *   rho_out[i]           robustify(kernel, r'r): 0.5 * sum(rho_out) is the group's share of nlls_sweep_cost,
+ *   weight_out[i]        rho' at r'r, the IRLS weight (1 without a robust kernel).
+ * Any pointer may be NULL; all NULL is NLLS_ERR_INVALID_ARG.  Adaptive kinds take their kernel from slot 0 of each block.  Blocks whose variables are
+ * all fixed are evaluated like the others.  The non-squared cost kinds (NLLS_COST_LINEAR3, NLLS_COST_DYN_LINEAR) have no residual: NLLS_ERR_UNSUPPORTED.
+ * Needs an upload, no sweep; reads only (no validity state of the context changes: a call between a sweep and a trial leaves the trial as it was).
+ * Under nlls_set_shard with nranks > 1 (not replicas) a rank holds only its own blocks: NLLS_ERR_UNSUPPORTED. */
+int  nlls_eval_blocks(nlls_ctx* ctx, int32_t which, int32_t group, double* r_out, double* sqerr_out, double* rho_out, double* weight_out);
+/* replaces: optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)  src/robustadaptive.jl:48-73 -- the adaptive kernel's parameters by
+ * Expectation-Maximization between two iterations (the EM callback of test/adaptivecost.jl:15-25), on the device.  kernel_var: 1-based index of a
+ * NLLS_VAR_CONTAMINATED_GAUSSIAN variable.  squarederrors = r'r, at variable set `which`, of every block of every group of an adaptive kind whose slot 0
+ * is that variable (in group, then upload order; none: NLLS_ERR_INVALID_ARG).  The blocks are evaluated once; then up to `maxiters` passes, enqueued
+ * without a host round trip, each a fixed-order sum (no atomics: the result is bit-identical run to run) and a finishing workgroup that forms the new
+ * parameters, orders them like the constructor (src/robustadaptive.jl:12-19: narrowest Gaussian first) and stops the passes behind it once
+ * isapprox(old, new; rtol = 1e-6) holds.  The kernel starts from its storage in set `which`; the result is written INTO THAT SET on the device and to
+ * storage_out (1/sigma1, 1/sigma2, w); iters_out = passes made (both may be NULL).  maxiters == 0 leaves the storage untouched.  Writing the set is
+ * the same state transition as nlls_set_variables(which): see nlls_sweep_gradhess for what a trial behind it is linearised at.
+ * Under nlls_set_shard with nranks > 1 (not replicas): NLLS_ERR_UNSUPPORTED. */
+int  nlls_adaptive_em(nlls_ctx* ctx, int32_t which, int64_t kernel_var, int32_t maxiters, double storage_out[3], int32_t* iters_out);
 
 /* ---- linear system access ---------------------------------------------------------------------
  * replaces: gethessgrad (src/linearsystem.jl:180-190), initlambda (src/iterators.jl:131-137). */

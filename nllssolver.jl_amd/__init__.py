@@ -17,11 +17,11 @@ __all__ = ["kinds", "NLLSProblem", "NoRobust", "HuberKernel", "Huber2oKernel", "
 def __getattr__(name):
     # lazily expose the device-backed API so that host-only use (tests -m "not gpu") needs no .so
     import importlib
-    if name in ("optimize", "optimizesingles", "NLLSOptions", "NLLSResult", "cost", "NLLSIterator", "newton", "levenbergmarquardt", "dogleg",
+    if name in ("optimize", "optimizesingles", "NLLSOptions", "NLLSResult", "cost", "residuals", "squarederrors", "NLLSIterator", "newton", "levenbergmarquardt", "dogleg",
                 "gradientdescent"):
         return getattr(importlib.import_module(__name__ + ".optimizer"), name)
     if name in ("MultiVariateLSgpu", "makesymmvls"):
         return getattr(importlib.import_module(__name__ + ".linearsystem"), name)
-    if name in ("nullcallback", "printoutcallback", "storecostscallback", "CostTrajectory"):
+    if name in ("nullcallback", "printoutcallback", "storecostscallback", "CostTrajectory", "emcallback"):
         return getattr(importlib.import_module(__name__ + ".callbacks"), name)
     raise AttributeError(name)

@@ -31,7 +31,8 @@ nlls_get_grad nlls_get_bsm_data nlls_max_abs_diag nlls_grad_sqnorm nlls_grad_qua
 nlls_get_step nlls_step_maxabs nlls_step_norm nlls_quadform nlls_retract nlls_sweep_gradhess_local
 nlls_sweep_gradhess_finish nlls_sweep_cost_local nlls_sweep_cost_finish nlls_solve_local nlls_solve_finish
 nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_owned nlls_trial_local nlls_solve_finish_async nlls_lm_trial nlls_optimize_singles nlls_time_sweep_gradhess nlls_time_sweep_accumulate nlls_time_sweep_cost nlls_time_solve nlls_time_reduced_solve nlls_profile_sweep nlls_profile_sweep_dispatch nlls_solve_finish_replicated nlls_get_variables_owned nlls_lm_iterations
-nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times""".split()
+nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
+nlls_eval_blocks nlls_adaptive_em""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -124,6 +125,7 @@ def lib():
         L.nlls_set_allreduce.argtypes = [vp, vp, vp]; L.nlls_comm_unique_id.argtypes = [vp]; L.nlls_comm_init_rccl.argtypes = [vp, vp]
         L.nlls_get_memory_info.argtypes = [vp, vp, i32]; L.nlls_flush_cache.argtypes = [vp, i64]; L.nlls_check_analytic.argtypes = [vp, vp, i32]
         L.nlls_set_option.argtypes = [vp, i32, i64]; L.nlls_get_time_buckets.argtypes = [vp, vp, i32]; L.nlls_get_phase_times.argtypes = [vp, vp, i32]
+        L.nlls_eval_blocks.argtypes = [vp, i32, i32, vp, vp, vp, vp]; L.nlls_adaptive_em.argtypes = [vp, i32, i64, i32, vp, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -147,6 +149,7 @@ class Context:
                             if rc == ERR_NO_DEVICE else "nlls_ctx_create failed")
         self.info = None
         self._keep = None
+        self._groups = []
 
     def close(self):
         if getattr(self, "h", None):
@@ -185,7 +188,13 @@ class Context:
             for k in range(4):
                 arr[i].robust_params[k] = float(rp[k])
             arr[i].ncost = vi.shape[0]; arr[i].varind = vi.ctypes.data; arr[i].data = da.ctypes.data
+        self._groups = []
         self._chk(self.L.nlls_upload_structure(self.h, len(vk), _p(vk), _p(vd), _p(bi), len(groups), arr, flags))
+        for i, g in enumerate(groups):             # (ncost, residuals per block) of every group, for eval_blocks; a dynamic kind's nres is its variable's run-time length
+            nres = self.L.nlls_res_nres(int(g["res_kind"]))
+            if nres < 0 and arr[i].ncost:
+                nres = int(vd[int(np.asarray(g["varind"]).reshape(arr[i].ncost, -1)[0, 0]) - 1])
+            self._groups.append((int(arr[i].ncost), max(int(nres), 1)))
         self.info = Info()
         self._chk(self.L.nlls_get_info(self.h, C.byref(self.info)))
         return self.info
@@ -225,6 +234,24 @@ class Context:
 
     def sweep_cost(self, which=VARS_CURRENT):
         return self._scalar(self.L.nlls_sweep_cost, which)
+
+    def eval_blocks(self, group, which=VARS_CURRENT, want=("r", "sqerr", "rho", "weight")):
+        """nlls_eval_blocks: the blocks of cost group `group` (0-based, upload order) at variable set `which` -- a dict with the entries of `want`:
+        "r" (ncost x nres) computeresidual, "sqerr" r'r, "rho" robustify(kernel, r'r), "weight" rho' (the IRLS weight)."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        assert want and set(want) <= {"r", "sqerr", "rho", "weight"}
+        g = self._groups[group] if 0 <= group < len(self._groups) else None
+        n, nres = (g if g is not None else (0, 1))
+        out = {k: np.zeros((n, nres) if k == "r" else n) for k in want}
+        self._chk(self.L.nlls_eval_blocks(self.h, int(which), int(group), *(_p(out.get(k)) if k in out else None for k in ("r", "sqerr", "rho", "weight"))))
+        return out
+
+    def adaptive_em(self, kernel_var=1, which=VARS_NEXT, maxiters=10):
+        """nlls_adaptive_em: the ContaminatedGaussian variable `kernel_var` (1-based) of set `which` re-estimated by Expectation-Maximization on the device, written
+        back into that set.  Returns (storage (1/sigma1, 1/sigma2, w), passes made)."""
+        st = np.zeros(3); it = C.c_int32(0)
+        self._chk(self.L.nlls_adaptive_em(self.h, int(which), int(kernel_var), int(maxiters), _p(st), C.byref(it)))
+        return st, int(it.value)
 
     def get_grad(self):
         out = np.zeros(self.info.ndof); self._chk(self.L.nlls_get_grad(self.h, _p(out))); return out

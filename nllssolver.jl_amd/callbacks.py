@@ -47,3 +47,22 @@ def storecostscallback(store):
         store.append(cost)
         return cost, 0
     return cb
+
+
+def emcallback(kernel_var=1, maxiters=10):
+    """The EM callback of test/adaptivecost.jl:15-25 for the adaptive ContaminatedGaussian kernel: between two iterations the kernel variable `kernel_var` (1-based) of
+    problem.varnext is re-estimated by Expectation-Maximization on the squared errors of its blocks (optimize(kernel, squarederrors, maxiters),
+    src/robustadaptive.jl:48-73), and the cost of what that leaves is returned.  Everything runs on the device (nlls_adaptive_em, nlls_sweep_cost): the residuals never
+    come to the host, so it serves any adaptive residual kind.  Use it with the kernel variable fixed for the optimiser, as the reference's test does."""
+    from ._capi import VARS_NEXT
+
+    def cb(cost, problem, data, *unused):
+        ls = data.linsystem
+        storage, _ = ls.adaptive_em(kernel_var, VARS_NEXT, maxiters)
+        o = int(problem.var_offsets[kernel_var - 1])
+        if problem.varnext is not None:
+            problem.varnext[o:o + 3] = storage        # (the outer loop mirrors problem.varnext around the callback: what it uploads again is what the device holds)
+        newcost = ls.cost(VARS_NEXT)
+        data.costcomputations += 1
+        return newcost, 0
+    return cb

@@ -277,6 +277,46 @@ int nlls_sweep_cost(nlls_ctx* ctx, int32_t which, double* cost_out) { NLLS_API_B
     NLLS_API_END(ctx)
 }
 
+// computeresidual / r'r / robustify / rho' of every block of one cost group, in upload order (nlls_eval.hip).  Reads only: no event of nlls_state.hpp.
+int nlls_eval_blocks(nlls_ctx* ctx, int32_t which, int32_t group, double* r_out, double* sqerr_out, double* rho_out, double* weight_out) { NLLS_API_BEGIN
+    NEED_READY(); if (!valid_set(which)) return NLLS_ERR_INVALID_ARG;
+    if (!r_out && !sqerr_out && !rho_out && !weight_out) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_eval_blocks: no output asked for");
+    if (ctx->nranks > 1) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_eval_blocks under nlls_set_shard: a rank holds only its own cost blocks");
+    if (group < 0 || group >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_eval_blocks: bad cost group");
+    const Group& G = ctx->groups[(size_t)group];
+    if (G.res_kind == NLLS_COST_LINEAR3 || G.res_kind == NLLS_COST_DYN_LINEAR) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_eval_blocks: a non-squared cost kind has no residual");
+    if (G.ncost == 0) return NLLS_OK;
+    const size_t n = (size_t)G.ncost, nr = (size_t)eval_nres(G), need = n * (nr + 3);
+    if (ctx->eval_out.n < need) HIPCHK(ctx->eval_out.alloc(need));
+    double* d_r = ctx->eval_out.p; double* d_sq = d_r + n * nr; double* d_rho = d_sq + n; double* d_w = d_rho + n;
+    TRY(enqueue_eval_blocks(ctx, G, which, r_out ? d_r : nullptr, sqerr_out ? d_sq : nullptr, rho_out ? d_rho : nullptr, weight_out ? d_w : nullptr));
+    if (r_out) HIPCHK(hipMemcpyAsync(r_out, d_r, sizeof(double) * n * nr, hipMemcpyDeviceToHost, ctx->stream));
+    if (sqerr_out) HIPCHK(hipMemcpyAsync(sqerr_out, d_sq, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (rho_out) HIPCHK(hipMemcpyAsync(rho_out, d_rho, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (weight_out) HIPCHK(hipMemcpyAsync(weight_out, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+// optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)  src/robustadaptive.jl:48-73 on the device (nlls_eval.hip): one synchronisation
+int nlls_adaptive_em(nlls_ctx* ctx, int32_t which, int64_t kernel_var, int32_t maxiters, double storage_out[3], int32_t* iters_out) { NLLS_API_BEGIN
+    NEED_READY(); if (!valid_set(which) || maxiters < 0) return NLLS_ERR_INVALID_ARG;
+    if (ctx->nranks > 1) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_adaptive_em under nlls_set_shard: a rank holds only its own cost blocks");
+    const int64_t v = kernel_var - 1;
+    if (v < 0 || v >= ctx->info.nvar || ctx->var_kind[(size_t)v] != NLLS_VAR_CONTAMINATED_GAUSSIAN) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_adaptive_em: kernel_var is not a NLLS_VAR_CONTAMINATED_GAUSSIAN variable");
+    if (!std::binary_search(ctx->em_kernel_vars.begin(), ctx->em_kernel_vars.end(), v)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_adaptive_em: no block of an adaptive kind has this variable as its kernel");
+    // writing the set: the transition nlls_set_variables(which) makes (what it enqueues goes ahead of the passes, in stream order)
+    if (maxiters > 0) { TRY(vars_written(ctx, which)); if (which == NLLS_VARS_CURRENT) { new_starting_point(ctx); ctx->tb_prev_end = 0.0; } }
+    TRY(enqueue_adaptive_em(ctx, which, ctx->var_off[(size_t)v], maxiters));
+    double st[10];
+    HIPCHK(hipMemcpyAsync(st, ctx->em_state.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (storage_out) { storage_out[0] = st[0]; storage_out[1] = st[1]; storage_out[2] = st[2]; }
+    if (iters_out) *iters_out = (int32_t)st[8];
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+
 int nlls_get_grad(nlls_ctx* ctx, double* b_out) { NLLS_API_BEGIN
     NEED_GRAD(); if (!b_out) return NLLS_ERR_INVALID_ARG;
     HIPCHK(hipMemcpyAsync(b_out, ctx->b.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));

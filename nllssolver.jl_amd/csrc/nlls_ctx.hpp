@@ -231,6 +231,7 @@ struct nlls_ctx {
     std::vector<int64_t> it_colptr, it_rowval, it_nzval;   // BSM indicestransposed, 0-based
     std::vector<int64_t> diag_off;           // per block: offset of the diagonal block (sparse) / dense index
     std::vector<nlls::Group> groups;
+    std::vector<int64_t> em_kernel_vars;     // the variables (0-based, sorted) that are slot 0 of a block of an adaptive group: what nlls_adaptive_em can fit
 
     // ---- device state -----------------------------------------------------------------------------
     nlls::DevBuf<double> vars[3];            // problem.variables / varnext / varbest (src/problem.jl:9-12)
@@ -361,4 +362,7 @@ struct nlls_ctx {
     nlls::DevBuf<char> arena, arena_pre;
     int64_t hot_bytes = 0;                   // bytes of the hot set (what an LM iteration reads or writes): nlls_get_memory_info
     nlls::DevBuf<char> flushbuf;             // nlls_flush_cache: foreign traffic for cold-cache timings
+    // nlls_eval_blocks / nlls_adaptive_em (nlls_eval.hip): scratch of their own, sized at first use and kept -- they read the problem and touch nothing a sweep or a trial
+    // has left in partials / scalars.  eval_out: one group's [r | r'r | rho | rho']; em_err: r'r of the adaptive groups' blocks, em_part: per-workgroup partial sums
+    nlls::DevBuf<double> eval_out, em_err, em_part, em_state;
 };

@@ -56,6 +56,10 @@ int enqueue_optimize_singles(nlls_ctx* c, int64_t nthread, int64_t nwave6, int64
                              const int32_t* d_cslot, const void* d_groups, int iterator, int maxiters, int maxfails, double reldcost, double absdcost, double dstep, int64_t* d_iters);
 int enqueue_copy_var_storage(nlls_ctx* c, const int64_t* d_sel, int64_t nsel, const double* src, double* dst);      // the listed variables' storage, src -> dst (same layout)
 int enqueue_iters_to_double(nlls_ctx* c, const int64_t* d_it, const int64_t* d_pos, int64_t n, double* d_out);
+// per-block values and the adaptive kernel's EM step (nlls_eval.hip): device output pointers (null: not wanted); the EM call's state is left in c->em_state
+int eval_nres(const Group& G);                 // residuals per block of the group (dynamic kinds: the run-time n)
+int enqueue_eval_blocks(nlls_ctx* c, const Group& G, int which, double* d_r, double* d_sq, double* d_rho, double* d_w);
+int enqueue_adaptive_em(nlls_ctx* c, int which, uint32_t kvoff, int maxiters);
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);
 int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot /* scalars[out], scalars[out+1] = v'Hv, b'v */);

@@ -379,6 +379,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     c->owner_of_block = owner_of_block;
     // ---- per-group lists ---------------------------------------------------------------------------------
     c->groups.resize(ngroups);
+    c->em_kernel_vars.clear();
     std::vector<int32_t> row_nlists(nb, 0);         // how many entry lists touch a row
     std::vector<std::vector<HostList>> hl(ngroups);
     int64_t npartials = 0;
@@ -401,6 +402,8 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
           if (nranks > 1 && !(flags & NLLS_FLAG_PRESHARDED)) { G.local_of.assign((size_t)in.ncost, -1); int32_t q = 0; for (int64_t k = 0; k < in.ncost; ++k) if (mine[g][k]) G.local_of[(size_t)k] = q++; }
           HIPCHK(G.data.upload(hd)); HIPCHK(G.voff.upload(hv)); }
         G.nfixedcost = (int64_t)fixedcost.size(); HIPCHK(G.fixedcost.upload(fixedcost));
+        if (d.adaptive) { for (int64_t k = 0; k < in.ncost; ++k) { const int64_t v = in.varind[k * d.ndeps] - 1; if (c->em_kernel_vars.empty() || c->em_kernel_vars.back() != v) c->em_kernel_vars.push_back(v); }
+            std::sort(c->em_kernel_vars.begin(), c->em_kernel_vars.end()); c->em_kernel_vars.erase(std::unique(c->em_kernel_vars.begin(), c->em_kernel_vars.end()), c->em_kernel_vars.end()); }
         npartials += (G.nfixedcost + 255) / 256;
         hl[g].resize(d.ndeps);
         if (!sparse || is_dyn_kind(in.res_kind)) continue;      // (dynamic-size groups take no entry lists: see the DenseList built for them below)

@@ -139,6 +139,30 @@ function gpucost(ls::MultiVariateLSgpu, vars::Vector)                           
     setvariables!(ls, vars, 1); c = Ref(0.0)
     check(ls.ctx, ccall((:nlls_sweep_cost, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), ls.ctx, 1, c)); return c[]
 end
+# computeresidual / r'r / robustify / rho' of every block of cost group `group` (0-based, the order of the nlls_cost_group array at upload), rows in the order of
+# problem.costs.data[T], at device variable set `which` (src/NLLSsolver.jl:16, src/residual.jl:52, src/robust.jl).  nres: residuals per block of the group.
+function blockvalues(ls::MultiVariateLSgpu, which::Integer, group::Integer, ncost::Integer, nres::Integer)
+    r = zeros(nres, ncost); sqerr = zeros(ncost); rho = zeros(ncost); weight = zeros(ncost)
+    check(ls.ctx, ccall((:nlls_eval_blocks, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, r, sqerr, rho, weight))
+    return r, sqerr, rho, weight
+end
+# optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
+# re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
+function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)
+    storage = zeros(3); iters = Ref(Int32(0))
+    check(ls.ctx, ccall((:nlls_adaptive_em, lib), Cint, (Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Float64}, Ptr{Int32}), ls.ctx, which, kernelvar, maxiters, storage, iters))
+    return storage
+end
+# The EM callback of test/adaptivecost.jl:15-25 with the residuals left on the device: EM into VARS_NEXT (= 1), problem.varnext's kernel rebuilt from what comes back, the
+# cost of what that leaves.  For the loop below, which keeps the variables resident (problem.varnext is fetched before a user callback runs).
+gpuemcallback(kernelvar=1, maxiters=10) = function (cost, problem, data, trailingargs...)
+    ls = data.linsystem
+    storage = adaptiveem!(ls, 1, kernelvar, maxiters)
+    problem.varnext[kernelvar] = NLLSsolver.ContaminatedGaussian(1 / storage[1], 1 / storage[2], storage[3])
+    c = Ref(0.0); check(ls.ctx, ccall((:nlls_sweep_cost, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), ls.ctx, 1, c))
+    data.costcomputations += 1
+    return c[], 0
+end
 # The reference's OTHER iterators (Newton, dogleg, gradient descent: src/iterators.jl:15-27,47-115,187-208) evaluate their trial points with
 # cost(problem.varnext, problem.costs) (src/iterators.jl:24,100,191,203), which does not see the linear system.  NLLSInternal is parametric in the
 # linear-system type (src/structs.jl:81-104), so -- exactly as for Levenberg-Marquardt below -- iterate! methods on NLLSInternal{MultiVariateLSgpu}

@@ -37,6 +37,14 @@ class MultiVariateLSgpu:
         """cost(vars, costs)   src/cost.jl:10-13"""
         return self.ctx.sweep_cost(which)
 
+    def eval_blocks(self, group, which=VARS_CURRENT, want=("r", "sqerr", "rho", "weight")):
+        """computeresidual / r'r / robustify / rho' of every block of a cost group, in the problem's order   src/NLLSsolver.jl:16, src/residual.jl:52"""
+        return self.ctx.eval_blocks(group, which, want)
+
+    def adaptive_em(self, kernel_var=1, which=VARS_NEXT, maxiters=10):
+        """optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)   src/robustadaptive.jl:48-73"""
+        return self.ctx.adaptive_em(kernel_var, which, maxiters)
+
     def uniformscaling(self, k):
         """uniformscaling!(hessian, k)   src/iterators.jl:149,162"""
         self.ctx.damp(k)

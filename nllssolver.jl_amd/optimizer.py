@@ -330,3 +330,24 @@ def cost(problem, device=0):
         return ls.cost(VARS_CURRENT)
     finally:
         ls.close()
+
+
+def _blockvalues(problem, group, what, device):
+    ls = makesymmvls(problem, np.ones(problem.nvariables, bool), 0, device)
+    try:
+        if group is not None:
+            return ls.eval_blocks(int(group), VARS_CURRENT, what)[what]
+        return [ls.eval_blocks(g, VARS_CURRENT, what)[what] for g in range(len(problem.costs))]
+    finally:
+        ls.close()
+
+
+def residuals(problem, group=None, device=0):
+    """computeresidual of every cost block at problem.variables (src/NLLSsolver.jl:16): an (ncost x nres) array for cost group `group` (0-based, in the order of
+    problem.costs; rows in the order the blocks were added), or with group=None the list of them over all groups."""
+    return _blockvalues(problem, group, "r", device)
+
+
+def squarederrors(problem, group=None, device=0):
+    """r'r of every cost block at problem.variables -- cost(residual, vars) before the robust kernel, src/residual.jl:52; shaped like residuals()."""
+    return _blockvalues(problem, group, "sqerr", device)
