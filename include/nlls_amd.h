@@ -319,6 +319,30 @@ int  nlls_eval_blocks(nlls_ctx* ctx, int32_t which, int32_t group, double* r_out
  * Under nlls_set_shard with nranks > 1 (not replicas): NLLS_ERR_UNSUPPORTED. */
 int  nlls_adaptive_em(nlls_ctx* ctx, int32_t which, int64_t kernel_var, int32_t maxiters, double storage_out[3], int32_t* iters_out);
 
+/* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
+ * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
+ *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.
+ * nlls_upload_structure is the symbolic phase (entry lists, tiles, the eliminated set, supernodes, orderings); these two change what it was given
+ * WITHOUT redoing it: which variables a block depends on, which are fixed, the kinds and ncost stay as uploaded.
+ *
+ * nlls_set_cost_data: new payload records for n blocks of cost group `group` (0-based index of the nlls_cost_group at upload, as in nlls_eval_blocks).
+ *   data[i * ndata ..] is the record of block index[i] -- 1-based, in the caller's upload order of that group; index == NULL: of block i + 1, the first
+ *   n blocks (n == ncost: the whole group).  ndata is what the upload used (nlls_res_ndata; dynamic kinds: the count their variable's length gives).
+ *   Every device copy of the record is rewritten (the cost-order arrays, the entry lists, the dense list, the matrix-free trial's list) by one
+ *   host-to-device copy and one launch on the context's stream, behind whatever is enqueued there.  `index` and `data` are read during the call only.
+ *   NLLS_ERR_INVALID_ARG -- nothing enqueued, nothing changed -- for a bad group, n < 0, n > ncost, an index outside 1 .. ncost or listed twice,
+ *   or data == NULL with n > 0.  n == 0: NLLS_OK, nothing changes (the state below included).
+ * nlls_set_robust_params: robust_params of cost group `group` (the meaning of nlls_cost_group::robust_params; [3] is unused as there).  The kind stays,
+ *   NLLS_ROBUST_SCALED included.  The kernels take the parameters by value with every launch: a host-side write.  An adaptive group's kernel is a
+ *   variable, not a parameter: NLLS_ERR_INVALID_ARG.
+ * Both: the linear system is of the old costs -- the state after an upload without a sweep: nlls_lm_trial, nlls_solve, nlls_get_grad, ... return
+ *   NLLS_ERR_NOT_READY until the next nlls_sweep_gradhess; a look-ahead sweep pending behind the last trial is dropped.  nlls_sweep_cost,
+ *   nlls_eval_blocks, nlls_optimize_singles and nlls_adaptive_em need no sweep and see the new costs at once.  The variable sets, the damping the
+ *   caller holds and the counters of nlls_get_solve_stats are untouched.  NLLS_ERR_NOT_READY before a successful upload; under nlls_set_shard with
+ *   nranks > 1: NLLS_ERR_UNSUPPORTED (a rank holds only its own blocks). */
+int  nlls_set_cost_data(nlls_ctx* ctx, int32_t group, int64_t n, const int64_t* index, const double* data);
+int  nlls_set_robust_params(nlls_ctx* ctx, int32_t group, const double params[4]);
+
 /* ---- linear system access ---------------------------------------------------------------------
  * replaces: gethessgrad (src/linearsystem.jl:180-190), initlambda (src/iterators.jl:131-137). */
 int  nlls_get_grad(nlls_ctx* ctx, double* b_out);                 /* linsystem.b            */
@@ -361,7 +385,8 @@ int  nlls_get_time_buckets(nlls_ctx* ctx, int64_t* out, int32_t n);
 #define NLLS_OPT_LOOKAHEAD   2
 #define NLLS_OPT_PHASE_EVENTS 3   /* value != 0: the COLLECTIVE nlls_lm_trial records stream events at its phase boundaries (resets the sums); nlls_get_phase_times reads them */
 /* out[0..4]: milliseconds summed over the trials since NLLS_OPT_PHASE_EVENTS was set -- [0] this rank's assembly of [S | s] (elimination), [1] the all-reduce of [S | s] (wait included),
- * [2] the reduced solve (every rank), [3] back-substitution + retraction, [4] trial tail (statistics, cost sweep, the scalars' gather); [5] gradient sweeps (ms summed), [6] trials, [7] sweeps counted. */
+ * [2] the reduced solve (every rank), [3] back-substitution + retraction, [4] trial tail (statistics, cost sweep, the scalars' gather); [5] gradient sweeps (ms summed), [6] trials, [7] sweeps counted.
+ * [8] milliseconds of the last nlls_set_cost_data's scatter launch alone (an event pair around it, while the option is set; waits for it), [9] the device copies of the payload the last such launch wrote. */
 int  nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n);
 int  nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value);
 int  nlls_set_step(nlls_ctx* ctx, const double* x);               /* host-formed steps (dogleg, GD) */

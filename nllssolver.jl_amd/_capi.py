@@ -32,7 +32,7 @@ nlls_get_step nlls_step_maxabs nlls_step_norm nlls_quadform nlls_retract nlls_sw
 nlls_sweep_gradhess_finish nlls_sweep_cost_local nlls_sweep_cost_finish nlls_solve_local nlls_solve_finish
 nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_owned nlls_trial_local nlls_solve_finish_async nlls_lm_trial nlls_optimize_singles nlls_time_sweep_gradhess nlls_time_sweep_accumulate nlls_time_sweep_cost nlls_time_solve nlls_time_reduced_solve nlls_profile_sweep nlls_profile_sweep_dispatch nlls_solve_finish_replicated nlls_get_variables_owned nlls_lm_iterations
 nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
-nlls_eval_blocks nlls_adaptive_em""".split()
+nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -126,6 +126,7 @@ def lib():
         L.nlls_get_memory_info.argtypes = [vp, vp, i32]; L.nlls_flush_cache.argtypes = [vp, i64]; L.nlls_check_analytic.argtypes = [vp, vp, i32]
         L.nlls_set_option.argtypes = [vp, i32, i64]; L.nlls_get_time_buckets.argtypes = [vp, vp, i32]; L.nlls_get_phase_times.argtypes = [vp, vp, i32]
         L.nlls_eval_blocks.argtypes = [vp, i32, i32, vp, vp, vp, vp]; L.nlls_adaptive_em.argtypes = [vp, i32, i64, i32, vp, vp]
+        L.nlls_set_cost_data.argtypes = [vp, i32, i64, vp, vp]; L.nlls_set_robust_params.argtypes = [vp, i32, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -150,6 +151,7 @@ class Context:
         self.info = None
         self._keep = None
         self._groups = []
+        self._ndata = []
 
     def close(self):
         if getattr(self, "h", None):
@@ -188,7 +190,7 @@ class Context:
             for k in range(4):
                 arr[i].robust_params[k] = float(rp[k])
             arr[i].ncost = vi.shape[0]; arr[i].varind = vi.ctypes.data; arr[i].data = da.ctypes.data
-        self._groups = []
+        self._groups = []; self._ndata = [int(da.size // max(vi.shape[0], 1)) for vi, da in zip(keep[3::2], keep[4::2])]     # doubles of payload per block, per group (set_cost_data)
         self._chk(self.L.nlls_upload_structure(self.h, len(vk), _p(vk), _p(vd), _p(bi), len(groups), arr, flags))
         for i, g in enumerate(groups):             # (ncost, residuals per block) of every group, for eval_blocks; a dynamic kind's nres is its variable's run-time length
             nres = self.L.nlls_res_nres(int(g["res_kind"]))
@@ -252,6 +254,22 @@ class Context:
         st = np.zeros(3); it = C.c_int32(0)
         self._chk(self.L.nlls_adaptive_em(self.h, int(which), int(kernel_var), int(maxiters), _p(st), C.byref(it)))
         return st, int(it.value)
+
+    def set_cost_data(self, group, data, index=None):
+        """nlls_set_cost_data: new payload records for blocks of cost group `group` (0-based) of the uploaded structure -- `data` (n x ndata) for the blocks `index`
+        (1-BASED, the caller's upload order of that group, as everywhere in the ABI; distinct) or, index=None, for the first n blocks (n = ncost: the whole group).
+        No linearisation is held afterwards: sweep_gradhess before the next trial."""
+        da = np.ascontiguousarray(data, np.float64)
+        ix = None if index is None else np.ascontiguousarray(index, np.int64).ravel()
+        nd = self._ndata[group] if 0 <= group < len(self._ndata) else 0
+        n = int(ix.size) if ix is not None else (int(da.size // nd) if nd else (da.shape[0] if da.ndim > 1 else 0))
+        assert not nd or da.size == n * nd, "set_cost_data: data must hold ndata doubles per listed block"      # (an unknown group is the library's to refuse)
+        self._chk(self.L.nlls_set_cost_data(self.h, int(group), n, _p(ix), _p(da)))
+
+    def set_robust_params(self, group, params):
+        """nlls_set_robust_params: the robust kernel's parameters of cost group `group` (0-based; the kind stays) -- a kinds.Robustifier's .params or up to four numbers"""
+        par = np.zeros(4); v = np.asarray(getattr(params, "params", params), np.float64).ravel(); par[:min(v.size, 4)] = v[:4]
+        self._chk(self.L.nlls_set_robust_params(self.h, int(group), _p(par)))
 
     def get_grad(self):
         out = np.zeros(self.info.ndof); self._chk(self.L.nlls_get_grad(self.h, _p(out))); return out
@@ -360,9 +378,10 @@ class Context:
 
     def phase_times(self):
         """nlls_get_phase_times: microseconds per collective trial by phase (stream events; NLLS_OPT_PHASE_EVENTS) and per gradient sweep"""
-        out = np.zeros(8); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 8)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
+        out = np.zeros(10); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 10)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
         return dict(trials=int(out[6]), sweeps=int(out[7]), elimination_us=1e3 * out[0] / nt, allreduce_S_us=1e3 * out[1] / nt, reduced_solve_us=1e3 * out[2] / nt,
-                    backsub_retraction_us=1e3 * out[3] / nt, trial_tail_us=1e3 * out[4] / nt, gradient_sweep_us=1e3 * out[5] / ns)
+                    backsub_retraction_us=1e3 * out[3] / nt, trial_tail_us=1e3 * out[4] / nt, gradient_sweep_us=1e3 * out[5] / ns,
+                    update_scatter_us=1e3 * out[8], update_copies=int(out[9]))
 
     def time_buckets(self):
         """device-timed NLLSResult buckets since the upload: seconds (gradient, cost, solver) and the trials counted"""

@@ -317,6 +317,46 @@ int nlls_adaptive_em(nlls_ctx* ctx, int32_t which, int64_t kernel_var, int32_t m
     NLLS_API_END(ctx)
 }
 
+// The cost blocks' payload and a group's robust parameters replaced on the uploaded structure (nlls_update.hip; the reference's mutable costs, src/optimize.jl:5-17).
+// Everything is checked on the host before anything is enqueued or any state changes.
+int nlls_set_cost_data(nlls_ctx* ctx, int32_t group, int64_t n, const int64_t* index, const double* data) { NLLS_API_BEGIN
+    NEED_READY();
+    if (ctx->shard_nranks > 1) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_set_cost_data under nlls_set_shard: a rank holds only its own cost blocks");
+    if (group < 0 || group >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_cost_data: bad cost group");
+    Group& G = ctx->groups[(size_t)group];
+    if (n < 0 || n > G.ncost) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_cost_data: n outside 0 .. ncost");
+    if (n == 0) return NLLS_OK;
+    if (!data) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_cost_data: data is NULL");
+    std::vector<uint32_t> blocks;                       // the listed blocks, 0-based, as the device takes them
+    if (index) { std::vector<uint8_t> seen((size_t)G.ncost, 0); blocks.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) { const int64_t k = index[i] - 1;
+            if (k < 0 || k >= G.ncost) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_cost_data: index outside 1 .. ncost");
+            if (seen[(size_t)k]) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_cost_data: a block is listed twice");
+            seen[(size_t)k] = 1; blocks[(size_t)i] = (uint32_t)k; } }
+    if (G.ndata <= 0) return NLLS_OK;                   // (a kind without payload: nothing to write, nothing changed)
+    const size_t nd = (size_t)n * (size_t)G.ndata;
+    if (ctx->upd_stage.n < nd) HIPCHK(ctx->upd_stage.alloc(nd));
+    if (index && ctx->upd_index.n < (size_t)n) HIPCHK(ctx->upd_index.alloc((size_t)n));
+    costs_changed(ctx); ctx->tb_prev_end = 0.0;
+    HIPCHK(hipMemcpyAsync(ctx->upd_stage.p, data, sizeof(double) * nd, hipMemcpyHostToDevice, ctx->stream));
+    if (index) HIPCHK(hipMemcpyAsync(ctx->upd_index.p, blocks.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));          // (the caller's buffers are read during the call only; the scatter itself is left enqueued)
+    return enqueue_update_scatter(ctx, G, n, index != nullptr);
+    NLLS_API_END(ctx)
+}
+int nlls_set_robust_params(nlls_ctx* ctx, int32_t group, const double params[4]) { NLLS_API_BEGIN
+    NEED_READY();
+    if (ctx->shard_nranks > 1) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_set_robust_params under nlls_set_shard");
+    if (group < 0 || group >= (int32_t)ctx->groups.size() || !params) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_robust_params: bad cost group or NULL parameters");
+    Group& G = ctx->groups[(size_t)group];
+    if (G.adaptive) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_robust_params: the kernel of an adaptive group is a variable");
+    // Group::rk is the one copy: every launch takes it by value (sweeps, trials, nlls_eval_blocks; nlls_optimize_singles fills its group table per call)
+    G.rk.p0 = params[0]; G.rk.p1 = params[1]; G.rk.p2 = params[2];
+    costs_changed(ctx); ctx->tb_prev_end = 0.0;
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+
 int nlls_get_grad(nlls_ctx* ctx, double* b_out) { NLLS_API_BEGIN
     NEED_GRAD(); if (!b_out) return NLLS_ERR_INVALID_ARG;
     HIPCHK(hipMemcpyAsync(b_out, ctx->b.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
@@ -598,8 +638,10 @@ int nlls_get_time_buckets(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEG
 }
 int nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
     if (!ctx || !out || n < 1) return NLLS_ERR_INVALID_ARG;
-    const double v[8] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps};
-    for (int i = 0; i < n && i < 8; ++i) out[i] = v[i];
+    if (take(ctx->upd_pending) && ctx->phase_ev.size() >= 10) { float ms = 0.f; (void)hipSetDevice(ctx->device);
+        if (hipEventSynchronize(ctx->phase_ev[9]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[8], ctx->phase_ev[9]) == hipSuccess) ctx->upd_ms = ms; else (void)hipGetLastError(); }
+    const double v[10] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies};
+    for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -610,7 +652,7 @@ int nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value) { NLLS_API_BEG
     case NLLS_OPT_LOOKAHEAD:   ctx->spec_on = value != 0; return NLLS_OK;
     case NLLS_OPT_PHASE_EVENTS:
         ctx->phase_on = value != 0; (void)hipSetDevice(ctx->device);
-        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(8); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
+        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(10); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
         if (ctx->phase_on) { for (double& v : ctx->phase_ms) v = 0.0; ctx->phase_trials = ctx->phase_sweeps = 0; }
         return NLLS_OK;
     }

@@ -129,7 +129,15 @@ struct Group {
     // block of [E] -- so that lane l of a wavefront's batch finds its block at obs0 + first member * ncb + l.  Same record form as an entry list (data + one storage offset per slot):
     // the cost sweep of an LM trial reads these arrays too (the loop's working set holds the blocks once)
     DevBuf<double> mf_data; DevBuf<uint32_t> mf_voff;
+    // nlls_set_cost_data (nlls_update.hip): where block k of the caller's group sits in every device copy of its payload other than the cost-order arrays (one rank:
+    // those hold block k at k) -- lists[s].data, dense.data, mf_data -- UPD_ABSENT where the copy skips the block (a fixed variable in that slot, no free variable at all).
+    // POSITIONS, not pointers: compact_hot_set moves the buffers.  Kept on the host by the upload (empty: the copy does not exist, or the upload was sharded); put on the
+    // device, outside the hot arena, by the first update; gone with the group at the next upload.
+    std::vector<uint32_t> pos_list[MAX_SLOTS], pos_dense, pos_mf;
+    DevBuf<uint32_t> d_pos_list[MAX_SLOTS], d_pos_dense, d_pos_mf; bool pos_on_device = false;
 };
+constexpr uint32_t UPD_ABSENT = 0xFFFFFFFFu;
+constexpr int UPD_MAX_COPIES = 1 + MAX_SLOTS + 2;   // cost order, one entry list per slot, the dense list, the elimination order
 
 // ---- Schur / solve structures ---------------------------------------------------------------------
 // one fast-path supernode, in launch order (position in d_fast_groups): everything a kernel needs to start on it comes with ONE
@@ -365,4 +373,9 @@ struct nlls_ctx {
     // nlls_eval_blocks / nlls_adaptive_em (nlls_eval.hip): scratch of their own, sized at first use and kept -- they read the problem and touch nothing a sweep or a trial
     // has left in partials / scalars.  eval_out: one group's [r | r'r | rho | rho']; em_err: r'r of the adaptive groups' blocks, em_part: per-workgroup partial sums
     nlls::DevBuf<double> eval_out, em_err, em_part, em_state;
+    // nlls_set_cost_data (nlls_update.hip): the new records and the 0-based blocks they belong to, as they came from the host -- staging of its own, outside the arena, grown on
+    // demand and kept (a context that never updates allocates none of it).  Under NLLS_OPT_PHASE_EVENTS the scatter launch sits between phase_ev[8] and [9]: upd_pending --
+    // the pair of the last launch has not been read yet (nlls_get_phase_times [8], [9])
+    nlls::DevBuf<double> upd_stage; nlls::DevBuf<uint32_t> upd_index;
+    bool upd_pending = false; double upd_ms = 0.0; int upd_copies = 0;     // upd_copies: device copies the last launch wrote
 };

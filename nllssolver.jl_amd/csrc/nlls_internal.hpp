@@ -60,6 +60,7 @@ int enqueue_iters_to_double(nlls_ctx* c, const int64_t* d_it, const int64_t* d_p
 int eval_nres(const Group& G);                 // residuals per block of the group (dynamic kinds: the run-time n)
 int enqueue_eval_blocks(nlls_ctx* c, const Group& G, int which, double* d_r, double* d_sq, double* d_rho, double* d_w);
 int enqueue_adaptive_em(nlls_ctx* c, int which, uint32_t kvoff, int maxiters);
+int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);
 int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot /* scalars[out], scalars[out+1] = v'Hv, b'v */);

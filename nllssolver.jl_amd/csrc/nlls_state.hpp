@@ -9,6 +9,7 @@
 //   lookahead_consume     CURRENT's linearisation is needed while a look-ahead sweep is pending: after the swap of an accepted trial it IS that (a hit); otherwise (a miss)
 //                         nothing of A and b counts as formed -- the current point is swept again, the damping kept -- and the look-ahead rests until the next sweep asked for
 //   vars_written          a variable set is about to be written (relaxed: nlls_optimize_singles changes it under the linear system); new_starting_point: CURRENT set
+//   costs_changed         the cost blocks' data or a group's robust parameters were replaced (nlls_set_cost_data, nlls_set_robust_params): no linearisation is held
 //   step_replaced         the caller writes x: nothing known of the last solve's step holds
 //   backsub_done, mf_backsub_done, step_solved   a solve's back-substitution wrote x (and S or the tiles); the host has read the step's statistics
 //   take_mf_tail          a trial's tail finishes the matrix-free step whose sets it retracts, and drops it otherwise (other sets, or a set written since)
@@ -61,6 +62,11 @@ inline int vars_written(nlls_ctx* c, int which, bool relaxed = false) {
     else if (c->lin.level < 2) c->lin.level = 0;    // (what is formed on demand would be formed at the NEW values: the caller sweeps again after writing CURRENT -- every iterator does)
     return NLLS_OK;
 }
+// ---- the costs ---------------------------------------------------------------------------------------------------------
+// The problem itself changed under the linear system, as vars_written(relaxed) has it for the variables: A and b are of the old costs -- the caller sweeps again before anything
+// reads them (NLLS_ERR_NOT_READY until then, as after an upload) --, a pending look-ahead sweep read the old data and is dropped uncounted, the step's cached statistics, E_v s and
+// a matrix-free tail are of the old system.  The variables, lambda, the counters, the known-zero scratch and deferred finishing work (none outlives its nlls_lm_trial) stay.
+inline void costs_changed(nlls_ctx* c) { c->lin.have = false; c->lin.level = 0; c->ahead.pending = c->ahead.stale = false; c->step.cached = c->step.tE_valid = c->step.mf = false; }
 inline void new_starting_point(nlls_ctx* c) { c->ahead.sweeps_since_set = 0; }     // (its first trial gets no look-ahead sweep: sweep_asked)
 // ---- the step, and finishing work deferred to the next launch ---------------------------------------------------------------
 inline void step_replaced(nlls_ctx* c) { c->step.tE_valid = c->step.cached = c->step.mf = false; }

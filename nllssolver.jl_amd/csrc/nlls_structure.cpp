@@ -377,6 +377,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
         }
     }
     c->owner_of_block = owner_of_block;
+    const bool updatable = c->shard_nranks == 1;     // (nlls_set_cost_data refuses a context under nlls_set_shard: no maps are kept for one)
     // ---- per-group lists ---------------------------------------------------------------------------------
     c->groups.resize(ngroups);
     c->em_kernel_vars.clear();
@@ -533,6 +534,9 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
         { const int rcf = build_fold(c, G, d, in, bi, hl[g], sh, segs, row_nlists, row_zero, flags); if (rcf != NLLS_OK) return rcf; }
         G.cost_list = -1;       // (see Group::cost_list)
         for (int s2 = 0; s2 < d.ndeps; ++s2) { const EntryList& E = G.lists[s2]; if (E.n == G.ncost && G.ncost > 0 && E.nlight > 0 && E.nheavy == 0) { G.cost_list = s2; break; } }
+        // (nlls_set_cost_data: the lists' order, turned round -- block k of the caller's group -> its entry -- before it is dropped; see Group::pos_list)
+        if (updatable) for (int s2 = 0; s2 < d.ndeps; ++s2) { const std::vector<int64_t>& lc = hl[g][s2].cost; if (lc.empty()) continue;
+            G.pos_list[s2].assign((size_t)in.ncost, UPD_ABSENT); for (size_t e = 0; e < lc.size(); ++e) G.pos_list[s2][(size_t)lc[e]] = (uint32_t)e; }
         for (int s2 = 0; s2 < d.ndeps; ++s2) std::vector<int64_t>().swap(hl[g][s2].cost);
     }
     std::vector<int64_t> red_off; std::vector<uint32_t> red_len, red_dst, red_which;   // stage-0 reduce ranges
@@ -555,6 +559,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
             const int64_t blk = (int64_t)bi[v] - 1;
             row_zero[blk] = 1;                                   // (every rank zeroes the row: it is summed over ranks)
             if (!mine[g][k]) continue;
+            if (updatable) { if (G.pos_dense.empty()) G.pos_dense.assign((size_t)in.ncost, UPD_ABSENT); G.pos_dense[(size_t)k] = (uint32_t)hv.size(); }
             for (int q = 0; q < d.ndata; ++q) hd.push_back(in.data[k * d.ndata + q]);
             hv.push_back(c->var_off[v]); hb.push_back((uint32_t)c->boffsets[blk]); ha.push_back((uint32_t)c->diag_off[blk]); row_zero[blk] = 1; }
         G.dense.n = (int64_t)hv.size();
@@ -570,6 +575,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
             Group& G = c->groups[g]; const ResDesc& d = desc[g]; const nlls_cost_group& in = groups[g];
             std::vector<double> hd; std::vector<uint32_t> hv, hb;
             for (int64_t k = 0; k < in.ncost; ++k) { bool any = false; for (int s = 0; s < d.ndeps; ++s) any |= bi[in.varind[k * d.ndeps + s] - 1] != 0; if (!any) continue;
+                if (updatable) { if (G.pos_dense.empty()) G.pos_dense.assign((size_t)in.ncost, UPD_ABSENT); G.pos_dense[(size_t)k] = (uint32_t)(hv.size() / std::max(d.ndeps, 1)); }
                 for (int q = 0; q < d.ndata; ++q) hd.push_back(in.data[k * d.ndata + q]);
                 for (int s = 0; s < d.ndeps; ++s) { int64_t v = in.varind[k * d.ndeps + s] - 1; hv.push_back(c->var_off[v]); hb.push_back(bi[v] ? (uint32_t)c->boffsets[bi[v] - 1] : DEST_NONE); } }
             G.dense.n = (int64_t)(hv.size() / std::max(d.ndeps, 1));
@@ -607,7 +613,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
 // Leaves c->mf_ok false (and nothing else changed) whenever the problem does not qualify: nlls_lm_trial then takes the materialised path.
 int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const uint64_t* bi, int32_t flags) {
     c->mf_ok = false; c->mf_group = -1; c->mf_ps = -1; c->mf_q.release(); c->d_mf_desc.release(); c->mf_nbig = 0;
-    for (Group& G : c->groups) { G.mf_data.release(); G.mf_voff.release(); }
+    for (Group& G : c->groups) { G.mf_data.release(); G.mf_voff.release(); G.pos_mf.clear(); G.d_pos_mf.release(); }
     // (the gather index of build_schur was built for this trial: without it -- or when the problem turns out not to qualify below -- it goes again, unless the flag asked for it)
     struct Drop { nlls_ctx* c; bool keep; ~Drop() { if (!c->mf_ok && !keep) { c->gather_ready = false; c->slab.release(); c->d_slab_off.release(); c->d_slab_groups.release(); c->d_gjobs.release(); c->d_gcons.release(); c->n_gjobs = 0; } } } drop{c, (flags & NLLS_FLAG_DETERMINISTIC) != 0};
     if ((flags & NLLS_FLAG_MATERIALIZE) || ngroups != 1 || c->nranks != 1 || !c->info.is_sparse || !c->gather_ready || c->h_slab_off.size() != c->h_elim_desc.size()) return NLLS_OK;
@@ -633,6 +639,7 @@ int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const 
     // launch order: the supernodes of several batches (one workgroup each), then those of ONE batch (one wavefront each).  Members per batch B <= 64 / (blocks per member):
     // the value that gives the four wavefronts the shortest longest share -- rounds x (fixed work per batch ~ four members' + B)
     std::vector<MfDesc> desc; desc.reserve(c->h_elim_desc.size()); uint32_t ecap = 0, imgmax = 0; int64_t nobs = 0;
+    std::vector<uint32_t> where((size_t)in.ncost, UPD_ABSENT);     // block k -> its record in elimination order (Group::pos_mf)
     const int bmax = mf_batch_max(), nw = mf_elim_waves();
     for (int pass = 0; pass < 2; ++pass) for (size_t ei = 0; ei < c->h_elim_desc.size(); ++ei) { const ElimDesc& e0 = c->h_elim_desc[ei];
         const int nd = (int)e0.nd; if (nd % dc || nd + 1 > 80 || nd / dc > 64 || nd / dc < 1 || e0.nmem > 128 || e0.nmem < 1) return NLLS_OK;
@@ -654,6 +661,7 @@ int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const 
                 int64_t found = -1;
                 for (int64_t t = pos[row]; t < pos[row + 1]; ++t) { const int64_t k = byrow[t]; if ((int64_t)bi[in.varind[k * 2 + cs] - 1] - 1 == nbk) { if (found >= 0) return NLLS_OK; found = k; } }
                 if (found < 0) return NLLS_OK;
+                where[(size_t)found] = (uint32_t)nobs;
                 for (int q2 = 0; q2 < d.ndata; ++q2) hd.push_back(in.data[found * d.ndata + q2]);
                 hv.push_back(c->var_off[in.varind[found * 2] - 1]); hv.push_back(c->var_off[in.varind[found * 2 + 1] - 1]); ++nobs; } }
         desc.push_back(e);
@@ -663,7 +671,7 @@ int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const 
     HIPCHK(G.mf_data.upload(hd)); HIPCHK(G.mf_voff.upload(hv)); HIPCHK(c->d_mf_desc.upload(desc)); HIPCHK(c->mf_q.alloc(mf_part_doubles(c->n_fast_groups, (160 + (int64_t)c->var_kind.size() / 64 + 8) / 4 + 2)));
     c->mf_ecap = ecap; c->mf_wsz = std::max(mf_wave_doubles(ecap, dp), (imgmax + 1) & ~1u); c->mf_lds = sizeof(double) * (size_t)c->mf_wsz * mf_elim_waves();      // (a wavefront's region also stages its supernode's share in slab layout)
     if (c->mf_lds > (size_t)150 * 1024) return NLLS_OK;
-    c->mf_ok = true; c->mf_group = 0; c->mf_ps = ps;
+    c->mf_ok = true; c->mf_group = 0; c->mf_ps = ps; if (c->shard_nranks == 1) G.pos_mf = std::move(where);
     return NLLS_OK;
 }
 

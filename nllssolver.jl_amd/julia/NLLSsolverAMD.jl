@@ -153,6 +153,16 @@ function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, 
     check(ls.ctx, ccall((:nlls_adaptive_em, lib), Cint, (Ptr{Cvoid}, Int32, Int64, Int32, Ptr{Float64}, Ptr{Int32}), ls.ctx, which, kernelvar, maxiters, storage, iters))
     return storage
 end
+# The reference's costs are mutable and optimize! may be called again (src/optimize.jl:5-17): the same on a linear system kept across calls.  New payload records
+# (ndata x n, one column per block) for the blocks `index` (1-based, the order of problem.costs.data[T]; nothing: the first n) of cost group `group` (0-based) ...
+function setcostdata!(ls::MultiVariateLSgpu, group::Integer, data::Matrix{Float64}, index::Union{Nothing, Vector{Int64}}=nothing)
+    n = index === nothing ? size(data, 2) : length(index)
+    check(ls.ctx, ccall((:nlls_set_cost_data, lib), Cint, (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}), ls.ctx, group, n, index === nothing ? C_NULL : index, data))
+end
+# ... and new parameters (the robust_params of the upload) for that group's robust kernel.  After either, costgradhess! before the next trial.
+function setrobustparams!(ls::MultiVariateLSgpu, group::Integer, params::NTuple{4, Float64})
+    check(ls.ctx, ccall((:nlls_set_robust_params, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), ls.ctx, group, Ref(params)))
+end
 # The EM callback of test/adaptivecost.jl:15-25 with the residuals left on the device: EM into VARS_NEXT (= 1), problem.varnext's kernel rebuilt from what comes back, the
 # cost of what that leaves.  For the loop below, which keeps the variables resident (problem.varnext is fetched before a user callback runs).
 gpuemcallback(kernelvar=1, maxiters=10) = function (cost, problem, data, trailingargs...)

@@ -45,6 +45,14 @@ class MultiVariateLSgpu:
         """optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)   src/robustadaptive.jl:48-73"""
         return self.ctx.adaptive_em(kernel_var, which, maxiters)
 
+    def set_cost_data(self, group, data, index=None):
+        """new measurements for blocks of a cost group on the uploaded structure (index 1-based; nlls_set_cost_data)   the reference's mutable costs, src/optimize.jl:5-17"""
+        self._x = None; self.ctx.set_cost_data(group, data, index)
+
+    def set_robust_params(self, group, params):
+        """new parameters for a cost group's robust kernel (nlls_set_robust_params)"""
+        self._x = None; self.ctx.set_robust_params(group, params)
+
     def uniformscaling(self, k):
         """uniformscaling!(hessian, k)   src/iterators.jl:149,162"""
         self.ctx.damp(k)

@@ -249,6 +249,96 @@ def optimize(problem, options=None, unfixed=None, callback=nullcallback, flags=0
     return NLLSResult(data)
 
 
+class Solver:
+    """One problem's structure kept on the device across solves: the linear system of makesymmvls (src/optimize.jl:16) built ONCE, then optimize / cost / residuals
+    any number of times, with the cost blocks' data and the robust kernels' parameters changed in place in between -- the reference's mutable costs and repeated
+    optimize! (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops.  N.optimize, N.cost, ... build and drop a linear system per call.
+    A context manager; `unfixed`, `flags`, `device`, `stream` as N.optimize takes them.  What cannot change without a new Solver: which variables a block depends on,
+    which are fixed, the kinds, the number of blocks."""
+
+    def __init__(self, problem, unfixed=None, flags=0, device=0, stream=None):
+        assert problem.nvariables > 0
+        self.problem = problem
+        self.ls = makesymmvls(problem, convertunfixed(unfixed, problem), flags, device, stream)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        if self.ls is not None:
+            self.ls.close(); self.ls = None
+
+    def _start(self):
+        """problem.variables -> the device's current set, varnext = deepcopy(variables) (what a fresh linear system starts with)"""
+        self.ls._x = None
+        self.ls.ctx.set_variables(self.problem.variables, VARS_CURRENT)
+        self.ls.copy(VARS_NEXT, VARS_CURRENT)
+
+    def _group(self, group):
+        return list(self.problem.costs.values())[group]
+
+    def optimize(self, options=None, callback=nullcallback, native=None):
+        """optimize!(problem, options, unfixed, callback) -> NLLSResult on the kept linear system: starts from problem.variables, leaves the best values there."""
+        options = options or NLLSOptions()
+        starttime = time.perf_counter_ns()
+        self._start()
+        data = NLLSInternal(self.ls, starttime)
+        mk, iterate = _ITER[options.iterator]
+        optimizeinternal(self.problem, options, data, mk(), iterate, callback or nullcallback, native)
+        self.problem.variables[:] = self.ls.variables(VARS_CURRENT)
+        return NLLSResult(data)
+
+    def cost(self):
+        """cost(problem)   src/cost.jl:9"""
+        self._start()
+        return self.ls.cost(VARS_CURRENT)
+
+    def _blockvalues(self, group, what):
+        self._start()
+        if group is not None:
+            return self.ls.eval_blocks(int(group), VARS_CURRENT, what)[what]
+        return [self.ls.eval_blocks(g, VARS_CURRENT, what)[what] for g in range(len(self.problem.costs))]
+
+    def residuals(self, group=None):
+        """as N.residuals"""
+        return self._blockvalues(group, "r")
+
+    def squarederrors(self, group=None):
+        """as N.squarederrors"""
+        return self._blockvalues(group, "sqerr")
+
+    def set_data(self, group, data, index=None):
+        """New data (measurements) for blocks of cost group `group` (0-based, the order of problem.costs): `data` (n x ndata) for the blocks `index` (0-BASED here, as
+        `group` is; distinct) or, index=None, for the first n.  Written to the device (nlls_set_cost_data) and to the problem's CostGroup: the two never disagree."""
+        g = self._group(group); vi, da = g.arrays()
+        data = np.ascontiguousarray(data, np.float64).reshape(-1, da.shape[1])
+        idx = None if index is None else np.asarray(index, np.int64).ravel()
+        assert data.shape[0] == (idx.size if idx is not None else data.shape[0]) and data.shape[0] <= da.shape[0]
+        self.ls.set_cost_data(int(group), data, None if idx is None else idx + 1)       # (refuses an index out of range or listed twice before anything changes)
+        new = da.copy()
+        if idx is None:
+            new[:data.shape[0]] = data
+        else:
+            new[idx] = data
+        g.set_arrays(vi, new)
+
+    def set_robust(self, group, params_or_kernel):
+        """New parameters for the robust kernel of cost group `group`: a kernel of the group's own kind (HuberKernel(w1), Scaled(HuberKernel(w1), h1), ...) or its
+        robust_params.  Written to the device (nlls_set_robust_params) and to the problem's CostGroup.  The kind itself cannot change."""
+        from . import kinds as K
+        g = self._group(group)
+        if isinstance(params_or_kernel, K.Robustifier):
+            assert params_or_kernel.kind == g.robust.kind, "set_robust: the robust kind is fixed at upload"
+            new = params_or_kernel
+        else:
+            new = K.Robustifier(g.robust.kind, tuple(np.asarray(params_or_kernel, np.float64).ravel()[:4]))
+        self.ls.set_robust_params(int(group), new.params)
+        g.robust = new
+
+
 SINGLES_MAX_DOF = 12          # NLLS_SINGLES_MAX_DOF (include/nlls_amd.h)
 last_singles_stats = dict(singles_wave=0, singles_thread=0)
 
