@@ -372,7 +372,15 @@ int  nlls_solve(nlls_ctx* ctx, double* x_out);
  * [18] lower tiles stored (fill included), [19] kernel launches per reduced solve, [20] 128^3 tile products per factorisation (updates + panels).
  * [21], [22] look-ahead sweeps used / thrown away; [23] matrix-free LM trials, [24] gradient sweeps of the reduced rows only, [25] full accumulate sweeps since the upload;
  * [26] unknowns per block of the block cyclic reduction (the smallest multiple of 16 that keeps the band block tridiagonal: may be below the bandwidth [5]);
- * [27], [28] variables the last nlls_optimize_singles call relaxed one per wavefront / one per thread (on this rank). */
+ * [27], [28] variables the last nlls_optimize_singles call relaxed one per wavefront / one per thread (on this rank).
+ * The branches nlls_upload_structure chose (host integers, for tests that must assert the path they were written for; on this rank):
+ * elimination supernodes [29] on the fast path with at most 60 neighbour unknowns, [30] fast with 61..63, [31] fast with 64..70, [32] on the generic
+ * (LDS-staged) path with pair accumulators in LDS, [33] generic without accumulators; [34] neighbour blocks of eliminated blocks that are stored in the
+ * NEIGHBOUR's block row and read transposed (an eliminated variable listed before a reduced neighbour), [35] all neighbour blocks; [36] 1: the materialised
+ * elimination assembles through slabs + gather (NLLS_FLAG_DETERMINISTIC took effect).  Accumulate sweep, summed over cost groups and their slots:
+ * [37] light tiles, [38] heavy tiles that carry an LDS image, [39] heavy tiles that write straight to memory (rows too long for an image), [40] tiles (light or
+ * heavy) whose rows are shared or split and flushed with atomics, [41] cost groups swept folded, [42] cost groups the last full accumulate sweep ran as one fused
+ * launch (0 before the first sweep). */
 int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
 /* Run-time switches of a context (A/B measurements, parity tests through both paths on ONE upload):
  *   NLLS_OPT_MATERIALIZE  value != 0: nlls_lm_trial eliminates from the materialised A.data (the round-5 path) although the structure qualifies for the

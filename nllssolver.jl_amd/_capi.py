@@ -389,14 +389,20 @@ class Context:
         return dict(timegradient=out[0] * 1e-9, timecost=out[1] * 1e-9, timesolver=out[2] * 1e-9, trials=int(out[3]))
 
     def solve_stats(self):
-        out = np.zeros(29, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 29))
+        out = np.zeros(43, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 43))
         return dict(status=int(out[0]), band_factor_cycles=int(out[1]), band_backward_cycles=int(out[2]), solve_mode=int(out[3]),
                     elim_supernodes=int(out[4]), bandwidth=int(out[5]), bcr_mfma_issued=int(out[6]), bcr_launches=int(out[7]), bcr_levels=int(out[8]),
                     band_dof=int(out[9]), dropped_pivots=int(out[10]), reduced_row_sums=int(out[11]), lazy_trials=int(out[12]),
                     reordered=int(out[13]), bandwidth_caller_order=int(out[14]), dense_window=int(out[15]),
                     tsp_tiles=int(out[16]), tsp_levels=int(out[17]), tsp_lower_tiles=int(out[18]), tsp_launches=int(out[19]), tsp_products=int(out[20]),
                     lookahead_hits=int(out[21]), lookahead_misses=int(out[22]), mf_trials=int(out[23]), reduced_sweeps=int(out[24]), full_sweeps=int(out[25]), bcr_block=int(out[26]),
-                    singles_wave=int(out[27]), singles_thread=int(out[28]))
+                    singles_wave=int(out[27]), singles_thread=int(out[28]),
+                    # the branches the upload chose: supernodes of the elimination by kernel class, neighbour blocks read transposed / in all, slab assembly in use;
+                    # tiles of the accumulate sweep by class (summed over groups and slots), folded groups, groups the last full sweep launched fused
+                    elim_fast60=int(out[29]), elim_fast_narrow=int(out[30]), elim_fast_wide=int(out[31]), elim_slow_acc=int(out[32]), elim_slow_noacc=int(out[33]),
+                    elim_nbrs_transposed=int(out[34]), elim_nbrs=int(out[35]), elim_slab=int(out[36]),
+                    sweep_light_tiles=int(out[37]), sweep_image_tiles=int(out[38]), sweep_direct_tiles=int(out[39]), sweep_partial_tiles=int(out[40]),
+                    sweep_fold_groups=int(out[41]), sweep_fused_groups=int(out[42]))
 
     def set_step(self, x):
         x = np.ascontiguousarray(x, np.float64); assert x.size == self.info.ndof

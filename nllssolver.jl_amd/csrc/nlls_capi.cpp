@@ -664,15 +664,22 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
     int32_t status[16] = {0};
     HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    const int64_t vals[29] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
+    const int64_t vals[43] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
                               ctx->ahead.hits, ctx->ahead.misses /* look-ahead sweeps used / thrown away */,
                               ctx->mf_trials, ctx->mf_reduced_sweeps, ctx->full_sweeps /* matrix-free LM trials, sweeps of the reduced rows only, full accumulate sweeps since the upload */,
                               ctx->bcr.ready ? 16 * ctx->bcr.NT : 0 /* unknowns per block of the block cyclic reduction */,
-                              ctx->singles_wave, ctx->singles_thread /* variables the last nlls_optimize_singles call relaxed one per wavefront / one per thread */};
-    for (int i = 0; i < n && i < 29; ++i) out[i] = vals[i];
+                              ctx->singles_wave, ctx->singles_thread /* variables the last nlls_optimize_singles call relaxed one per wavefront / one per thread */,
+                              // [29..36] the elimination as the upload classed it: fast supernodes of at most 60 / 61..63 / 64..70 neighbour unknowns, generic (LDS-staged) supernodes with / without
+                              // pair accumulators, neighbour blocks read transposed (stored in the neighbour's row) / in all, the slab + gather assembly of the materialised elimination in use
+                              ctx->n_fast_n60, ctx->n_fast_narrow - ctx->n_fast_n60, ctx->n_fast_groups - ctx->n_fast_narrow, ctx->n_slow_acc, ctx->n_slow_groups - ctx->n_slow_acc,
+                              ctx->n_elim_nbrs_trans, ctx->n_elim_nbrs, ctx->elim_slab ? 1 : 0,
+                              // [37..42] the accumulate sweep, summed over groups (and slots): light tiles, heavy tiles with an LDS image, TILE_DIRECT tiles, TILE_PARTIAL tiles (light or heavy),
+                              // folded groups, groups whose last full sweep was one fused launch
+                              ctx->n_tiles_light, ctx->n_tiles_image, ctx->n_tiles_direct, ctx->n_tiles_partial, ctx->n_fold_groups, ctx->sweep_fused_groups};
+    for (int i = 0; i < n && i < 43; ++i) out[i] = vals[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

@@ -289,6 +289,10 @@ struct nlls_ctx {
     int64_t mf_trials = 0, mf_reduced_sweeps = 0, full_sweeps = 0;   // diagnostics (nlls_get_solve_stats [23..25])
     int64_t singles_wave_min = 64;           // nlls_optimize_singles: cost blocks from which a variable of at most 6 dof gets a wavefront instead of a thread (NLLS_SINGLES_WAVE_MIN)
     int64_t singles_wave = 0, singles_thread = 0;   // variables of the last nlls_optimize_singles call per kernel (nlls_get_solve_stats [27], [28])
+    // the branches the upload chose, reported so that a test can assert the path it was written for (nlls_get_solve_stats [29..42]; the supernode classes are the
+    // n_fast_* / n_slow_* counters below).  Tiles are summed over groups and slots; sweep_fused_groups is counted by the last full accumulate sweep itself.
+    int64_t n_elim_nbrs = 0, n_elim_nbrs_trans = 0;      // neighbour blocks of the eliminated members, and those stored in the NEIGHBOUR's row (SchurNbr::trans)
+    int64_t n_tiles_light = 0, n_tiles_image = 0, n_tiles_direct = 0, n_tiles_partial = 0, n_fold_groups = 0, sweep_fused_groups = 0;
     std::vector<int64_t> h_erow; std::vector<int64_t> h_eptr; std::vector<int64_t> h_enbr_block; std::vector<nlls::ElimDesc> h_elim_desc; std::vector<uint32_t> h_fast_voff;   // host copies kept between build_schur and build_mf
 
     // ---- sharding ------------------------------------------------------------------------------------

@@ -208,6 +208,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     c->rank = c->shard_rank; c->nranks = c->shard_nranks; c->replicated = false;      // what nlls_set_shard asked for (a problem that does not shard falls back to replicas below)
     c->presharded = (flags & NLLS_FLAG_PRESHARDED) != 0 && c->nranks > 1;
     c->ready = false; c->n_stage0 = 0; c->n_lazy_trials = 0; upload_started(c);
+    c->n_tiles_light = c->n_tiles_image = c->n_tiles_direct = c->n_tiles_partial = c->n_fold_groups = c->sweep_fused_groups = 0;
     { std::vector<HotItem> v; hot_set(c, v); for (HotItem& it : v) if (!*it.owned) { *it.pp = nullptr; *it.owned = true; } }   // what lived in the previous upload's arena is gone with it
     c->arena.release(); c->arena_pre.release();     // ... so release it NOW: a re-upload would otherwise hold two arenas (and every buffer once more) at its peak
     c->groups.clear();
@@ -529,9 +530,11 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
             E.nlight = (int64_t)light.size(); E.nheavy = (int64_t)heavy.size();
             HIPCHK(E.light.upload(light)); HIPCHK(E.heavy.upload(heavy));
             npartials += E.nlight + E.nheavy;
+            for (const Tile& t : light) { c->n_tiles_light++; if (t.flags & TILE_PARTIAL) c->n_tiles_partial++; }
+            for (const Tile& t : heavy) { if (t.flags & TILE_DIRECT) c->n_tiles_direct++; else c->n_tiles_image++; if (t.flags & TILE_PARTIAL) c->n_tiles_partial++; }
             sh[s].dest = std::move(dest); sh[s].light = std::move(light); sh[s].heavy = std::move(heavy);
         }
-        { const int rcf = build_fold(c, G, d, in, bi, hl[g], sh, segs, row_nlists, row_zero, flags); if (rcf != NLLS_OK) return rcf; }
+        { const int rcf = build_fold(c, G, d, in, bi, hl[g], sh, segs, row_nlists, row_zero, flags); if (rcf != NLLS_OK) return rcf; if (G.fold) c->n_fold_groups++; }
         G.cost_list = -1;       // (see Group::cost_list)
         for (int s2 = 0; s2 < d.ndeps; ++s2) { const EntryList& E = G.lists[s2]; if (E.n == G.ncost && G.ncost > 0 && E.nlight > 0 && E.nheavy == 0) { G.cost_list = s2; break; } }
         // (nlls_set_cost_data: the lists' order, turned round -- block k of the caller's group -> its entry -- before it is dropped; see Group::pos_list)
@@ -767,6 +770,7 @@ int build_schur(nlls_ctx* c, int32_t flags) {
     // (a re-upload -- or the retry without Schur elimination after an unsupported shape -- must not see the previous
     // attempt's supernode lists: the solve dispatches on these counters)
     c->n_fast_groups = 0; c->n_slow_groups = 0; c->n_fast_members = 0; c->n_fast_narrow = 0; c->n_fast_n60 = 0; c->fast_dv = 0;
+    c->n_slow_acc = 0; c->n_elim_nbrs = 0; c->n_elim_nbrs_trans = 0;
     c->h_elim_desc.clear(); c->h_erow.clear(); c->h_eptr.clear(); c->h_enbr_block.clear(); c->mf_ok = false; c->bcr.release();
     c->elim_slab = false; c->gather_ready = false; c->h_slab_off.clear(); c->slab.release(); c->d_slab_off.release(); c->d_slab_groups.release(); c->d_gjobs.release(); c->d_gcons.release(); c->n_gjobs = 0;
     // (the solve also dispatches on the SIZE of these lists: an upload without elimination must not inherit them)
@@ -931,7 +935,7 @@ int build_schur(nlls_ctx* c, int32_t flags) {
                 if (c->diag_off[v] != ediag.back() + dv * dv + dv * nd || (int64_t)c->boffsets[v] != (int64_t)eboff.back() + dv) same = false; }
             if (!same) { egroup.push_back((uint32_t)ediag.size()); glen = 0; }
             ++glen; prev = nl;
-            for (auto& n : nl) enbr.push_back(n);
+            for (auto& n : nl) { enbr.push_back(n); c->n_elim_nbrs++; c->n_elim_nbrs_trans += n.trans; }
             erow.push_back(v); eptr.push_back((int64_t)enbr.size()); ediag.push_back(c->diag_off[v]); eboff.push_back((uint32_t)c->boffsets[v]); edim.push_back((uint16_t)c->blocksizes[v]);
         }
         egroup.push_back((uint32_t)ediag.size());

@@ -815,7 +815,9 @@ static int launch_gh(nlls_ctx* c, const Group& G, const double* vars, int64_t& p
     if (c->info.is_sparse) {
         // (three-slot kinds whose lists do not qualify for the folded sweep take one launch per role: rounds 2-4's one-launch form of that, gh_fused3_kernel -- every block
         //  evaluated once per ROLE, 244 registers -- went with the fold: 104 against 55 us at BASELINE config 5; last in the tree at commit 6e015b8)
-        if (!launch_gh_fold<KIND>(c, G, vars, pbase) && !launch_gh_fused<KIND>(c, G, vars, pbase)) {
+        if (launch_gh_fold<KIND>(c, G, vars, pbase)) {}
+        else if (launch_gh_fused<KIND>(c, G, vars, pbase)) c->sweep_fused_groups++;      // (diagnostics: nlls_get_solve_stats [42])
+        else {
             [&]<int... S>(std::integer_sequence<int, S...>) { (launch_gh_slot<KIND, S>(c, G, vars, pbase), ...); }(std::make_integer_sequence<int, Res<KIND>::NDEPS>{});   // (one pass per slot: up to MAX_SLOTS)
         }
     } else if (G.dense.n > 0) {
@@ -835,7 +837,7 @@ int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost, int which, int mode) {
     if (mode == 1 && (!c->mf_ok || want_cost)) mode = 0;
     sweep_enqueued(c, which, mode == 1 ? 1 : 2); if (mode == 1) c->mf_reduced_sweeps++; else c->full_sweeps++;
     const double* vars = vars_ptr(c, which); int64_t pbase = 0;
-    c->dense_slab_used = 0;
+    c->dense_slab_used = 0; if (mode != 1) c->sweep_fused_groups = 0;
     if (c->tiny_dense) {
         // (nothing to zero: the gathering launch writes every element of A and b)
     } else if (!c->info.is_sparse) {

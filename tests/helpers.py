@@ -174,6 +174,94 @@ def longdouble_schur_step(A_data, bsm_index, b, lam, elim_blocks):
     return x, S.astype(np.float64)
 
 
+# ---- the same problem with its variables listed in another order (tests/test_variable_order.py, tests/test_gpu_variable_order.py) ---------------------
+# Every generator lists the variables of the reduced system (cameras, poses, the adaptive kernel variable) before the eliminated ones (points).  The C ABI
+# takes any order and the reference does not care (its LDL' orders itself); the device code does: a coupling block lies in the block row of whichever of its
+# two variables comes LATER, so an eliminated variable listed before a reduced neighbour finds its block in the neighbour's row, stored transposed.
+def permute_variables(problem, perm):
+    """(new_problem, new_of_old): the variables of `problem` -- kind, size and stored values -- listed in the order `perm` (perm[new] = old, 0-based); every cost
+    group with its block order, data and robust kernel, its varind re-indexed (the slot order inside a block is the residual kind's and stays).
+    new_of_old[old] = new, 0-based."""
+    from nllssolver_jl_amd import NLLSProblem
+    perm = np.asarray(perm, np.int64); n = problem.nvariables
+    assert perm.shape == (n,) and np.array_equal(np.sort(perm), np.arange(n)), "perm is not a permutation of the variables"
+    new_of_old = np.empty(n, np.int64); new_of_old[perm] = np.arange(n)
+    off = problem.var_offsets; v = problem.variables; kk, dd = problem.var_kind, problem.var_dim
+    q = NLLSProblem()
+    for old in perm:
+        q.addvariable(v[off[old]:off[old + 1]], int(kk[old]))
+    assert np.array_equal(q.var_kind, kk[perm]) and np.array_equal(q.var_dim, dd[perm])
+    for g in problem.costs.values():
+        vi, da = g.arrays()
+        q.addcosts(g.res_kind, new_of_old[vi - 1] + 1, da.copy(), g.robust)
+    assert list(q.costs.keys()) == list(problem.costs.keys())
+    return q, new_of_old
+
+
+def to_original_order(vec, sizes, new_of_old):
+    """A packed vector of the PERMUTED problem (one segment per variable, in the new order) in the ORIGINAL order.  sizes[old] = length of the variable's
+    segment: its storage for a variable vector, its unknowns (0 if fixed) for a step or a gradient."""
+    sizes = np.asarray(sizes, np.int64); new_of_old = np.asarray(new_of_old, np.int64); n = sizes.size
+    sizes_new = np.empty(n, np.int64); sizes_new[new_of_old] = sizes
+    off_new = np.concatenate([[0], np.cumsum(sizes_new)])
+    vec = np.asarray(vec); assert vec.size == off_new[-1], (vec.size, off_new[-1])
+    start = off_new[new_of_old]                                              # per old variable: where its segment starts in the permuted vector
+    idx = np.repeat(start, sizes) + (np.arange(sizes.sum()) - np.repeat(np.cumsum(sizes) - sizes, sizes))
+    return vec[idx]
+
+
+def variable_sizes(problem, unfixed=None):
+    """(storage, unknowns) per variable of `problem`; unknowns 0 for the variables `unfixed` marks False."""
+    from nllssolver_jl_amd import kinds as K
+    st = np.diff(problem.var_offsets)
+    dof = np.array([K.var_dof(int(k), int(d)) for k, d in zip(problem.var_kind, problem.var_dim)], np.int64)
+    if unfixed is not None: dof = dof * np.asarray(unfixed, bool)
+    return st, dof
+
+
+def eliminated_mask(problem):
+    """The variables of a bundle-adjustment problem of the generators that the elimination takes: the 3-dof Euclidean points."""
+    from nllssolver_jl_amd import kinds as K
+    return (problem.var_kind == K.VAR_EUCLIDEAN) & (problem.var_dim == 3)
+
+
+# named orders (perm[new] = old).  `elim`: boolean per variable, the eliminated ones.
+def order_identity(elim):
+    return np.arange(len(elim))                                              # the control
+
+
+def order_elim_first(elim):
+    elim = np.asarray(elim, bool); return np.r_[np.nonzero(elim)[0], np.nonzero(~elim)[0]]     # all points, then the cameras: every neighbour block transposed
+
+
+def order_reversed(elim):
+    return np.arange(len(elim))[::-1].copy()
+
+
+def order_interleaved(elim):
+    """reduced variable k followed by the k-th share of the eliminated ones: a point's neighbours lie on both sides of it (lists that mix both `trans` values)"""
+    elim = np.asarray(elim, bool); red = np.nonzero(~elim)[0]; shares = np.array_split(np.nonzero(elim)[0], max(red.size, 1))
+    return np.concatenate([np.r_[r, s] for r, s in zip(red, shares)]).astype(np.int64)
+
+
+def order_random(seed):
+    return lambda elim: np.random.default_rng(seed).permutation(len(elim))
+
+
+def order_var_last(var=0):
+    """variable `var` (the adaptive kernel variable: index 0 in every generator) moved behind all others"""
+    return lambda elim: np.r_[np.delete(np.arange(len(elim)), var), var]
+
+
+def order_var_middle(var=0):
+    def f(elim):
+        rest = np.delete(np.arange(len(elim)), var); return np.r_[rest[:rest.size // 2], var, rest[rest.size // 2:]]
+    return f
+
+
+NAMED_ORDERS = dict(identity=order_identity, elim_first=order_elim_first, reversed=order_reversed, interleaved=order_interleaved, random=order_random(7))
+
+
 # ---- two-slot problems of a chosen elimination structure (the matrix-free LM trial's kernel shapes: tests/test_gpu_mf_shapes.py) -------------------
 def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3):
     """A problem of ONE cost group of a two-slot kind whose eliminated set and supernodes the caller chooses.  The `nred` reduced variables come first,
