@@ -335,3 +335,198 @@ def check_structure(ols, meta):
     sizes, counts = np.unique(bs, return_counts=True); best = sizes[np.argmax(counts)]
     assert np.all(bs[elim] == best) and 2 * elim.sum() >= nb
     if np.all(bs == best): assert deg[~elim].min() > deg[elim].max(), "a reduced block would be eliminated first"
+
+
+# ---- graphs that are not bundle adjustment (tests/test_general_graphs.py, tests/test_gpu_general_graphs.py) ------------------------------------------
+# Every sparse problem of the generators is bipartite with the eliminated variable in one fixed slot of one kind.  The symbolic phase takes any graph of cost
+# blocks: the problems below have cost blocks between two REDUCED variables (copied into S, Schur updates on top), the eliminated variable in slot 0 of some
+# blocks and slot 1 of others, four-slot kinds, unary groups beside the coupling group, several block sizes in the reduced system, eliminated classes other than
+# the 3-dof points, and independent sets too small for a Schur complement.
+def expected_elimination(ols):
+    """The blocks select_elimination (csrc/nlls_structure.cpp) takes, from the oracle's block structure (ols.bsm_index()): the candidates are the blocks of the most
+    numerous size (ties: the smaller size) whose neighbours fit the LDS-staged kernels; by ascending degree (stable: ties in block order) a candidate is taken unless
+    a block it shares a stored block with was taken before; the set is kept only if it holds at least half of all blocks.  A boolean per block."""
+    cp, rv, _, bo = (np.asarray(a, np.int64) for a in ols.bsm_index()); nb = len(cp) - 1
+    elim = np.zeros(nb, bool)
+    if not ols.info.is_sparse or nb <= 1: return elim
+    bs = np.diff(np.r_[bo - 1, ols.info.ndof]); rows = np.repeat(np.arange(nb), np.diff(cp)); cols = rv - 1
+    off = rows != cols
+    deg = np.bincount(rows[off], minlength=nb) + np.bincount(cols[off], minlength=nb)
+    nbrs = [[] for _ in range(nb)]
+    for r, c in zip(rows[off], cols[off]): nbrs[r].append(c); nbrs[c].append(r)
+    sizes, counts = np.unique(bs, return_counts=True); best = int(sizes[np.argmax(counts)])          # (np.unique sorts ascending, argmax takes the first: ties to the smaller)
+    fits = lambda v: 8 * (best * best + best * (2 * sum(bs[u] for u in nbrs[v]) + 1)) + 28 * sum(bs[u] for u in nbrs[v]) + 16 <= 150 * 1024
+    cand = [v for v in range(nb) if bs[v] == best and fits(v)]
+    blocked = np.zeros(nb, bool)
+    for v in sorted(cand, key=lambda v: deg[v]):                                                    # (sorted is stable)
+        if blocked[v]: continue
+        elim[v] = True; blocked[v] = True; blocked[nbrs[v]] = True
+    if 2 * elim.sum() < nb: elim[:] = False
+    return elim
+
+
+def block_mask_to_variables(block_mask, bi):
+    """a boolean per variable from a boolean per block (bi: blockindices, 0 = fixed -> False)"""
+    bi = np.asarray(bi, np.int64); out = np.zeros(bi.size, bool); out[bi > 0] = np.asarray(block_mask, bool)[bi[bi > 0] - 1]; return out
+
+
+def structure_counts(problem, ols, elim_blocks, bi=None):
+    """What a case of the general-graph tests is written for, from the oracle's structure and the mirror's set: `independent` (no stored block joins two eliminated
+    blocks), `reduced_reduced` (stored off-diagonal blocks between two reduced blocks), `mixed_slots` (eliminated variables seen in more than one slot of ONE cost
+    group), `elim_slots` (the slots eliminated variables are seen in, over all groups of two or more slots), `elim_unary` (unary cost blocks on eliminated variables),
+    `reduced_sizes` / `elim_sizes` (block sizes)."""
+    cp, rv, _, bo = (np.asarray(a, np.int64) for a in ols.bsm_index()); nb = len(cp) - 1; elim = np.asarray(elim_blocks, bool)
+    bs = np.diff(np.r_[bo - 1, ols.info.ndof]); rows = np.repeat(np.arange(nb), np.diff(cp)); cols = rv - 1; off = rows != cols
+    bi = blockindices(problem) if bi is None else bi
+    ev = block_mask_to_variables(elim, bi)
+    mixed, slots, unary = 0, set(), 0
+    for g in problem.costs.values():
+        vi, _ = g.arrays()
+        if vi.shape[1] == 1: unary += int(ev[vi[:, 0] - 1].sum()); continue
+        seen = np.zeros((problem.nvariables, vi.shape[1]), bool)
+        for s in range(vi.shape[1]): seen[vi[:, s] - 1, s] = True
+        mixed += int((seen[ev].sum(axis=1) > 1).sum()); slots |= set(np.nonzero(seen[ev].any(axis=0))[0].tolist())
+    return dict(independent=not np.any(off & elim[rows] & elim[cols]), reduced_reduced=int((off & ~elim[rows] & ~elim[cols]).sum()), mixed_slots=mixed,
+                elim_slots=sorted(slots), elim_unary=unary, reduced_sizes=sorted(set(bs[~elim].tolist())), elim_sizes=sorted(set(bs[elim].tolist())),
+                nelim=int(elim.sum()), nreduced_dof=int(bs[~elim].sum()))
+
+
+def greedy_independent_set(n, edges):
+    """expected_elimination on a graph of n one-dof variables given as an edge list (0-based pairs; repeated edges count once): what scalar_graph_problem needs to know
+    BEFORE it builds the problem, to keep the eliminated variables in one slot when mix_slots is off."""
+    e = np.unique(np.sort(np.asarray(edges, np.int64).reshape(-1, 2), axis=1), axis=0)
+    deg = np.bincount(e.ravel(), minlength=n); nbrs = [[] for _ in range(n)]
+    for a, b in e: nbrs[a].append(b); nbrs[b].append(a)
+    elim = np.zeros(n, bool); blocked = np.zeros(n, bool)
+    for v in sorted(range(n), key=lambda v: deg[v]):
+        if blocked[v]: continue
+        elim[v] = True; blocked[v] = True; blocked[nbrs[v]] = True
+    if 2 * elim.sum() < n: elim[:] = False
+    return elim
+
+
+def scalar_graph_problem(edges, n, seed, mix_slots=True, unary=True, robust=None):
+    """n one-dof variables in U(0.5, 1.5); one RES_ROSENBROCK_B block b (x^2 - y), b in U(0.5, 2), per entry of `edges` (0-based pairs, repeats allowed: several cost
+    blocks on one stored block) under `robust`; unary: one RES_ROSENBROCK_A block on every variable (a second group, on eliminated and reduced variables alike).
+    mix_slots: every edge's orientation -- which end is x -- is drawn with probability 1/2, so a variable is x in some of its blocks and y in others; off: an end the
+    greedy independent set takes is always x (slot 0), edges between two reduced variables stay as listed."""
+    from nllssolver_jl_amd import NLLSProblem, kinds as K
+    rng = np.random.default_rng(seed); e = np.asarray(edges, np.int64).reshape(-1, 2).copy()
+    assert e.min() >= 0 and e.max() < n and np.all(e[:, 0] != e[:, 1])
+    p = NLLSProblem(); p.addvariables(rng.uniform(0.5, 1.5, (n, 1)))
+    flip = rng.random(len(e)) < 0.5                                                                 # (drawn either way: the other numbers do not depend on mix_slots)
+    if not mix_slots: flip = greedy_independent_set(n, e)[e[:, 1]]
+    e[flip] = e[flip][:, ::-1]
+    p.addcosts(K.RES_ROSENBROCK_B, e + 1, rng.uniform(0.5, 2.0, (len(e), 1)), robust)
+    if unary: p.addcosts(K.RES_ROSENBROCK_A, np.arange(1, n + 1)[:, None], rng.uniform(0.5, 1.5, (n, 1)))
+    return p
+
+
+# edge-list builders: (edges, n).  The size parameter puts the reduced system under the 64 dof of the one-wavefront solve or over the 128 of the band solvers.
+def chain_edges(n):
+    """a path: the ends (degree 1), then every other variable: n / 2 eliminated, each with two reduced neighbours; one reduced-reduced block for even n"""
+    return np.stack([np.arange(n - 1), np.arange(1, n)], axis=1), n
+
+
+def lattice_edges(w, h, diagonal=False):
+    """a w x h grid, row-major; diagonal: with one diagonal per cell (a triangular lattice).  Its greedy independent set stays under half of the variables."""
+    idx = np.arange(w * h).reshape(h, w)
+    e = [np.stack([idx[:, :-1].ravel(), idx[:, 1:].ravel()], axis=1), np.stack([idx[:-1].ravel(), idx[1:].ravel()], axis=1)]
+    if diagonal: e.append(np.stack([idx[:-1, :-1].ravel(), idx[1:, 1:].ravel()], axis=1))
+    return np.concatenate(e), w * h
+
+
+def caterpillar_edges(nhubs, nleaves=4):
+    """hubs 0 .. nhubs-1, hub k coupled to k+1 and k+2 (2 nhubs - 3 reduced-reduced blocks, a band of two); nleaves leaves (degree 1: eliminated) on every hub, listed
+    after the hubs"""
+    hubs = np.arange(nhubs)
+    e = [np.stack([hubs[:-1], hubs[1:]], axis=1), np.stack([hubs[:-2], hubs[2:]], axis=1)]
+    e.append(np.stack([np.repeat(hubs, nleaves), nhubs + np.arange(nhubs * nleaves)], axis=1))
+    return np.concatenate(e), nhubs * (1 + nleaves)
+
+
+def shared_leaves_edges(nhubs, nleaves, heavy=0):
+    """hubs in a chain (nhubs - 1 reduced-reduced blocks); every leaf on three consecutive hubs (degree 3, eliminated: the Schur update of a leaf lands on the two
+    chain blocks inside its window and fills the block between its outer hubs).  heavy: leaf 0's three edges are listed that many times more (one variable with
+    3 (heavy + 1) coupling blocks on three stored blocks)."""
+    hubs = np.arange(nhubs); start = (np.arange(nleaves) * (nhubs - 2)) // nleaves
+    leaf = nhubs + np.arange(nleaves)
+    e = [np.stack([hubs[:-1], hubs[1:]], axis=1)] + [np.stack([start + k, leaf], axis=1) for k in range(3)]
+    e += [np.stack([start[:1] + k, leaf[:1]], axis=1) for _ in range(heavy) for k in range(3)]
+    return np.concatenate(e), nhubs + nleaves
+
+
+def hub_edges(n, pendants=0):
+    """a chain of n (odd) variables, `pendants` more variables hung on its odd members (which the chain's elimination leaves in the reduced system), and one last variable
+    coupled to every other: with 64 or more eliminated variables it couples to more than a quarter of them and becomes a border block of the reduced system."""
+    assert n % 2 == 1
+    e = [chain_edges(n)[0]]
+    odd = np.arange(1, n, 2)
+    if pendants: e.append(np.stack([odd[np.arange(pendants) % odd.size], n + np.arange(pendants)], axis=1))
+    hub = n + pendants
+    e.append(np.stack([np.arange(hub), np.full(hub, hub)], axis=1))
+    return np.concatenate(e), hub + 1
+
+
+def curve_family_problem(ncurves, npoints, own, seed=0, noise=1e-3):
+    """a exp(b t) + c t + d - y (RES_CURVE_EXP4, four one-dof slots) over ncurves curves of npoints samples each.  own: the slots (0 .. 3) whose parameter every curve
+    has for itself; the others are shared by all curves.  own = (0,) or (3,): the curves' own parameters (degree 3) are eliminated, each coupled to the three shared
+    scalars by npoints cost blocks, the same blocks that couple the three reduced scalars to one another.  own = (0, 1): a curve's two parameters share a stored
+    block, the independent set holds one of them -- under half of all blocks, no Schur complement."""
+    from nllssolver_jl_amd import NLLSProblem, kinds as K
+    rng = np.random.default_rng(seed); own = tuple(own); truth = np.array([2.0, -1.5, 0.7, 0.3]); start = np.array([1.5, -1.0, 0.0, 0.0])
+    p = NLLSProblem(); par = np.tile(truth, (ncurves, 1)); slotvar = np.zeros((ncurves, 4), np.int64)
+    for s in range(4):
+        if s in own:
+            par[:, s] = truth[s] * rng.uniform(0.8, 1.2, ncurves)
+            slotvar[:, s] = p.addvariables((start[s] + rng.uniform(-0.1, 0.1, ncurves))[:, None]) + np.arange(ncurves)
+        else:
+            slotvar[:, s] = p.addvariable(start[s])
+    t = rng.random((ncurves, npoints)) * 2.0
+    y = par[:, 0:1] * np.exp(par[:, 1:2] * t) + par[:, 2:3] * t + par[:, 3:4] + rng.standard_normal(t.shape) * noise
+    p.addcosts(K.RES_CURVE_EXP4, np.repeat(slotvar, npoints, axis=0), np.stack([t.ravel(), y.ravel()], axis=1))
+    return p
+
+
+def mixed_sizes_problem(extra="linear3", seed=3):
+    """Affine bundle adjustment 12 x 150 at 0.3 under a Huber kernel (6-dof cameras, 3-dof points: the eliminated class) with, beside it,
+      extra = "linear3": X w - y (RES_LINEAR3, unary) on every third point, and a chain of 40 scalars (RES_ROSENBROCK_B with both orientations, RES_ROSENBROCK_A on each):
+        a second component of one-dof blocks that all stay in the reduced system, next to the 6-dof cameras;
+      extra = "cost3": the same with the non-squared cost y'w (COST_LINEAR3) on those points;
+      extra = "adaptive_mean": instead an RES_ADAPTIVE_MEAN component -- one ContaminatedGaussian variable (3 dof: the points' size class, not Euclidean, of degree 2: a
+        candidate the greedy set reaches early) and two means, 60 blocks."""
+    import nllssolver_jl_amd as N
+    from nllssolver_jl_amd import synthetic, kinds as K
+    from nllssolver_jl_amd.variables import contaminated_gaussian
+    ncam, npts = 12, 150; rng = np.random.default_rng(seed)
+    p = synthetic.perturb_ba_problem(synthetic.create_ba_problem(ncam, npts, 0.3, seed=seed, robust=N.HuberKernel(0.05), outlier_frac=0.1, outlier_sigma=0.05), 1e-3, 1e-3)
+    if extra in ("linear3", "cost3"):
+        pts = np.arange(0, npts, 3); w = p.variables.reshape(-1)[6 * ncam:].reshape(npts, 3)[pts]
+        if extra == "linear3":
+            X = rng.standard_normal((pts.size, 3, 3)) + 2.0 * np.eye(3); y = np.einsum("nij,nj->ni", X, w) + 0.01 * rng.standard_normal((pts.size, 3))
+            p.addcosts(K.RES_LINEAR3, (ncam + pts + 1)[:, None], np.concatenate([y, X.transpose(0, 2, 1).reshape(pts.size, 9)], axis=1))      # (y, X column-major)
+        else:
+            p.addcosts(K.COST_LINEAR3, (ncam + pts + 1)[:, None], 0.01 * rng.standard_normal((pts.size, 3)))
+        n0 = p.nvariables; e, n = chain_edges(40)
+        p.addvariables(rng.uniform(0.5, 1.5, (n, 1)))
+        e = e.copy(); flip = rng.random(len(e)) < 0.5; e[flip] = e[flip][:, ::-1]
+        p.addcosts(K.RES_ROSENBROCK_B, e + n0 + 1, rng.uniform(0.5, 2.0, (len(e), 1)))
+        p.addcosts(K.RES_ROSENBROCK_A, (np.arange(n) + n0 + 1)[:, None], rng.uniform(0.5, 1.5, (n, 1)))
+    else:
+        assert extra == "adaptive_mean"
+        k = p.addvariable(contaminated_gaussian(0.5, 5.0, 0.6), K.VAR_CONTAMINATED_GAUSSIAN); m1 = p.addvariable(-0.7); m2 = p.addvariable(0.6)
+        draws = np.concatenate([rng.standard_normal(24), rng.standard_normal(6) * 10.0])
+        vi = np.empty((60, 2), np.int64); vi[:, 0] = k; vi[0::2, 1] = m1; vi[1::2, 1] = m2
+        da = np.empty((60, 1)); da[0::2, 0] = draws - 1; da[1::2, 0] = draws + 1
+        p.addcosts(K.RES_ADAPTIVE_MEAN, vi, da)
+    return p
+
+
+def many_cameras_problem(so3, seed=4):
+    """120 cameras over 30 points at 0.15: the 6-dof class is the most numerous and independent -- the CAMERAS (affine, or SO(3) poses: storage 12, a retraction that is
+    not an addition) are eliminated, the points form the reduced system."""
+    import nllssolver_jl_amd as N
+    from nllssolver_jl_amd import synthetic
+    if so3: p = synthetic.create_so3_ba_problem(120, 30, 0.15, seed=seed, adaptive=False, robust=N.HuberKernel(0.05))
+    else: p = synthetic.create_ba_problem(120, 30, 0.15, seed=seed, robust=N.HuberKernel(0.05), outlier_frac=0.1, outlier_sigma=0.05)
+    return synthetic.perturb_ba_problem(p, 1e-3, 1e-3)
