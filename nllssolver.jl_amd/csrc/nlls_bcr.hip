@@ -26,8 +26,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "nlls_bcr.hpp"
-#include "nlls_tsp.hpp"
+#include "nlls_internal.hpp"
 
 namespace nlls {
 
@@ -598,30 +597,23 @@ void launch_dense_dcopy_all(hipStream_t st, double* S, const double* Dfac, int n
 template <int NT, int DCH> constexpr size_t dense_panel_lds() { return sizeof(double) * ((size_t)(NT * (NT + 1) / 2 + DCH * NT) * BTS + 2 * (size_t)(NT + DCH) * 16 * BP + 64 + 2 * 16 * BP + BTS); }
 static_assert(dense_panel_lds<8, 2>() <= 160 * 1024, "the 128-column panel must fit the LDS of a CU");
 // k: index of the panel in units of ITS width (64 or 128 columns)
-void launch_dense_panel(hipStream_t st, double* S, double* W, double* LiD, int npad, int k, int* status, int wide, double* Dfac, DenseWin win) {
+void launch_dense_panel(hipStream_t st, double* S, double* W, double* LiD, int npad, int k, int* status, int wide, double* Dfac, int one_row_max, DenseWin win) {
     const int T = npad / 16;
     DensePanelArgs a{S, W, LiD, npad, k, T, status, Dfac + (size_t)(wide ? 2 * k : k) * 128 * 128, -1, 0};   // the panel's slot
     if (win.nwin >= 0 && wide) {
         // windowed: the step's logical tile rows = 8 per 128-row block of the window and of the strip; one X tile row per workgroup (few rows: the pivot chain sets the pace)
         a.T = 8 * win.ntot; a.wq = 8 * win.nwin; a.wstrip = 8 * win.strip;
-        static bool attrw = false;
-        if (!attrw) { constexpr int ldsw = (int)dense_panel_lds<8, 1>(); (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsw); attrw = true; }
         constexpr size_t ldsq = dense_panel_lds<8, 1>();
         hipLaunchKernelGGL((dense_panel_kernel<8, 1>), dim3((unsigned)std::max(a.T, 1)), dim3(BCR_T), ldsq, st, a);
         return;
     }
-    static const int one_row_max = [] { const char* e = getenv("NLLS_DENSE_DCH1"); return e ? atoi(e) : 256; }();   // (one round of a 256-CU chip; NLLS_DENSE_DCH1=0: two rows per workgroup everywhere, for A/B runs: 4.28 instead of 4.19 ms at 6000 dof)
     if (wide && T - 8 * (k + 1) <= one_row_max && T - 8 * (k + 1) > 0) {
-        // one X tile row per workgroup while that still fits one round of the chip: less helper work beside the pivot chain
+        // one X tile row per workgroup while that still fits one round of the chip: less helper work beside the pivot chain (two rows everywhere: 4.28 instead of 4.19 ms at 6000 dof)
         const int below = T - 8 * (k + 1);
-        static bool attr1 = false;
-        if (!attr1) { constexpr int ldsw = (int)dense_panel_lds<8, 1>(); (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsw); attr1 = true; }
         constexpr size_t lds = dense_panel_lds<8, 1>();
         hipLaunchKernelGGL((dense_panel_kernel<8, 1>), dim3((unsigned)below), dim3(BCR_T), lds, st, a);
     } else if (wide) {
         const int below = T - 8 * (k + 1), nch = below > 0 ? (below + 1) / 2 : 1;
-        static bool attr = false;
-        if (!attr) { constexpr int ldsw = (int)dense_panel_lds<8, 2>(); (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, ldsw); attr = true; }
         constexpr size_t lds = dense_panel_lds<8, 2>();
         hipLaunchKernelGGL((dense_panel_kernel<8, 2>), dim3((unsigned)nch), dim3(BCR_T), lds, st, a);
     } else {
@@ -1037,12 +1029,11 @@ __global__ __launch_bounds__(512) void dense_bwd_fused_kernel(DenseBwdArgs a) {
 #undef DBW_TILE
 #undef DBW_LOAD
 }
+constexpr size_t dense_dinv_lds = sizeof(double) * 36 * BTS;
 // Dinv: ceil(n / 128) slots of 128 x 128 doubles
 void launch_dense_bwd_fused(hipStream_t st, const double* S, const double* LiD, double* Dinv, int npad, int n, double* x, int* status) {
     const int NBB = (n + DBB - 1) / DBB; if (NBB <= 0) return;
-    static bool attr = false; constexpr int lds = (int)(sizeof(double) * 36 * BTS);
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_dinv_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-    hipLaunchKernelGGL(dense_dinv_kernel<0>, dim3((unsigned)NBB), dim3(512), lds, st, S, LiD, Dinv, x, npad, n, 0, (const double*)nullptr);
+    hipLaunchKernelGGL(dense_dinv_kernel<0>, dim3((unsigned)NBB), dim3(512), dense_dinv_lds, st, S, LiD, Dinv, x, npad, n, 0, (const double*)nullptr);
     DenseBwdArgs a{S, Dinv, x, status, npad, n, NBB};
     hipLaunchKernelGGL(dense_bwd_fused_kernel, dim3((unsigned)NBB), dim3(512), 0, st, a);
 }
@@ -1050,33 +1041,43 @@ void launch_dense_bwd_fused(hipStream_t st, const double* S, const double* LiD, 
 // tile-sparse reduced system (nlls_tsp.hip): the panels of all pivot tiles of a level; the inverses of all factored diagonal tiles
 void launch_tsp_panel(hipStream_t st, double* S, double* W, double* LiD, double* Dfac, const TspPanelJob* jobs, int njobs, int* status, int dch, const double* diag0, double relfloor, unsigned* mask) {
     if (njobs <= 0) return;
-    static bool attr = false; constexpr int lds1 = (int)dense_panel_lds<8, 1>(), lds2 = (int)dense_panel_lds<8, 2>();
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds1);
-                 (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_panel_kernel<8, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2); attr = true; }
+    constexpr size_t lds1 = dense_panel_lds<8, 1>(), lds2 = dense_panel_lds<8, 2>();
     TspPanelArgs a{S, W, LiD, Dfac, jobs, status, diag0, relfloor, mask};
-    if (relfloor > 0.0) {
-        if (dch == 2) hipLaunchKernelGGL((dense_panel_kernel<8, 2, true, true>), dim3((unsigned)njobs), dim3(BCR_T), (size_t)lds2, st, a);
-        else hipLaunchKernelGGL((dense_panel_kernel<8, 1, true, true>), dim3((unsigned)njobs), dim3(BCR_T), (size_t)lds1, st, a);
-    } else if (dch == 2) hipLaunchKernelGGL((dense_panel_kernel<8, 2, true>), dim3((unsigned)njobs), dim3(BCR_T), (size_t)lds2, st, a);
-    else hipLaunchKernelGGL((dense_panel_kernel<8, 1, true>), dim3((unsigned)njobs), dim3(BCR_T), (size_t)lds1, st, a);
+    if (!(relfloor > 0.0)) {
+        if (dch != 2) hipLaunchKernelGGL((dense_panel_kernel<8, 1, true>), dim3((unsigned)njobs), dim3(BCR_T), lds1, st, a);
+        else hipLaunchKernelGGL((dense_panel_kernel<8, 2, true>), dim3((unsigned)njobs), dim3(BCR_T), lds2, st, a);
+    } else if (dch != 2) hipLaunchKernelGGL((dense_panel_kernel<8, 1, true, true>), dim3((unsigned)njobs), dim3(BCR_T), lds1, st, a);
+    else hipLaunchKernelGGL((dense_panel_kernel<8, 2, true, true>), dim3((unsigned)njobs), dim3(BCR_T), lds2, st, a);
 }
 void launch_tsp_dinv(hipStream_t st, const double* LiD, const double* Dfac, double* Dinv, const int32_t* list, int nlist, int nt) {
     if (nlist <= 0) return;
-    static bool attr = false; constexpr int lds = (int)(sizeof(double) * 36 * BTS);
-    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_dinv_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); attr = true; }
-    hipLaunchKernelGGL(dense_dinv_kernel<2>, dim3((unsigned)nlist), dim3(512), lds, st, (const double*)nullptr, LiD, Dinv, (double*)nullptr, DBB * nt, 0, 0, Dfac, list);
+    hipLaunchKernelGGL(dense_dinv_kernel<2>, dim3((unsigned)nlist), dim3(512), dense_dinv_lds, st, (const double*)nullptr, LiD, Dinv, (double*)nullptr, DBB * nt, 0, 0, Dfac, list);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------
+// the launches above and the cyclic reduction's panel take more dynamic LDS than a kernel gets unasked (nlls_bcr.hpp)
+hipError_t grant_bcr_lds(const BcrSolver& S) {
+    hipError_t e = grant_dynamic_lds(&dense_panel_kernel<8, 1>, dense_panel_lds<8, 1>());
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_panel_kernel<8, 2>, dense_panel_lds<8, 2>());
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_panel_kernel<4, BCR_CH>, dense_panel_lds<4, BCR_CH>());      // (the odd last 64-column panel: 83 KB)
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_panel_kernel<8, 1, true>, dense_panel_lds<8, 1>());
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_panel_kernel<8, 2, true>, dense_panel_lds<8, 2>());
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_panel_kernel<8, 1, true, true>, dense_panel_lds<8, 1>());
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_panel_kernel<8, 2, true, true>, dense_panel_lds<8, 2>());
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_dinv_kernel<0>, dense_dinv_lds);
+    if (e == hipSuccess) e = grant_dynamic_lds(&dense_dinv_kernel<2>, dense_dinv_lds);
+    if (e == hipSuccess && S.ready) e = grant_dynamic_lds(&bcr_panel_kernel<true>, S.panel_lds);       // (blocks of 48 unknowns and more: 65 KB .. 106 KB)
+    if (e == hipSuccess && S.ready) e = grant_dynamic_lds(&bcr_panel_kernel<false>, S.panel_lds);
+    return e;
+}
+
 bool BcrSolver::supports(int64_t n_band, int bw, int nbd) {
     return bw >= 1 && (bw + 15) / 16 <= BCR_MAXNT && nbd <= 15 && n_band >= 1 && n_band < (int64_t)1 << 30;
 }
 
-int BcrSolver::build(int64_t n_band_, int bw_, int nbd_, int H_, std::string* err, int nt) {
+int BcrSolver::build(int64_t n_band_, int bw_, int nbd_, int H_, std::string* err, const Switches& sw, int nt) {
     release();
     n_band = (int)n_band_; bw = bw_; nbd = nbd_; H = H_;
     NT = nt > 0 ? nt : std::max(1, (bw + 15) / 16); const int b = 16 * NT; N = (n_band + b - 1) / b;
@@ -1156,14 +1157,14 @@ int BcrSolver::build(int64_t n_band_, int bw_, int nbd_, int H_, std::string* er
     }
     if (hipSuccess != ws.alloc(off) || hipSuccess != d_elim.upload(elims) || hipSuccess != d_upd.upload(upds)) { if (err) *err = "block cyclic reduction workspace alloc"; return NLLS_ERR_HIP; }
     if (hipSuccess != hipMemset(ws.p, 0, off * sizeof(double))) { if (err) *err = "workspace memset"; return NLLS_ERR_HIP; }
-    { const char* e = getenv("NLLS_BCR_LEVEL_BACKWARD"); fused_backward = !(e && e[0] == '1'); }      // A/B switch: one backward launch per level, as in round 2
+    fused_backward = !sw.bcr_level_backward;                   // (off: one backward launch per level, as in round 2)
     // (the dispatch order of workgroups is not a contract: the fused pass is taken only while ALL its workgroups are resident at once -- 23 KB of LDS
     //  and 5 wavefronts each, six per CU -- so that nothing waits on a workgroup that has not started)
     if (N > 4 * 256) fused_backward = false;
     geom.ws = ws.p;
     panel_lds = sizeof(double) * ((size_t)(ND + BCR_CH * NT) * BTS + 2 * (size_t)(NT + BCR_CH) * 16 * BP + 64 + 2 * 16 * BP + BTS + 128);
     back_lds = sizeof(double) * ((size_t)RXT * 16 + NT * 64 + 2 * NT * 16 + (size_t)NO * 256 + 256 + 16);
-    { const char* e = getenv("NLLS_BCR_CHROWS_SLOTS"); chrows_slots = e ? atoi(e) : 256; }
+    chrows_slots = sw.bcr_chrows_slots;
     launches = 1; for (auto& lv : levels) launches += 1 + (lv.nupd > 0) + (fused_backward ? 0 : 1);
     launches += fused_backward ? 1 : 0;
     {   // matrix-core instructions per solve (2048 flop each): panel kernel per workgroup + update kernel per job
@@ -1221,17 +1222,10 @@ int BcrSolver::enqueue(hipStream_t st, const double* Sb, double* xr, int* status
     // The tiles: assembled in place (Sb == nullptr: schur_gather_kernel) or converted from the band storage.  (Rounds 3-4 could skip the conversion for damped solves -- the first
     // level reading the band storage itself, NLLS_BCR_FOLD_CONVERT: measured equal, 312.5 against 313.0 us per trial; out of the library since round 5, last in the tree at 6e015b8.)
     if (Sb) hipLaunchKernelGGL(bcr_convert_kernel, dim3((unsigned)(N * per + 1)), dim3(256), 0, st, geom, Sb);
-#define BCR_NT_SWITCH(CALL) switch (NT) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; default: CALL(5); break; }
-#define BCR_FWD(n) bcr_launch_level<n>(*this, st, lv, status, pivot_floor, xr)
-    for (const BcrLevel& lv : levels) BCR_NT_SWITCH(BCR_FWD)
-#define BCR_BWD(n) bcr_launch_back<n>(*this, st, levels[li], xr, li + 1 == levels.size() ? 1 : 0, status)
-#define BCR_BWD_ALL(n) bcr_launch_back_all<n>(*this, st, xr, status)
-    if (fused_backward) { BCR_NT_SWITCH(BCR_BWD_ALL) }
-    else for (size_t li = levels.size(); li-- > 0;) BCR_NT_SWITCH(BCR_BWD)
-#undef BCR_BWD_ALL
-#undef BCR_FWD
-#undef BCR_BWD
-#undef BCR_NT_SWITCH
+    const int ntd = NT >= 1 && NT < BCR_MAXNT ? NT : BCR_MAXNT;      // (build keeps NT within 1 .. BCR_MAXNT)
+    for (const BcrLevel& lv : levels) dispatch_nt(ntd, [&](auto nt) { bcr_launch_level<nt()>(*this, st, lv, status, pivot_floor, xr); });
+    if (fused_backward) dispatch_nt(ntd, [&](auto nt) { bcr_launch_back_all<nt()>(*this, st, xr, status); });
+    else for (size_t li = levels.size(); li-- > 0;) dispatch_nt(ntd, [&](auto nt) { bcr_launch_back<nt()>(*this, st, levels[li], xr, li + 1 == levels.size() ? 1 : 0, status); });
     return hipGetLastError() == hipSuccess ? NLLS_OK : NLLS_ERR_HIP;
 }
 

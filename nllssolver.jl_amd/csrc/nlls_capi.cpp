@@ -10,8 +10,6 @@ using namespace nlls;
 namespace {
 constexpr int32_t NLLS_MAX_GRAPH_NODES = 1 << 27;      // nlls_rcm_order / nlls_nd_tiles: nodes of a reduced-system graph
 int fail(nlls_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; return code; }
-int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(ctx, e_, #expr); } while (0)
 // (every entry point launches on ctx->stream: make the context's device current first -- two contexts on different devices in one
 // process, or a caller that changed the current device, must not end up on a foreign stream)
 #define NEED_READY() do { if (!ctx) return NLLS_ERR_INVALID_ARG; if (!ctx->ready) return fail(ctx, NLLS_ERR_NOT_READY, "nlls_upload_structure has not succeeded"); (void)hipSetDevice(ctx->device); } while (0)
@@ -22,8 +20,8 @@ int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(wha
 
 // copy `count` scalars starting at `slot` to the pinned mirror and wait
 int fetch_scalars(nlls_ctx* ctx, int slot, int count) {
-    HIPCHK(hipMemcpyAsync(ctx->h_scalars + slot, ctx->scalars.p + slot, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_scalars + slot, ctx->scalars.p + slot, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
 }
 bool valid_set(int w) { return w >= 0 && w < 3; }
@@ -37,7 +35,7 @@ int ensure_grad(nlls_ctx* ctx, int level) {
 // phase events (nlls_ctx::phase_on): record event k on the stream
 void phase_mark(nlls_ctx* ctx, int k) { if (ctx->phase_on && (size_t)k < ctx->phase_ev.size()) (void)hipEventRecord(ctx->phase_ev[k], ctx->stream); }
 // is this trial matrix-free?  (nlls_ctx::mf_ok: the structure qualifies; mf_on: not switched off; the trial starts at CURRENT, one rank, no collective route)
-bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->mf_on && !ctx->lin.stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
+bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->sw.mf_on && !ctx->lin.stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
 }  // namespace
 
 extern "C" {
@@ -56,14 +54,7 @@ int nlls_ctx_create(const int32_t* device_ids, int32_t ndev, nlls_ctx** out) { N
     if (!c) return NLLS_ERR_HIP;
     c->device = dev; c->num_cus = prop.multiProcessorCount;
     { int khz = 100000; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000; c->tb_ns_per_tick = 1e6 / (double)khz; }
-    { const char* e = getenv("NLLS_NO_LOOKAHEAD_SWEEP"); if (e && e[0] == '1') c->spec_on = false; }
-    { const char* e = getenv("NLLS_MATERIALIZE"); if (e && e[0] == '1') c->mf_on = false; }
-    { const char* e = getenv("NLLS_TINY_DENSE"); if (e && e[0] == '0') c->tiny_dense_on = false; }
-    { const char* e = getenv("NLLS_POST_SPLIT"); if (e && e[0] == '1') c->post_fuse = false; }
-    { const char* e = getenv("NLLS_ELIM_SPLIT"); if (e && e[0] == '1') c->elim_split = true; }
-    { const char* e = getenv("NLLS_DENSE_STEP_BACKWARD"); if (e && e[0] == '1') c->dense_fused_bwd = false; }
-    { const char* e = getenv("NLLS_DENSE_T128_MIN"); if (e) c->dense_t128_min = atoi(e); }
-    { const char* e = getenv("NLLS_SINGLES_WAVE_MIN"); const long long v = e ? atoll(e) : 0; if (v > 0) c->singles_wave_min = (int64_t)v; }
+    read_create_env(c->sw);
     if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return NLLS_ERR_HIP; }
     c->own_stream = true;
     if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -143,8 +134,8 @@ int nlls_nd_tiles(int32_t n, int32_t nborder, const int64_t* adjptr, const int32
     for (int32_t i = 0; i < n; ++i) { if (adjptr[i + 1] < adjptr[i]) return NLLS_ERR_INVALID_ARG;
         for (int64_t q = adjptr[i]; q < adjptr[i + 1]; ++q) { if (adj[q] < 0 || adj[q] >= n || adj[q] == i) return NLLS_ERR_INVALID_ARG; a[i].push_back(adj[q]); }
         std::sort(a[i].begin(), a[i].end()); a[i].erase(std::unique(a[i].begin(), a[i].end()), a[i].end()); }
-    nlls::TspSym sym;
-    if (!nlls::tsp_symbolic(a, std::vector<int32_t>(dof, dof + n + nborder), nborder, sym)) return NLLS_ERR_INVALID_ARG;
+    nlls::TspSym sym; nlls::Switches sw; read_upload_env(sw);
+    if (!nlls::tsp_symbolic(a, std::vector<int32_t>(dof, dof + n + nborder), nborder, sym, sw)) return NLLS_ERR_INVALID_ARG;
     if (sym.nt > max_tiles || sym.ntiles_lower - sym.nt > max_rows) return NLLS_ERR_INVALID_ARG;
     for (int32_t i = 0; i < n + nborder; ++i) { tile_of[i] = sym.tile_of[i]; row_in_tile[i] = sym.row_in_tile[i]; }
     colptr[0] = 0;
@@ -157,6 +148,7 @@ int nlls_upload_structure(nlls_ctx* ctx, int64_t nvar, const int32_t* var_kind, 
     if (!ctx || nvar < 0 || ngroups < 0 || (nvar && (!var_kind || !var_dim || !blockindices)) || (ngroups && !groups)) return NLLS_ERR_INVALID_ARG;
     try {
         (void)hipSetDevice(ctx->device);
+        read_upload_env(ctx->sw);                // (the upload-time switches hold for this upload; what nlls_ctx_create read and nlls_set_option wrote stays)
         ctx->err_sub = NLLS_SUB_NONE;
         int rc = build_structure(ctx, nvar, var_kind, var_dim, blockindices, ngroups, groups, flags);
         // an eliminated block with more neighbours than the Schur kernels stage in LDS: solve the full system instead of failing
@@ -194,15 +186,15 @@ int nlls_set_variables(nlls_ctx* ctx, int32_t which, const double* packed) { NLL
     NEED_READY(); if (!valid_set(which) || !packed) return NLLS_ERR_INVALID_ARG;
     TRY(vars_written(ctx, which));
     if (which == NLLS_VARS_CURRENT) { new_starting_point(ctx); ctx->tb_prev_end = 0.0; }
-    HIPCHK(hipMemcpyAsync(vars_ptr(ctx, which), packed, sizeof(double) * ctx->info.var_storage, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(vars_ptr(ctx, which), packed, sizeof(double) * ctx->info.var_storage, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_get_variables(nlls_ctx* ctx, int32_t which, double* packed) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(which) || !packed) return NLLS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(packed, vars_ptr(ctx, which), sizeof(double) * ctx->info.var_storage, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(packed, vars_ptr(ctx, which), sizeof(double) * ctx->info.var_storage, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -214,7 +206,7 @@ int nlls_swap_variables(nlls_ctx* ctx, int32_t a, int32_t b) { NLLS_API_BEGIN
 int nlls_copy_variables(nlls_ctx* ctx, int32_t dst, int32_t src) { NLLS_API_BEGIN
     NEED_READY(); if (!valid_set(dst) || !valid_set(src)) return NLLS_ERR_INVALID_ARG;
     if (dst != src) TRY(vars_written(ctx, dst));
-    if (dst != src) HIPCHK(hipMemcpyAsync(vars_ptr(ctx, dst), vars_ptr(ctx, src), sizeof(double) * ctx->info.var_storage, hipMemcpyDeviceToDevice, ctx->stream));
+    if (dst != src) HIP_TRY(ctx, hipMemcpyAsync(vars_ptr(ctx, dst), vars_ptr(ctx, src), sizeof(double) * ctx->info.var_storage, hipMemcpyDeviceToDevice, ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -287,14 +279,14 @@ int nlls_eval_blocks(nlls_ctx* ctx, int32_t which, int32_t group, double* r_out,
     if (G.res_kind == NLLS_COST_LINEAR3 || G.res_kind == NLLS_COST_DYN_LINEAR) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_eval_blocks: a non-squared cost kind has no residual");
     if (G.ncost == 0) return NLLS_OK;
     const size_t n = (size_t)G.ncost, nr = (size_t)eval_nres(G), need = n * (nr + 3);
-    if (ctx->eval_out.n < need) HIPCHK(ctx->eval_out.alloc(need));
+    if (ctx->eval_out.n < need) HIP_TRY(ctx, ctx->eval_out.alloc(need));
     double* d_r = ctx->eval_out.p; double* d_sq = d_r + n * nr; double* d_rho = d_sq + n; double* d_w = d_rho + n;
     TRY(enqueue_eval_blocks(ctx, G, which, r_out ? d_r : nullptr, sqerr_out ? d_sq : nullptr, rho_out ? d_rho : nullptr, weight_out ? d_w : nullptr));
-    if (r_out) HIPCHK(hipMemcpyAsync(r_out, d_r, sizeof(double) * n * nr, hipMemcpyDeviceToHost, ctx->stream));
-    if (sqerr_out) HIPCHK(hipMemcpyAsync(sqerr_out, d_sq, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (rho_out) HIPCHK(hipMemcpyAsync(rho_out, d_rho, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    if (weight_out) HIPCHK(hipMemcpyAsync(weight_out, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (r_out) HIP_TRY(ctx, hipMemcpyAsync(r_out, d_r, sizeof(double) * n * nr, hipMemcpyDeviceToHost, ctx->stream));
+    if (sqerr_out) HIP_TRY(ctx, hipMemcpyAsync(sqerr_out, d_sq, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (rho_out) HIP_TRY(ctx, hipMemcpyAsync(rho_out, d_rho, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (weight_out) HIP_TRY(ctx, hipMemcpyAsync(weight_out, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -309,8 +301,8 @@ int nlls_adaptive_em(nlls_ctx* ctx, int32_t which, int64_t kernel_var, int32_t m
     if (maxiters > 0) { TRY(vars_written(ctx, which)); if (which == NLLS_VARS_CURRENT) { new_starting_point(ctx); ctx->tb_prev_end = 0.0; } }
     TRY(enqueue_adaptive_em(ctx, which, ctx->var_off[(size_t)v], maxiters));
     double st[10];
-    HIPCHK(hipMemcpyAsync(st, ctx->em_state.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(st, ctx->em_state.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (storage_out) { storage_out[0] = st[0]; storage_out[1] = st[1]; storage_out[2] = st[2]; }
     if (iters_out) *iters_out = (int32_t)st[8];
     return NLLS_OK;
@@ -335,12 +327,12 @@ int nlls_set_cost_data(nlls_ctx* ctx, int32_t group, int64_t n, const int64_t* i
             seen[(size_t)k] = 1; blocks[(size_t)i] = (uint32_t)k; } }
     if (G.ndata <= 0) return NLLS_OK;                   // (a kind without payload: nothing to write, nothing changed)
     const size_t nd = (size_t)n * (size_t)G.ndata;
-    if (ctx->upd_stage.n < nd) HIPCHK(ctx->upd_stage.alloc(nd));
-    if (index && ctx->upd_index.n < (size_t)n) HIPCHK(ctx->upd_index.alloc((size_t)n));
+    if (ctx->upd_stage.n < nd) HIP_TRY(ctx, ctx->upd_stage.alloc(nd));
+    if (index && ctx->upd_index.n < (size_t)n) HIP_TRY(ctx, ctx->upd_index.alloc((size_t)n));
     costs_changed(ctx); ctx->tb_prev_end = 0.0;
-    HIPCHK(hipMemcpyAsync(ctx->upd_stage.p, data, sizeof(double) * nd, hipMemcpyHostToDevice, ctx->stream));
-    if (index) HIPCHK(hipMemcpyAsync(ctx->upd_index.p, blocks.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));          // (the caller's buffers are read during the call only; the scatter itself is left enqueued)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_stage.p, data, sizeof(double) * nd, hipMemcpyHostToDevice, ctx->stream));
+    if (index) HIP_TRY(ctx, hipMemcpyAsync(ctx->upd_index.p, blocks.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (the caller's buffers are read during the call only; the scatter itself is left enqueued)
     return enqueue_update_scatter(ctx, G, n, index != nullptr);
     NLLS_API_END(ctx)
 }
@@ -359,15 +351,15 @@ int nlls_set_robust_params(nlls_ctx* ctx, int32_t group, const double params[4])
 
 int nlls_get_grad(nlls_ctx* ctx, double* b_out) { NLLS_API_BEGIN
     NEED_GRAD(); if (!b_out) return NLLS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(b_out, ctx->b.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(b_out, ctx->b.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_get_bsm_data(nlls_ctx* ctx, double* data_out) { NLLS_API_BEGIN
     NEED_GRAD(); if (!data_out) return NLLS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(data_out, ctx->A.p, sizeof(double) * ctx->info.nnz_data, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(data_out, ctx->A.p, sizeof(double) * ctx->info.nnz_data, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -404,10 +396,10 @@ int nlls_solve(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     const bool precompute = ctx->nranks == 1;
     if (precompute) { TRY(enqueue_post_solve(ctx, ctx->stamp_ptr())); }
     int32_t status[4] = {0, 0, 0, 0};
-    if (precompute) HIPCHK(hipMemcpyAsync(ctx->h_scalars + 1, ctx->scalars.p + 1, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->stream));   // ... and the status in [10]
-    else HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
-    if (x_out) HIPCHK(hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (precompute) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_scalars + 1, ctx->scalars.p + 1, sizeof(double) * 10, hipMemcpyDeviceToHost, ctx->stream));   // ... and the status in [10]
+    else HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
+    if (x_out) HIP_TRY(ctx, hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (precompute) { status[0] = (int32_t)ctx->h_scalars[10]; step_solved(ctx, false); }
     if (status[0] != 0) return status_error(ctx, status[0], "factorisation met a non-positive pivot");
     return NLLS_OK;
@@ -447,7 +439,7 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
         TRY(comm_gather_trial_scalars(ctx, (double)ctx->trial_seq));
         phase_mark(ctx, 5);
     } else if (ctx->tiny_dense) {
-        const bool la = ctx->spec_on && ctx->ahead.armed && from == NLLS_VARS_CURRENT;
+        const bool la = ctx->sw.spec_on && ctx->ahead.armed && from == NLLS_VARS_CURRENT;
         TRY(enqueue_tiny_dense_trial(ctx, to, from));
         if (la) TRY(enqueue_lookahead(ctx, to, 0));
         TRY(enqueue_tiny_trial_finish_pending(ctx));      // (the finishing reduction, unless the look-ahead sweep's accumulate launch took it along)
@@ -455,7 +447,7 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
     { double* st = ctx->h_scalars + 40; st[0] = st[1] = st[2] = st[3] = 0.0; }       // (the launches of this trial stamp them: device-timed buckets)
     TrialArgs t{.to = to, .from = from, .mf = mf, .mirror = ctx->h_scalars_dev}; ctx->mf_trials += mf;    // (the back-substitution launch may take the retraction with it)
     TRY(enqueue_solve(ctx, t));
-    const bool la = ctx->spec_on && ctx->ahead.armed && ctx->nranks == 1 && ctx->info.is_sparse && from == NLLS_VARS_CURRENT;
+    const bool la = ctx->sw.spec_on && ctx->ahead.armed && ctx->nranks == 1 && ctx->info.is_sparse && from == NLLS_VARS_CURRENT;
     // (matrix-free trial with a look-ahead sweep behind it: the trial's finishing workgroup rides in that sweep's launch -- nlls_sweep.hip -- unless rows have to be zeroed in between)
     t.zero_for_lookahead = la; t.defer_fin = mf && la && ctx->nzero == 0;
     drop(ctx->zero.heavy_rows); drop(ctx->fin.mf_pending);   // (left over only by a trial that failed in between)
@@ -465,8 +457,8 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
     }
     // (sparse systems: the finishing launch -- TrialArgs::mirror, or comm_gather_trial_scalars -- has written the scalars, in [10] the status, to the pinned host mirror)
     if ((!ctx->info.is_sparse && !ctx->tiny_dense) || !ctx->h_scalars_dev) {
-        HIPCHK(hipMemcpyAsync(ctx->h_scalars, ctx->scalars.p, sizeof(double) * 12, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->scalars.p, sizeof(double) * 12, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     } else {
         // spin on the sequence numbers the finishing launch publishes (a few milliseconds at most: then fall back to the synchronisation,
         // after which the values are there in any case)
@@ -479,7 +471,7 @@ int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, doubl
             if ((spin & 255) == 255) { if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(1500)) break; __builtin_ia32_pause(); }
         }
         std::atomic_thread_fence(std::memory_order_acquire);
-        if (!seen) HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (!seen) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     {   // device-timed buckets (nlls_ctx::tb_*): only a trial whose launches all stamped (the sparse single-GPU routes) counts
         const double* st = ctx->h_scalars + 40;
@@ -514,8 +506,8 @@ int nlls_trial_local(nlls_ctx* ctx, int32_t to, int32_t from, double* out) { NLL
     NEED_GRAD(); if (!valid_set(to) || !valid_set(from) || to == from) return NLLS_ERR_INVALID_ARG;
     TRY(enqueue_lm_trial_tail(ctx, TrialArgs{.to = to, .from = from, .mirror = ctx->h_scalars_dev}));     // step statistics + quadratic form + retraction in one launch, the cost sweep, one finishing launch
     if (!out) return NLLS_OK;                      // enqueue only: the eleven scalars stay on the device (reduce buffer 3) for a device-side gather
-    HIPCHK(hipMemcpyAsync(ctx->h_scalars, ctx->scalars.p, sizeof(double) * 11, hipMemcpyDeviceToHost, ctx->stream));   // [10]: the factorisation status
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->scalars.p, sizeof(double) * 11, hipMemcpyDeviceToHost, ctx->stream));   // [10]: the factorisation status
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     out[0] = ctx->h_scalars[0]; out[1] = ctx->h_scalars[8]; out[2] = ctx->h_scalars[5]; out[3] = ctx->h_scalars[1]; out[4] = ctx->h_scalars[2];
     if (ctx->nranks > 1) {
         // sharded: max|x| and |x|^2 over THIS rank's share of the step (its own eliminated blocks; rank 0 also the reduced part), and the
@@ -573,7 +565,7 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
     for (int run = 0; run < 3; ++run)
     for (int64_t i = 0; i < nsel; ++i) {
         const int dof = var_dof(ctx->var_kind[varindices[i] - 1], ctx->var_dim[varindices[i] - 1]);
-        if (run != (dof > 6 ? 2 : std::max<int64_t>(cptr[i + 1] - cptr[i], 1) >= ctx->singles_wave_min ? 1 : 0)) continue;      // (an empty list counts as one block: NLLS_SINGLES_WAVE_MIN=1 sends everything to the wavefront kernel)
+        if (run != (dof > 6 ? 2 : std::max<int64_t>(cptr[i + 1] - cptr[i], 1) >= ctx->sw.singles_wave_min ? 1 : 0)) continue;      // (an empty list counts as one block: NLLS_SINGLES_WAVE_MIN=1 sends everything to the wavefront kernel)
         int64_t mine = 0; const size_t mark = cidx.size();
         for (int64_t e = cptr[i]; e < cptr[i + 1]; ++e) {
             if (cgroup[e] < 0 || cgroup[e] >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_optimize_singles: bad cost group");
@@ -591,9 +583,9 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
         else { cidx.resize(mark); cg.resize(mark); cs.resize(mark); if (mine != 0) spread = 1.0; }
     }
     if (sharded) {          // a variable whose blocks are spread over ranks: declined everywhere (one small collective, so that no rank is left in the gather below)
-        DevBuf<double> df; HIPCHK(df.alloc(1)); HIPCHK(hipMemcpyAsync(df.p, &spread, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        DevBuf<double> df; HIP_TRY(ctx, df.alloc(1)); HIP_TRY(ctx, hipMemcpyAsync(df.p, &spread, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         TRY(comm_reduce(ctx, df.p, 1, NLLS_REDUCE_MAX));
-        HIPCHK(hipMemcpyAsync(&spread, df.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&spread, df.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (spread != 0.0) return fail(ctx, NLLS_ERR_UNSUPPORTED, "nlls_optimize_singles under nlls_set_shard: a listed variable's cost blocks are spread over ranks (only variables whose blocks one rank owns -- the eliminated ones -- are relaxed in parallel)");
     }
     const int64_t nloc = (int64_t)sel.size();
@@ -601,31 +593,31 @@ int nlls_optimize_singles(nlls_ctx* ctx, int64_t nsel, const int64_t* varindices
     for (size_t g = 0; g < ctx->groups.size(); ++g) singles_group_fill(gbuf.data() + g * singles_group_size(), ctx->groups[g]);
     DevBuf<int64_t> d_sel, d_cptr, d_iters, d_pos, d_all; DevBuf<int32_t> d_cgroup, d_cslot; DevBuf<uint32_t> d_cidx; DevBuf<unsigned char> d_groups;
     if (cidx.empty()) { cidx.push_back(0); cg.push_back(0); cs.push_back(0); }
-    if (nloc > 0) { HIPCHK(d_sel.upload(sel)); HIPCHK(d_cptr.upload(cp)); HIPCHK(d_cgroup.upload(cg)); HIPCHK(d_cslot.upload(cs)); HIPCHK(d_cidx.upload(cidx)); HIPCHK(d_iters.alloc((size_t)nloc)); }
-    HIPCHK(d_groups.upload(gbuf));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (nloc > 0) { HIP_TRY(ctx, d_sel.upload(sel)); HIP_TRY(ctx, d_cptr.upload(cp)); HIP_TRY(ctx, d_cgroup.upload(cg)); HIP_TRY(ctx, d_cslot.upload(cs)); HIP_TRY(ctx, d_cidx.upload(cidx)); HIP_TRY(ctx, d_iters.alloc((size_t)nloc)); }
+    HIP_TRY(ctx, d_groups.upload(gbuf));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     vars_written(ctx, NLLS_VARS_CURRENT, true);
     ctx->singles_thread = nrun[0]; ctx->singles_wave = nrun[1] + nrun[2];
     if (nloc > 0) TRY(enqueue_optimize_singles(ctx, nrun[0], nrun[1], nrun[2], d_sel.p, d_cptr.p, d_cgroup.p, d_cidx.p, d_cslot.p, d_groups.p, iterator, maxiters, maxfails, reldcost, absdcost, dstep, d_iters.p));
     if (!sharded) {
         std::vector<int64_t> hit((size_t)nsel);                                                                        // (unsharded: nloc == nsel, in the order of the runs)
-        if (iters_out) HIPCHK(hipMemcpyAsync(hit.data(), d_iters.p, sizeof(int64_t) * nsel, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (iters_out) HIP_TRY(ctx, hipMemcpyAsync(hit.data(), d_iters.p, sizeof(int64_t) * nsel, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (iters_out) for (int64_t i = 0; i < nsel; ++i) iters_out[pos[(size_t)i]] = hit[(size_t)i];
         return NLLS_OK;
     }
     // the gather: [storage of the variables this rank relaxed, zero elsewhere | their iteration counts at the caller's positions] summed over ranks; then every listed
     // variable's storage is taken from the sum -- exact: each entry has one non-zero contribution
-    const size_t nst = (size_t)ctx->info.var_storage; DevBuf<double> gb; HIPCHK(gb.alloc(nst + (size_t)nsel));
-    HIPCHK(hipMemsetAsync(gb.p, 0, sizeof(double) * (nst + (size_t)nsel), ctx->stream));
+    const size_t nst = (size_t)ctx->info.var_storage; DevBuf<double> gb; HIP_TRY(ctx, gb.alloc(nst + (size_t)nsel));
+    HIP_TRY(ctx, hipMemsetAsync(gb.p, 0, sizeof(double) * (nst + (size_t)nsel), ctx->stream));
     double* cur = vars_ptr(ctx, NLLS_VARS_CURRENT);
-    if (nloc > 0) { HIPCHK(d_pos.upload(pos)); TRY(enqueue_copy_var_storage(ctx, d_sel.p, nloc, cur, gb.p)); TRY(enqueue_iters_to_double(ctx, d_iters.p, d_pos.p, nloc, gb.p + nst)); }
+    if (nloc > 0) { HIP_TRY(ctx, d_pos.upload(pos)); TRY(enqueue_copy_var_storage(ctx, d_sel.p, nloc, cur, gb.p)); TRY(enqueue_iters_to_double(ctx, d_iters.p, d_pos.p, nloc, gb.p + nst)); }
     TRY(comm_reduce(ctx, gb.p, (int64_t)(nst + (size_t)nsel), NLLS_REDUCE_SUM));
-    { std::vector<int64_t> all((size_t)nsel); for (int64_t i = 0; i < nsel; ++i) all[(size_t)i] = varindices[i] - 1; HIPCHK(d_all.upload(all)); }
+    { std::vector<int64_t> all((size_t)nsel); for (int64_t i = 0; i < nsel; ++i) all[(size_t)i] = varindices[i] - 1; HIP_TRY(ctx, d_all.upload(all)); }
     TRY(enqueue_copy_var_storage(ctx, d_all.p, nsel, gb.p, cur));
     std::vector<double> hit((size_t)nsel);
-    HIPCHK(hipMemcpyAsync(hit.data(), gb.p + nst, sizeof(double) * (size_t)nsel, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(hit.data(), gb.p + nst, sizeof(double) * (size_t)nsel, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (iters_out) for (int64_t i = 0; i < nsel; ++i) iters_out[i] = (int64_t)hit[(size_t)i];
     return NLLS_OK;
 }
@@ -648,8 +640,8 @@ int nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
 int nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value) { NLLS_API_BEGIN
     if (!ctx) return NLLS_ERR_INVALID_ARG;
     switch (option) {
-    case NLLS_OPT_MATERIALIZE: ctx->mf_on = value == 0; return NLLS_OK;          // (takes effect with the next nlls_lm_trial / nlls_sweep_gradhess; what A and b hold is tracked either way)
-    case NLLS_OPT_LOOKAHEAD:   ctx->spec_on = value != 0; return NLLS_OK;
+    case NLLS_OPT_MATERIALIZE: ctx->sw.mf_on = value == 0; return NLLS_OK;          // (takes effect with the next nlls_lm_trial / nlls_sweep_gradhess; what A and b hold is tracked either way)
+    case NLLS_OPT_LOOKAHEAD:   ctx->sw.spec_on = value != 0; return NLLS_OK;
     case NLLS_OPT_PHASE_EVENTS:
         ctx->phase_on = value != 0; (void)hipSetDevice(ctx->device);
         if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(10); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
@@ -662,8 +654,8 @@ int nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value) { NLLS_API_BEG
 int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGIN
     NEED_READY(); if (!out || n < 1) return NLLS_ERR_INVALID_ARG;
     int32_t status[16] = {0};
-    HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const int64_t vals[43] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
@@ -686,15 +678,15 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
 int nlls_set_step(nlls_ctx* ctx, const double* x) { NLLS_API_BEGIN
     NEED_READY(); if (!x) return NLLS_ERR_INVALID_ARG;
     step_replaced(ctx);
-    HIPCHK(hipMemcpyAsync(ctx->x.p, x, sizeof(double) * ctx->info.ndof, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->x.p, x, sizeof(double) * ctx->info.ndof, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
 int nlls_get_step(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     NEED_READY(); if (!x_out) return NLLS_ERR_INVALID_ARG;
-    HIPCHK(hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -753,9 +745,9 @@ int nlls_solve_local(nlls_ctx* ctx) { NLLS_API_BEGIN
 int nlls_solve_finish(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     NEED_GRAD(); TRY(enqueue_solve_finish(ctx));
     int32_t status[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
-    if (x_out) HIPCHK(hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
+    if (x_out) HIP_TRY(ctx, hipMemcpyAsync(x_out, ctx->x.p, sizeof(double) * ctx->info.ndof, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (status[0] != 0) return status_error(ctx, status[0], "factorisation met a zero pivot");
     return NLLS_OK;
     NLLS_API_END(ctx)
@@ -786,7 +778,7 @@ int nlls_get_grad_owned(nlls_ctx* ctx, double* b_out) { NLLS_API_BEGIN
     TRY(nlls_get_grad(ctx, b_out));
     if (ctx->nranks > 1) {
         std::vector<double> mask((size_t)ctx->info.ndof);
-        HIPCHK(hipMemcpy(mask.data(), ctx->d_dof_mask.p, sizeof(double) * mask.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(mask.data(), ctx->d_dof_mask.p, sizeof(double) * mask.size(), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < mask.size(); ++i) if (mask[i] == 0.0) b_out[i] = 0.0;
     }
     return NLLS_OK;
@@ -803,13 +795,13 @@ int nlls_get_shard_info(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGIN
 // ---- timing helpers: HIP events on the context's stream around `reps` back-to-back enqueues -------------
 static int time_loop(nlls_ctx* ctx, int reps, float* ms_avg, int (*fn)(nlls_ctx*)) {
     if (reps < 1 || !ms_avg) return NLLS_ERR_INVALID_ARG;
-    hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    hipEvent_t e0, e1; HIP_TRY(ctx, hipEventCreate(&e0)); HIP_TRY(ctx, hipEventCreate(&e1));
     TRY(fn(ctx));   // warm-up
-    HIPCHK(hipEventRecord(e0, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
     for (int i = 0; i < reps; ++i) TRY(fn(ctx));
-    HIPCHK(hipEventRecord(e1, ctx->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(e1));
+    float ms = 0; HIP_TRY(ctx, hipEventElapsedTime(&ms, e0, e1));
     *ms_avg = ms / reps;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return NLLS_OK;
@@ -842,10 +834,10 @@ int nlls_check_analytic(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
     int64_t nb = 0; TRY(enqueue_check_analytic(ctx, nullptr, &nb));
     for (int q = 0; q < 7; ++q) out[q] = 0.0;
     if (nb == 0) return NLLS_OK;
-    nlls::DevBuf<double> d; HIPCHK(d.alloc((size_t)nb * 8));
+    nlls::DevBuf<double> d; HIP_TRY(ctx, d.alloc((size_t)nb * 8));
     TRY(enqueue_check_analytic(ctx, d.p, nullptr));
     std::vector<double> h((size_t)nb * 8);
-    HIPCHK(hipMemcpyAsync(h.data(), d.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), d.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int64_t b = 0; b < nb; ++b) for (int q = 0; q < 7; ++q) { const double v = h[(size_t)b * 8 + q]; if (!(v <= out[q])) out[q] = v; }   // (a NaN difference comes through)
     return NLLS_OK;
     NLLS_API_END(ctx)
@@ -857,10 +849,10 @@ int nlls_robustify(nlls_ctx* ctx, int32_t robust_kind, const double params[4], i
     if (n == 0) return NLLS_OK;
     (void)hipSetDevice(ctx->device);
     RobustSpec rk{}; rk.kind = robust_kind; rk.p0 = params[0]; rk.p1 = params[1]; rk.p2 = params[2];
-    nlls::DevBuf<double> d; HIPCHK(d.alloc((size_t)n * 5));
-    HIPCHK(hipMemcpyAsync(d.p, cost, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    nlls::DevBuf<double> d; HIP_TRY(ctx, d.alloc((size_t)n * 5));
+    HIP_TRY(ctx, hipMemcpyAsync(d.p, cost, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     TRY(enqueue_robustify(ctx, rk, n, d.p, d.p + n));
-    HIPCHK(hipMemcpyAsync(out, d.p + n, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream)); HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, d.p + n, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream)); HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -868,8 +860,8 @@ int nlls_flush_cache(nlls_ctx* ctx, int64_t bytes) { NLLS_API_BEGIN
     if (!ctx || bytes <= 0 || bytes > ((int64_t)8 << 30)) return NLLS_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     const size_t half = ((size_t)bytes / 2 + 255) & ~(size_t)255;
-    if (ctx->flushbuf.n < 2 * half) { HIPCHK(ctx->flushbuf.alloc(2 * half)); HIPCHK(hipMemsetAsync(ctx->flushbuf.p, 1, 2 * half, ctx->stream)); }
-    HIPCHK(hipMemcpyAsync(ctx->flushbuf.p + half, ctx->flushbuf.p, half, hipMemcpyDeviceToDevice, ctx->stream));
+    if (ctx->flushbuf.n < 2 * half) { HIP_TRY(ctx, ctx->flushbuf.alloc(2 * half)); HIP_TRY(ctx, hipMemsetAsync(ctx->flushbuf.p, 1, 2 * half, ctx->stream)); }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->flushbuf.p + half, ctx->flushbuf.p, half, hipMemcpyDeviceToDevice, ctx->stream));
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -877,7 +869,7 @@ int nlls_profile_sweep(nlls_ctx* ctx, int32_t on, float* ms_avg, float* ms_min, 
     if (!ctx) return NLLS_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
     if (ms_avg || ms_min || ms_max || nsamples) {            // read what has been recorded so far (synchronises the stream)
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const int64_t cap = (int64_t)ctx->prof_ev.size() / 2, n = std::min(ctx->prof_count, cap);
         double sum = 0; float mn = 1e30f, mx = 0.f;
         for (int64_t i = 0; i < n; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, ctx->prof_ev[2 * i], ctx->prof_ev[2 * i + 1]) != hipSuccess) continue; sum += ms; mn = std::min(mn, ms); mx = std::max(mx, ms); }
@@ -891,7 +883,7 @@ int nlls_profile_sweep(nlls_ctx* ctx, int32_t on, float* ms_avg, float* ms_min, 
             const double ms_per_tick = 1.0 / (double)khz;
             for (int64_t i = 0; i < nk; ++i) {
                 const unsigned nwg = ctx->prof_nwg[i]; if (!nwg) continue;
-                HIPCHK(hipMemcpy(h.data(), ctx->prof_clk.p + (size_t)i * 2 * PROF_MAXWG, sizeof(unsigned long long) * 2 * (size_t)nwg, hipMemcpyDeviceToHost));
+                HIP_TRY(ctx, hipMemcpy(h.data(), ctx->prof_clk.p + (size_t)i * 2 * PROF_MAXWG, sizeof(unsigned long long) * 2 * (size_t)nwg, hipMemcpyDeviceToHost));
                 unsigned long long t0 = ~0ull, t1 = 0; for (unsigned w = 0; w < nwg; ++w) { t0 = std::min(t0, h[w]); t1 = std::max(t1, h[nwg + w]); }
                 if (t1 <= t0) continue;
                 const float ms = (float)((double)(t1 - t0) * ms_per_tick); sum += ms; mn = std::min(mn, ms); mx = std::max(mx, ms); ++ok;
@@ -912,7 +904,7 @@ int nlls_profile_sweep(nlls_ctx* ctx, int32_t on, float* ms_avg, float* ms_min, 
 int nlls_profile_sweep_dispatch(nlls_ctx* ctx, float* ms_avg, float* ms_min, float* ms_max, int64_t* nsamples) { NLLS_API_BEGIN
     if (!ctx) return NLLS_ERR_INVALID_ARG;
     (void)hipSetDevice(ctx->device);
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const int64_t cap = (int64_t)ctx->prof_ev.size() / 2, n = std::min(ctx->prof_count, cap);
     double sum = 0; float mn = 1e30f, mx = 0.f; int64_t ok = 0;
     for (int64_t i = 0; i < n; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, ctx->prof_ev[2 * i], ctx->prof_ev[2 * i + 1]) != hipSuccess) { (void)hipGetLastError(); continue; } sum += ms; mn = std::min(mn, ms); mx = std::max(mx, ms); ++ok; }

@@ -9,8 +9,6 @@
 namespace nlls {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
 
 // ---------------------------------------------------------------------------------------------------
 // bordered-band LDL' + both triangular solves in ONE persistent workgroup (narrow-band reduced systems,
@@ -737,15 +735,30 @@ __global__ __launch_bounds__(256) void band_backward_tiles_kernel(BwdArgs2 args)
 }
 
 
+// dynamic LDS of the chain kernels.  NBW: tile rows below the diagonal tile that a block column reaches; nbr: border rows + the right-hand side
+static size_t blk_factor_lds(int NBW) { return sizeof(double) * ((size_t)(NBW + 2) * (NBW + 2) * 272 + 272 + 2 * (size_t)(NBW + 2) * 16 * 17 + 64 + 32 * 17 + 272 + 8); }
+static size_t blk_backward_lds(int NBW, int nbr) { return sizeof(double) * ((size_t)(BWD_RING + 1) * bwd_slot(NBW) + 384 + (size_t)nbr * nbr + nbr + 8); }
+static size_t blk_backward_sep_lds(int NBW) { return sizeof(double) * ((size_t)(BWD_RING + 1) * bwd_slot(NBW) + 384 + 16); }      // (the twisted factorisation's separator: no border)
+static bool chain_blocked(const nlls_ctx* c, int bw, int H) { const int NBW = (bw + 15) / 16; return c->band_blocked && NBW <= 5 && (NBW + 2) * 16 <= 128 && H <= 96 && blk_factor_lds(NBW) <= 160 * 1024; }
+static void band_ldlt_args(const nlls_ctx* c, int bw, BandArgs& a) { a.CH = c->band_CH; a.PFC = (bw + 1 + a.CH - 1) / a.CH + 1; a.RC = (a.PFC + 1) * a.CH; a.NSC = (bw + 1 + c->band_SEG - 1) / c->band_SEG; }
+static size_t band_ldlt_lds(const nlls_ctx* c, const BandArgs& a, int bw, int nbd, int H) { const int nbr = nbd + 1;
+    return sizeof(double) * ((size_t)a.RC * H + 2 * (size_t)(2 * a.NSC * c->band_SEG + 2 * c->band_SEG) + (size_t)(bw + 2) * nbr + (size_t)nbr * nbr + nbr + 8); }
+// the register window of band_ldlt_solve_kernel (SEG, NSLOT) among those build_schur chooses from; anything else runs as the last
+template <class F> static auto dispatch_band_window(int seg, int nseg, F&& f) {
+    if (seg == 10 && nseg == 2) return f(Const<10>{}, Const<2>{});
+    if (seg == 8 && nseg == 1) return f(Const<8>{}, Const<1>{});
+    if (seg == 12 && nseg == 2) return f(Const<12>{}, Const<2>{});
+    if (seg == 12 && nseg == 4) return f(Const<12>{}, Const<4>{});
+    return f(Const<16>{}, Const<4>{});
+}
+
 // the solve of a band in band storage (c->S: [banded part | border rows | rhs row] per column, then the border corner); the solution lands in c->s_ptr()
 int enqueue_chain_solve(nlls_ctx* c, int n_band, int bw, int nbd, int H) {
-    BandArgs a{}; a.Sb = c->S.p; a.Lb = c->Lwork.p; a.xr = c->s_ptr(); a.n_band = n_band; a.bw = bw; a.nbd = nbd; a.H = H; a.CH = c->band_CH; a.status = c->d_status.p;
-    a.PFC = (bw + 1 + a.CH - 1) / a.CH + 1; a.RC = (a.PFC + 1) * a.CH; a.NSC = (bw + 1 + c->band_SEG - 1) / c->band_SEG;
+    BandArgs a{}; a.Sb = c->S.p; a.Lb = c->Lwork.p; a.xr = c->s_ptr(); a.n_band = n_band; a.bw = bw; a.nbd = nbd; a.H = H; a.status = c->d_status.p;
+    band_ldlt_args(c, bw, a);
     const int nbr = nbd + 1;
-    const size_t lds = sizeof(double) * ((size_t)a.RC * H + 2 * (size_t)(2 * a.NSC * c->band_SEG + 2 * c->band_SEG) + (size_t)(bw + 2) * nbr + (size_t)nbr * nbr + nbr + 8);
-    const int NBW = (bw + 15) / 16;                // tile rows below the diagonal tile that a block column reaches
-    const size_t blk_lds = sizeof(double) * ((size_t)(NBW + 2) * (NBW + 2) * 272 + 272 + 2 * (size_t)(NBW + 2) * 16 * 17 + 64 + 32 * 17 + 272 + 8);
-    if (c->band_blocked && NBW <= 5 && (NBW + 2) * 16 <= 128 && H <= 96 && blk_lds <= 160 * 1024) {
+    const int NBW = (bw + 15) / 16;
+    if (chain_blocked(c, bw, H)) {
         const int nJb = (n_band + 15) / 16, fsz = blk_fsize(NBW, nbd);
         // twisted (two-sided) factorisation: two workgroups, one from each end of the band, meet at a separator of
         // ws columns, bw <= ws <= 16 NBW, so that the sides do not touch each other
@@ -759,7 +772,7 @@ int enqueue_chain_solve(nlls_ctx* c, int n_band, int bw, int nbd, int H) {
             BlkArgs& q = bkl.c[sd]; q.Sb = c->S.p; q.Lb = c->Lwork.p + (size_t)(sd ? JA : 0) * fsz; q.corner_out = corner + sd * nbr * nbr;
             q.sep_out = twisted ? (sd ? sepB : sepA) : nullptr; q.n_band = n_band; q.bw = bw; q.nbd = nbd; q.H = H; q.NBW = NBW; q.rev = sd; q.nJs = sd ? JB : JA; q.timing = 1; q.status = c->d_status.p;
         }
-        hipLaunchKernelGGL(band_blocked_factor_kernel, dim3(twisted ? 2 : 1), dim3(BLK_T), blk_lds, c->stream, bkl);
+        hipLaunchKernelGGL(band_blocked_factor_kernel, dim3(twisted ? 2 : 1), dim3(BLK_T), blk_factor_lds(NBW), c->stream, bkl);
         if (twisted) {
             // the separator: a dense ws x ws system in band layout (bandwidth ws - 1), same kernels, one workgroup
             double* Ssep = sepB + (size_t)(16 * NBW) * (16 * NBW) + 16 * NBW; double* Lsep = Ssep + (size_t)ws * (ws + 1) + 8;
@@ -767,41 +780,34 @@ int enqueue_chain_solve(nlls_ctx* c, int n_band, int bw, int nbd, int H) {
             hipLaunchKernelGGL(band_sep_combine_kernel, dim3(8), dim3(256), 0, c->stream, (const double*)c->S.p, (const double*)sepA, (const double*)sepB, cA, ws, 16 * NBW, bw, nbd, H, Ssep);
             BlkArgs2 bs{}; BlkArgs& q = bs.c[0]; q.Sb = Ssep; q.Lb = Lsep; q.corner_out = Lsep + (size_t)nJs2 * blk_fsize(NBWs, 0) + 128; q.sep_out = nullptr;
             q.n_band = ws; q.bw = ws - 1; q.nbd = 0; q.H = ws + 1; q.NBW = NBWs; q.rev = 0; q.nJs = nJs2; q.status = c->d_status.p;
-            const size_t lds_s = sizeof(double) * ((size_t)(NBWs + 2) * (NBWs + 2) * 272 + 272 + 2 * (size_t)(NBWs + 2) * 16 * 17 + 64 + 32 * 17 + 272 + 8);
-            hipLaunchKernelGGL(band_blocked_factor_kernel, dim3(1), dim3(BLK_T), lds_s, c->stream, bs);
+            hipLaunchKernelGGL(band_blocked_factor_kernel, dim3(1), dim3(BLK_T), blk_factor_lds(NBWs), c->stream, bs);
             BwdArgs2 b2{}; BwdArgs& r = b2.c[0]; r.Lt = Lsep; r.corner_in = q.corner_out; r.xr = c->s_ptr() + cA; r.n_band = ws; r.nbd = 0; r.NBW = NBWs; r.rev = 0; r.nJs = nJs2; r.xnext = -1; r.nxnext = 0; r.status = c->d_status.p;
-            const size_t lds_sb = sizeof(double) * ((size_t)(BWD_RING + 1) * bwd_slot(NBWs) + 384 + 16);
-            switch (NBWs) {
-                case 1: hipLaunchKernelGGL(band_backward_tiles_kernel<1>, dim3(1), dim3(256), lds_sb, c->stream, b2); break;
-                case 2: hipLaunchKernelGGL(band_backward_tiles_kernel<2>, dim3(1), dim3(256), lds_sb, c->stream, b2); break;
-                case 3: hipLaunchKernelGGL(band_backward_tiles_kernel<3>, dim3(1), dim3(256), lds_sb, c->stream, b2); break;
-                case 4: hipLaunchKernelGGL(band_backward_tiles_kernel<4>, dim3(1), dim3(256), lds_sb, c->stream, b2); break;
-                default: hipLaunchKernelGGL(band_backward_tiles_kernel<5>, dim3(1), dim3(256), lds_sb, c->stream, b2); break;
-            }
+            dispatch_nt(NBWs >= 1 && NBWs < 5 ? NBWs : 5, [&](auto w) { hipLaunchKernelGGL(band_backward_tiles_kernel<w()>, dim3(1), dim3(256), blk_backward_sep_lds(NBWs), c->stream, b2); });
         }
         BwdArgs2 bw2{};
         for (int sd = 0; sd < (twisted ? 2 : 1); ++sd) {
             BwdArgs& q = bw2.c[sd]; q.Lt = c->Lwork.p + (size_t)(sd ? JA : 0) * fsz; q.corner_in = corner; q.xr = c->s_ptr(); q.n_band = n_band; q.nbd = nbd; q.NBW = NBW;
             q.rev = sd; q.nJs = sd ? JB : JA; q.xnext = twisted ? (sd ? cA + ws - 1 : cA) : -1; q.nxnext = ws; q.timing = 1; q.status = c->d_status.p;
         }
-        const size_t lds_b = sizeof(double) * ((size_t)(BWD_RING + 1) * bwd_slot(NBW) + 384 + (size_t)nbr * nbr + nbr + 8);
         const dim3 gb(twisted ? 2 : 1);
-        switch (NBW) {
-            case 1: hipLaunchKernelGGL(band_backward_tiles_kernel<1>, gb, dim3(256), lds_b, c->stream, bw2); break;
-            case 2: hipLaunchKernelGGL(band_backward_tiles_kernel<2>, gb, dim3(256), lds_b, c->stream, bw2); break;
-            case 3: hipLaunchKernelGGL(band_backward_tiles_kernel<3>, gb, dim3(256), lds_b, c->stream, bw2); break;
-            case 4: hipLaunchKernelGGL(band_backward_tiles_kernel<4>, gb, dim3(256), lds_b, c->stream, bw2); break;
-            default: hipLaunchKernelGGL(band_backward_tiles_kernel<5>, gb, dim3(256), lds_b, c->stream, bw2); break;
-        }
-    } else
-#define LAUNCH_BAND(SEG, NSLOT) hipLaunchKernelGGL((band_ldlt_solve_kernel<SEG, NSLOT>), dim3(1), dim3(256), lds, c->stream, a)
-    if (c->band_SEG == 10 && c->band_NSEG == 2) LAUNCH_BAND(10, 2);
-    else if (c->band_SEG == 8 && c->band_NSEG == 1) LAUNCH_BAND(8, 1);
-    else if (c->band_SEG == 12 && c->band_NSEG == 2) LAUNCH_BAND(12, 2);
-    else if (c->band_SEG == 12 && c->band_NSEG == 4) LAUNCH_BAND(12, 4);
-    else LAUNCH_BAND(16, 4);
-#undef LAUNCH_BAND
+        dispatch_nt(NBW >= 1 && NBW < 5 ? NBW : 5, [&](auto w) { hipLaunchKernelGGL(band_backward_tiles_kernel<w()>, gb, dim3(256), blk_backward_lds(NBW, nbr), c->stream, bw2); });
+    } else dispatch_band_window(c->band_SEG, c->band_NSEG, [&](auto seg, auto nslot) {
+        hipLaunchKernelGGL((band_ldlt_solve_kernel<seg(), nslot()>), dim3(1), dim3(256), band_ldlt_lds(c, a, bw, nbd, H), c->stream, a); });
     HIPCHK(hipGetLastError());
     return NLLS_OK;
+}
+// the band solver's launches take up to 150 KB of dynamic LDS: granted for a structure whose band the chain kernels solve (SOLVE_BAND without block cyclic reduction).
+// The separator of the twisted factorisation is a narrower band through the same kernels: every instantiation up to this band's width, at the larger of its two uses
+hipError_t grant_chain_lds(const nlls_ctx* c) {
+    if (c->solve_mode != SOLVE_BAND || c->bcr.ready) return hipSuccess;
+    const int NBW = (c->bw + 15) / 16, nbr = c->nbd + 1;
+    if (!chain_blocked(c, c->bw, c->band_H)) {
+        BandArgs a{}; band_ldlt_args(c, c->bw, a);
+        return dispatch_band_window(c->band_SEG, c->band_NSEG, [&](auto seg, auto nslot) { return grant_dynamic_lds(&band_ldlt_solve_kernel<seg(), nslot()>, band_ldlt_lds(c, a, c->bw, c->nbd, c->band_H)); });
+    }
+    hipError_t e = grant_dynamic_lds(&band_blocked_factor_kernel, blk_factor_lds(NBW));
+    for (int w = 1; w <= NBW && e == hipSuccess; ++w)
+        e = dispatch_nt(w, [&](auto k) { return grant_dynamic_lds(&band_backward_tiles_kernel<k()>, std::max(blk_backward_lds(w, w == NBW ? nbr : 1), blk_backward_sep_lds(w))); }, hipSuccess);
+    return e;
 }
 }  // namespace nlls

@@ -473,18 +473,16 @@ __global__ __launch_bounds__(64) void singles_wave_kernel(const SinglesGroup* __
 // ================================================================================================
 // host-side enqueue
 // ================================================================================================
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
 
 template <int KIND>
 static int launch_cost(nlls_ctx* c, const Group& G, const double* vars, int64_t& pbase, const PostSolveArgs* post, bool* taken) {
     if (G.ncost > 0) {
-        static const int cost_grid_max = [] { const char* e = getenv("NLLS_COST_GRID_MAX"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2048; }();   // (A/B: workgroups of the cost sweep)
+        const int cost_grid_max = c->sw.cost_grid_max;   // (A/B: workgroups of the cost sweep)
         int grid = (int)std::min<int64_t>((G.ncost + TPB - 1) / TPB, cost_grid_max);
         const bool shared = G.cost_list >= 0 && c->info.is_sparse;
         const double* data = shared ? G.lists[G.cost_list].data.p : G.data.p; const uint32_t* voff = shared ? G.lists[G.cost_list].voff.p : G.voff.p;
         // (matrix-free LM trial: the blocks in elimination order are what the loop's other two launches stream -- the cost sweep reads the same 24 bytes per block)
-        if (c->mf_ok && c->mf_on && G.mf_data.p && G.mf_voff.p) { data = G.mf_data.p; voff = G.mf_voff.p; }
+        if (c->mf_ok && c->sw.mf_on && G.mf_data.p && G.mf_voff.p) { data = G.mf_data.p; voff = G.mf_voff.p; }
         if (post && taken && !*taken) {      // the first launch of the sweep takes the statistics roles along
             hipLaunchKernelGGL((cost_kernel<KIND, true>), dim3(grid + post->np + post->np3 + post->np2), dim3(TPB), 0, c->stream, vars, data, voff, (const uint32_t*)nullptr, G.ncost, G.rk, c->partials.p + pbase, grid, *post);
             *taken = true;
@@ -524,12 +522,7 @@ int enqueue_dyn_gradhess(nlls_ctx* c, const Group& G, const double* vars, int64_
 // cost blocks whose variables are all fixed: cost only (called from the gradient sweep as well)
 int enqueue_fixedcost(nlls_ctx* c, const Group& G, const double* vars, int64_t& pbase) {
     if (is_dyn_kind(G.res_kind)) return launch_dyn_cost(c, G, vars, pbase, true);
-    switch (G.res_kind) {
-#define X(K) case K: return launch_fixedcost<K>(c, G, vars, pbase);
-        NLLS_FOR_EACH_RES(X)
-#undef X
-    }
-    return NLLS_OK;
+    return dispatch_res(G.res_kind, [&](auto k) { return launch_fixedcost<k()>(c, G, vars, pbase); }, NLLS_OK);
 }
 // ---- closed forms against dual numbers (nlls_check_analytic) --------------------------------------------------------------------------------------
 // Every block of a group evaluated twice -- BlockGH<KIND, true> (a residual kind's own `jac`, the adaptive kernel's closed-form derivatives) and
@@ -571,11 +564,7 @@ int enqueue_check_analytic(nlls_ctx* c, double* d_out /* [nblocks_total][8] */, 
     for (const Group& G : c->groups) {
         if (is_dyn_kind(G.res_kind) || G.ncost == 0) continue;
         const int grid = (int)std::min<int64_t>((G.ncost + TPB - 1) / TPB, 256);
-        if (d_out) switch (G.res_kind) {
-#define X(K) case K: hipLaunchKernelGGL(check_analytic_kernel<K>, dim3(grid), dim3(TPB), 0, c->stream, vars, G.data.p, G.voff.p, G.ncost, G.rk, 1, d_out + base * 8); break;
-            NLLS_FOR_EACH_RES(X)
-#undef X
-        }
+        if (d_out) dispatch_res(G.res_kind, [&](auto k) { hipLaunchKernelGGL(check_analytic_kernel<k()>, dim3(grid), dim3(TPB), 0, c->stream, vars, G.data.p, G.voff.p, G.ncost, G.rk, 1, d_out + base * 8); });
         base += grid;
     }
     if (nblocks_out) *nblocks_out = base;
@@ -608,11 +597,7 @@ int enqueue_sweep_cost(nlls_ctx* c, int which, int64_t pofs, int64_t* count, con
     const double* vars = vars_ptr(c, which); int64_t pbase = pofs;
     for (const Group& G : c->groups) {
         if (is_dyn_kind(G.res_kind)) { launch_dyn_cost(c, G, vars, pbase, false); continue; }
-        switch (G.res_kind) {
-#define X(K) case K: launch_cost<K>(c, G, vars, pbase, post, post_taken); break;
-            NLLS_FOR_EACH_RES(X)
-#undef X
-        }
+        dispatch_res(G.res_kind, [&](auto k) { launch_cost<k()>(c, G, vars, pbase, post, post_taken); });
     }
     if (count) *count = pbase - pofs;
     else hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(TPB), 0, c->stream, c->partials.p + pofs, pbase - pofs, c->scalars.p);

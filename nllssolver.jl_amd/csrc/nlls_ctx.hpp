@@ -14,6 +14,7 @@
 #include "nlls_devbuf.hpp"
 #include "nlls_bcr.hpp"
 #include "nlls_tsp.hpp"
+#include "nlls_switches.hpp"
 
 namespace nlls {
 
@@ -216,6 +217,7 @@ struct nlls_ctx {
     bool prof_sweep = false; std::vector<hipEvent_t> prof_ev; int64_t prof_count = 0;
     hipEvent_t prof_e0 = nullptr, prof_e1 = nullptr; bool prof_taken = false;   // the event pair of the sweep being enqueued, handed to its fused / folded launch (hipExtLaunchKernelGGL)
     nlls::DevBuf<unsigned long long> prof_clk; int64_t prof_kcount = 0; unsigned prof_nwg[16] = {0};   // [PROF_SLOTS][2][PROF_MAXWG] start / end stamp of every workgroup (100 MHz constant clock) of the fused accumulate launch
+    nlls::Switches sw;                       // the environment's switches (nlls_switches.hpp): nlls_ctx_create reads its share, every upload the rest; nlls_set_option writes spec_on / mf_on
     std::string err;
     int err_sub = 0;                         // why the last nlls_upload_structure declined (NLLS_SUB_*): control flow never reads the error text
     int rank = 0, nranks = 1; bool presharded = false;
@@ -263,11 +265,10 @@ struct nlls_ctx {
     double lambda = 0.0;                     // accumulated uniformscaling! (src/iterators.jl:149,162)
     // validity state (nlls_ctx.hpp above; assigned by nlls_state.hpp alone)
     nlls::Linearisation lin; nlls::Lookahead ahead; nlls::StepState step; nlls::KnownZero zero; nlls::Deferred fin;
-    bool spec_on = true;                     // the look-ahead sweep (nlls::Lookahead): NLLS_NO_LOOKAHEAD_SWEEP unset, NLLS_OPT_LOOKAHEAD
     // the small dense system (fewer than 64 unknowns, nothing eliminated, one rank: curve fits, Rosenbrock): the sweep leaves one image of [A | b] per workgroup in
     // dense_slab and ONE gathering launch sums them (no zero fill, no atomics on HBM, no mirror launch); an LM trial is one single-workgroup launch for
-    // damping + factorisation + step statistics + retraction, then the cost sweep.  NLLS_TINY_DENSE=0 keeps the general kernels (A/B)
-    bool tiny_dense = false, tiny_dense_on = true; nlls::DevBuf<double> dense_slab; int64_t dense_slab_wgs = 0, dense_slab_used = 0;
+    // damping + factorisation + step statistics + retraction, then the cost sweep.  Switches::tiny_dense_on off keeps the general kernels (A/B)
+    bool tiny_dense = false; nlls::DevBuf<double> dense_slab; int64_t dense_slab_wgs = 0, dense_slab_used = 0;
     // Device-timed NLLSResult buckets (round 6; src/structs.jl:37-50, filled at src/iterators.jl:152,157): the launches of an LM trial leave the constant clock (100 MHz) in the pinned
     // mirror -- h_scalars[40] start of the assembly launch, [41] of the back-substitution, [42] start of the cost launch (matrix-free trial: of the finishing workgroup; the cost rides in
     // the back-substitution), [43] end of the finishing workgroup -- one thread each, off every critical path.  nlls_lm_trial turns them into nanoseconds: solver [40]..[42], cost
@@ -283,11 +284,10 @@ struct nlls_ctx {
     // two iterations shrinks to the reduced slot's pass; b's eliminated part is written by the elimination launch itself.  A.data in the reference's layout is formed on demand:
     // every entry point that reads it (nlls_get_bsm_data, nlls_solve, nlls_max_abs_diag, ...) sweeps in full first (ensure_grad level 2).  NLLS_FLAG_MATERIALIZE / NLLS_MATERIALIZE=1 /
     // nlls_set_option(NLLS_OPT_MATERIALIZE): the round-5 path.
-    bool mf_ok = false, mf_on = true; int mf_group = -1, mf_ps = -1;     // eligibility (build_mf), run-time switch, the cost group and its eliminated slot
+    bool mf_ok = false; int mf_group = -1, mf_ps = -1;     // eligibility (build_mf; the run-time switch is Switches::mf_on), the cost group and its eliminated slot
     nlls::DevBuf<double> mf_q; int mf_rows = 0;   // the back-substitution launch's rows of partials (nlls::StepState::mf)
     nlls::DevBuf<nlls::MfDesc> d_mf_desc; int64_t mf_nbig = 0; size_t mf_lds = 0; uint32_t mf_ecap = 0, mf_wsz = 0;    // per-supernode partials of the step's quadratic form; dynamic LDS of the two launches
     int64_t mf_trials = 0, mf_reduced_sweeps = 0, full_sweeps = 0;   // diagnostics (nlls_get_solve_stats [23..25])
-    int64_t singles_wave_min = 64;           // nlls_optimize_singles: cost blocks from which a variable of at most 6 dof gets a wavefront instead of a thread (NLLS_SINGLES_WAVE_MIN)
     int64_t singles_wave = 0, singles_thread = 0;   // variables of the last nlls_optimize_singles call per kernel (nlls_get_solve_stats [27], [28])
     // the branches the upload chose, reported so that a test can assert the path it was written for (nlls_get_solve_stats [29..42]; the supernode classes are the
     // n_fast_* / n_slow_* counters below).  Tiles are summed over groups and slots; sweep_fused_groups is counted by the last full accumulate sweep itself.
@@ -295,18 +295,14 @@ struct nlls_ctx {
     int64_t n_tiles_light = 0, n_tiles_image = 0, n_tiles_direct = 0, n_tiles_partial = 0, n_fold_groups = 0, sweep_fused_groups = 0;
     std::vector<int64_t> h_erow; std::vector<int64_t> h_eptr; std::vector<int64_t> h_enbr_block; std::vector<nlls::ElimDesc> h_elim_desc; std::vector<uint32_t> h_fast_voff;   // host copies kept between build_schur and build_mf
 
-    // ---- sharding ------------------------------------------------------------------------------------
+    // ---- the LM trial's fused tail ------------------------------------------------------------------
     int ps_np = 0, ps_np2 = 0;                 // partial counts of the last enqueue_post_solve (for the trial's finishing launch)
-    int dense_t128_min = 16;                   // dense LDL': 128 x 128 tiles in the trailing update only while it has at least this many 128-blocks per side (fewer: the 64 x 64 kernel fills the chip better)
-    bool dense_pad128 = false;                 // the dense layout is padded to a multiple of 128 rows (windowed and look-ahead factorisations: 128-column panels only)
-    bool dense_window = false;                 // dense LDL' restricted to the band of the (re-ordered) reduced system + the border strip: O(n w^2) instead of n^3 / 3 (build_schur decides)
-    bool dense_fused_bwd = true;               // dense LDL': the backward substitution in one launch (NLLS_DENSE_STEP_BACKWARD=1: one launch per 64-column block, for A/B runs)
     // LM trial with the retraction inside the back-substitution launch and the step statistics / quadratic form inside the cost sweep's launch
-    // (one rank, every eliminated block on the fast path, Euclidean eliminated variables): no launch of its own for them.  NLLS_POST_SPLIT=1: off (A/B)
+    // (one rank, every eliminated block on the fast path, Euclidean eliminated variables): no launch of its own for them.  Switches::post_fuse off: launches of their own (A/B)
     nlls::DevBuf<uint32_t> d_fast_voff;      // where the variable of each eliminated member is stored (elimination order)
     nlls::DevBuf<uint32_t> d_rest_var; nlls::DevBuf<int32_t> d_rest_red;   // the other variables, and where their step starts in the reduced solution (-1: fixed)
-    bool fast_all_euclid = false, post_fuse = true;
-    bool elim_split = false;                   // NLLS_ELIM_SPLIT=1: the assembly of the reduced system in three launches (A/B)
+    bool fast_all_euclid = false;
+    // ---- sharding ------------------------------------------------------------------------------------
     bool elim_selected = false;
     std::vector<int32_t> owner_of_block;
     int64_t local_ncost = 0, local_nnz_data = 0, local_ndof = 0;
@@ -317,6 +313,8 @@ struct nlls_ctx {
     nlls::DevBuf<uint8_t> d_blk_mask, d_row_mask;
     size_t s_elems = 0;                      // S occupies S.p[0, s_elems); the rhs vector s follows it (one reduce buffer)
     // ---- solve ---------------------------------------------------------------------------------------
+    bool dense_pad128 = false;                 // the dense layout is padded to a multiple of 128 rows (windowed and look-ahead factorisations: 128-column panels only)
+    bool dense_window = false;                 // dense LDL' restricted to the band of the (re-ordered) reduced system + the border strip: O(n w^2) instead of n^3 / 3 (build_schur decides)
     std::vector<uint8_t> is_elim;            // per block
     int64_t nelim = 0, nred = 0;             // blocks eliminated / dof of the reduced system
     int64_t nelim_all = 0;                   // ... eliminated over ALL ranks of a pre-sharded upload (= nelim otherwise): nothing rank-local may gate a collective or the solver choice

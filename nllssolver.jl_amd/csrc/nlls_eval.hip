@@ -164,9 +164,6 @@ __global__ __launch_bounds__(TPB) void em_finish_kernel(const double* __restrict
 // ================================================================================================
 // host-side enqueue
 // ================================================================================================
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
-
 int eval_nres(const Group& G) { return G.res_kind == NLLS_RES_DYN_LINEAR ? 1 : G.nres; }
 static int eval_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + TPB - 1) / TPB, 2048)); }
 
@@ -181,11 +178,7 @@ int enqueue_eval_blocks(nlls_ctx* c, const Group& G, int which, double* d_r, dou
     if (is_dyn_kind(G.res_kind)) {
         const int n = G.res_kind == NLLS_RES_DYN_LINEAR ? G.ndata - 1 : G.nres;
         hipLaunchKernelGGL(eval_dyn_kernel, dim3((unsigned)G.ncost), dim3(TPB), 0, c->stream, G.res_kind, n, G.ndata, vars, G.data.p, G.voff.p, G.rk, d_r, d_sq, d_rho, d_w);
-    } else switch (G.res_kind) {
-#define X(K) case K: launch_eval<K>(c, G, vars, d_r, d_sq, d_rho, d_w, SEL_ALL, nullptr, eval_grid(G.ncost)); break;
-        NLLS_FOR_EACH_RES(X)
-#undef X
-    }
+    } else dispatch_res(G.res_kind, [&](auto k) { launch_eval<k()>(c, G, vars, d_r, d_sq, d_rho, d_w, SEL_ALL, nullptr, eval_grid(G.ncost)); });
     HIPCHK(hipGetLastError());
     return NLLS_OK;
 }
@@ -204,11 +197,7 @@ int enqueue_adaptive_em(nlls_ctx* c, int which, uint32_t kvoff, int maxiters) {
     for (const Group& G : c->groups) {
         if (!G.adaptive || G.ncost == 0) continue;
         const int grid = std::min(eval_grid(G.ncost), EM_GRID_MAX);
-        switch (G.res_kind) {
-#define X(K) case K: launch_eval<K>(c, G, vars, nullptr, c->em_err.p + ebase, nullptr, nullptr, kvoff, c->em_part.p + 2 * pbase, grid); break;
-            NLLS_FOR_EACH_RES(X)
-#undef X
-        }
+        dispatch_res(G.res_kind, [&](auto k) { launch_eval<k()>(c, G, vars, nullptr, c->em_err.p + ebase, nullptr, nullptr, kvoff, c->em_part.p + 2 * pbase, grid); });
         ebase += G.ncost; pbase += grid;
     }
     hipLaunchKernelGGL(em_init_kernel, dim3(1), dim3(TPB), 0, c->stream, c->em_part.p, (int)npart, vars + kvoff, c->em_state.p);

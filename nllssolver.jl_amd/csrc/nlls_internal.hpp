@@ -9,6 +9,7 @@
 #define NLLS_FOR_EACH_RES(X) \
     X(NLLS_RES_BA_AFFINE) X(NLLS_RES_ROSENBROCK_A) X(NLLS_RES_ROSENBROCK_B) X(NLLS_RES_ROSENBROCK_2D) \
     X(NLLS_RES_CURVE_EXP4) X(NLLS_RES_ADAPTIVE_MEAN) X(NLLS_RES_BA_SO3) X(NLLS_RES_BA_SO3_ADAPTIVE) X(NLLS_RES_LINEAR3) X(NLLS_COST_LINEAR3) X(NLLS_RES_SCALE_MIX) NLLS_USER_RES(X)
+#include "nlls_launch.hpp"
 
 // Every extern "C" entry point runs between these two (nothing may throw or longjmp across the ccall boundary): a C++ exception -- std::bad_alloc of a host-side
 // work vector, above all -- becomes NLLS_ERR_HIP with the message in nlls_last_error.
@@ -142,6 +143,11 @@ int enqueue_mf_sweep_cost(nlls_ctx* c, int which);   // cost(vars[which]) summed
 int enqueue_gather(nlls_ctx* c);   // (nlls_solve.hip) schur_gather_kernel: slabs -> the block cyclic reduction's tiles
 uint32_t mf_wave_doubles(uint32_t ecap, int dp); int mf_batch_max(); int mf_elim_waves(); uint32_t mf_slab_doubles(int B, int dp, int tr);
 int build_mf(nlls_ctx* c, int32_t ngroups, const nlls_cost_group* groups, const uint64_t* bi, int32_t flags);   // (nlls_structure.cpp)
+// dynamic LDS above the default for the kernels of the structure just built, on the current device (grant_dynamic_lds; the upload calls them behind build_mf; nlls_bcr.hpp has a fifth)
+hipError_t grant_solve_lds(const nlls_ctx* c);   // (nlls_solve.hip) the generic elimination
+hipError_t grant_mf_lds(const nlls_ctx* c);      // (nlls_mf.hip) the matrix-free elimination of the group build_mf chose
+hipError_t grant_chain_lds(const nlls_ctx* c);   // (nlls_chain.hip) the chain kernels, where they solve the band
+hipError_t grant_sweep_lds(const nlls_ctx* c);   // (nlls_sweep.hip) the heavy rows of the accumulate sweep
 
 // collectives (nlls_comm.cpp)
 int comm_reduce(nlls_ctx* c, double* dev_ptr, int64_t count, int op);                 // no-op without an installed all-reduce

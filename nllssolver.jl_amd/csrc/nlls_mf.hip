@@ -315,17 +315,12 @@ __global__ __launch_bounds__(64 * MF_ENW) __attribute__((amdgpu_waves_per_eu(2, 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
-
 template <int KIND, int PS>
 static int launch_mf_elim(nlls_ctx* c, const Group& G) {
-    if constexpr (Res<KIND>::NDEPS == 2 && Res<KIND>::ADAPT == 0 && !is_cost_kind<KIND> && ResInfo<KIND>::dof(PS < 2 ? PS : 0) <= 3) {
+    if constexpr (mf_kind_ok<KIND, PS>) {
         const unsigned nsn = (unsigned)c->mf_nbig + (unsigned)((c->n_fast_groups - c->mf_nbig + MF_ENW - 1) / MF_ENW);
         MfArgs a{}; a.vars = vars_ptr(c, NLLS_VARS_CURRENT); a.odata = G.mf_data.p; a.ovoff = G.mf_voff.p; a.rk = G.rk; a.desc = c->d_mf_desc.p; a.rcflat = c->d_elim_rc.p; a.nbig = (uint32_t)c->mf_nbig; a.ntiny = (uint32_t)(c->n_fast_groups - c->mf_nbig);
         a.stamps = c->stamp_ptr(); a.Cinv = c->Cinv.p; a.b = c->b.p; a.slab = c->slab.p; a.lambda = c->lambda; a.status = c->d_status.p; a.wsz = c->mf_wsz; a.ecap = c->mf_ecap;
-        static size_t granted = 0;
-        if (c->mf_lds > 64 * 1024 && c->mf_lds > granted) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mf_elim_kernel<KIND, PS, SLayout>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->mf_lds)); granted = c->mf_lds; }
         hipLaunchKernelGGL((mf_elim_kernel<KIND, PS, SLayout>), dim3(nsn), dim3(64 * MF_ENW), c->mf_lds, c->stream, a);
         HIPCHK(hipGetLastError());
         return NLLS_OK;
@@ -337,14 +332,16 @@ int enqueue_mf_solve_local(nlls_ctx* c) {
     const int n = (int)c->nred; if (n == 0 || !c->mf_ok) return NLLS_ERR_NOT_READY;
     const Group& G = c->groups[c->mf_group];
     if (!take(c->zero.status)) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
-    int rc = NLLS_ERR_UNSUPPORTED;
-    switch (G.res_kind) {
-#define X(K) case K: rc = c->mf_ps == 0 ? launch_mf_elim<K, 0>(c, G) : launch_mf_elim<K, 1>(c, G); break;
-        NLLS_FOR_EACH_RES(X)
-#undef X
-    }
+    const int rc = dispatch_res(G.res_kind, [&](auto k) { return c->mf_ps == 0 ? launch_mf_elim<k(), 0>(c, G) : launch_mf_elim<k(), 1>(c, G); }, NLLS_ERR_UNSUPPORTED);
     if (rc != NLLS_OK) return rc;
     return enqueue_gather(c);
+}
+// the elimination launch takes up to gfx950's 160 KB: the one instantiation that the group and slot of build_mf select
+template <int KIND, int PS>
+static hipError_t grant_mf_elim(size_t lds) { if constexpr (mf_kind_ok<KIND, PS>) return grant_dynamic_lds(&mf_elim_kernel<KIND, PS, SLayout>, lds); else return hipSuccess; }
+hipError_t grant_mf_lds(const nlls_ctx* c) {
+    if (!c->mf_ok) return hipSuccess;
+    return dispatch_res(c->groups[c->mf_group].res_kind, [&](auto k) { return c->mf_ps == 0 ? grant_mf_elim<k(), 0>(c->mf_lds) : grant_mf_elim<k(), 1>(c->mf_lds); }, hipSuccess);
 }
 // (nlls_structure.cpp sizes the launches' LDS with this)
 uint32_t mf_wave_doubles(uint32_t ecap, int dp) { return mf_wave_lds(ecap, dp); }

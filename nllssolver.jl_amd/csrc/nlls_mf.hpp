@@ -11,6 +11,8 @@ constexpr int MF_ENW = 2;           // wavefronts per supernode of the eliminati
 constexpr int MF_BMAX = 8;          // members per batch at most (one lane per cost block: 64 / blocks per member, capped)
 constexpr int MF_TRMAX = 5;         // tile rows of [E | b]: nd + 1 <= 80
 constexpr int MF_SLOTS = 40;        // members one wavefront handles at most (128 members per supernode)
+// the kinds the trial's kernels are instantiated for (build_mf admits no other): two slots, not adaptive, a residual, at most three unknowns in the eliminated slot PS
+template <int KIND, int PS> constexpr bool mf_kind_ok = Res<KIND>::NDEPS == 2 && Res<KIND>::ADAPT == 0 && !is_cost_kind<KIND> && ResInfo<KIND>::dof(PS < 2 ? PS : 0) <= 3;
 // one supernode of the matrix-free trial, in launch order (nlls_ctx::d_mf_desc): everything a workgroup needs to start on it comes with one uniform load
 // (struct MfDesc: nlls_ctx.hpp -- v0, nmem, nd, rc_off, eb0, obs0, B = members per batch)
 

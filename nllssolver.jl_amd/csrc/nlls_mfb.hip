@@ -262,12 +262,9 @@ __global__ __launch_bounds__(256) void mf_trial_finish_kernel(MfFin fin, MfZero 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
-
 template <int KIND, int PS>
 static int launch_mf_backsub(nlls_ctx* c, const Group& G, const BsfRetract& rt, int write_red, double* zptr, int64_t zcount, unsigned nextra, unsigned nrestwg) {
-    if constexpr (Res<KIND>::NDEPS == 2 && Res<KIND>::ADAPT == 0 && !is_cost_kind<KIND> && ResInfo<KIND>::dof(PS < 2 ? PS : 0) <= 3) {
+    if constexpr (mf_kind_ok<KIND, PS>) {
         MfBackArgs a{}; a.vars = vars_ptr(c, NLLS_VARS_CURRENT); a.odata = G.mf_data.p; a.ovoff = G.mf_voff.p; a.rk = G.rk; a.desc = c->d_mf_desc.p; a.rcflat = c->d_elim_rc.p;
         a.Cinv = c->Cinv.p; a.b = c->b.p; a.xr = c->s_ptr(); a.x = c->x.p; a.part = c->mf_q.p; a.ngroups = (uint32_t)c->n_fast_groups; a.red_boff = c->d_red_boff.p; a.nred = (int)c->nred; a.write_red = write_red;
         a.Szero = zptr; a.nzero = zcount; a.nextra = nextra; a.rt = rt; a.stamps = c->stamp_ptr();
@@ -278,22 +275,19 @@ static int launch_mf_backsub(nlls_ctx* c, const Group& G, const BsfRetract& rt, 
         if ((size_t)grid * MF_PW > c->mf_q.n) { c->err = "matrix-free trial: partials buffer too small"; return NLLS_ERR_HIP; }
         c->mf_rows = (int)grid;
         hipLaunchKernelGGL((mf_backsub_kernel<KIND, PS>), dim3(grid), dim3(64 * MF_NW), 0, c->stream, a);
+        HIPCHK(hipGetLastError());
         if constexpr (!mf_fuses_cost<KIND, PS>) {      // (the trial point is in memory now: its cost by the same lanes and sums, into column 1 of the supernodes' rows)
             MfCostArgs ca{rt.vto, G.mf_data.p, G.mf_voff.p, G.rk, c->d_mf_desc.p, c->mf_q.p, 0};
             hipLaunchKernelGGL((mf_cost_kernel<KIND, PS>), dim3((unsigned)c->n_fast_groups), dim3(64 * MF_NW), 0, c->stream, ca);
+            HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipGetLastError());
         return NLLS_OK;
     } else { c->err = "matrix-free trial: kind not eligible"; return NLLS_ERR_UNSUPPORTED; }
 }
 int enqueue_mf_backsub(nlls_ctx* c, const BsfRetract& rt, int write_red, double* zptr, int64_t zcount, unsigned nextra, unsigned nrestwg) {
     const Group& G = c->groups[c->mf_group];
-    switch (G.res_kind) {
-#define X(K) case K: return c->mf_ps == 0 ? launch_mf_backsub<K, 0>(c, G, rt, write_red, zptr, zcount, nextra, nrestwg) : launch_mf_backsub<K, 1>(c, G, rt, write_red, zptr, zcount, nextra, nrestwg);
-        NLLS_FOR_EACH_RES(X)
-#undef X
-    }
-    return NLLS_ERR_UNSUPPORTED;
+    return dispatch_res(G.res_kind, [&](auto k) { return c->mf_ps == 0 ? launch_mf_backsub<k(), 0>(c, G, rt, write_red, zptr, zcount, nextra, nrestwg)
+                                                                       : launch_mf_backsub<k(), 1>(c, G, rt, write_red, zptr, zcount, nextra, nrestwg); }, NLLS_ERR_UNSUPPORTED);
 }
 // the end of the trial whose back-substitution launch has left the rows of partials (nlls_ctx::mf_rows): one finishing workgroup, nothing else -- as a launch of its own, or
 // (TrialArgs::defer_fin) as the first workgroup of the look-ahead sweep's launch behind it (nlls_sweep.hip takes it along: nlls::Deferred::mf_pending)
@@ -314,9 +308,10 @@ int enqueue_mf_trial_finish_now(nlls_ctx* c, const TrialArgs& t) {
 // cost(vars[which]) of a problem the matrix-free trial applies to: the trial's own sum (scalars[0])
 template <int KIND, int PS>
 static int launch_mf_cost(nlls_ctx* c, const Group& G, int which) {
-    if constexpr (Res<KIND>::NDEPS == 2 && Res<KIND>::ADAPT == 0 && !is_cost_kind<KIND> && ResInfo<KIND>::dof(PS < 2 ? PS : 0) <= 3) {
+    if constexpr (mf_kind_ok<KIND, PS>) {
         MfCostArgs ca{vars_ptr(c, which), G.mf_data.p, G.mf_voff.p, G.rk, c->d_mf_desc.p, c->mf_q.p, 1};
         hipLaunchKernelGGL((mf_cost_kernel<KIND, PS>), dim3((unsigned)c->n_fast_groups), dim3(64 * MF_NW), 0, c->stream, ca);
+        HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(mf_cost_reduce_kernel, dim3(1), dim3(256), 0, c->stream, c->mf_q.p, (int)c->n_fast_groups, c->scalars.p);
         HIPCHK(hipGetLastError());
         return NLLS_OK;
@@ -325,12 +320,7 @@ static int launch_mf_cost(nlls_ctx* c, const Group& G, int which) {
 int enqueue_mf_sweep_cost(nlls_ctx* c, int which) {
     const Group& G = c->groups[c->mf_group];
     drop(c->step.mf);                         // (its rows of mf_q overwrite the last trial's: that trial's tail is no longer there to be finished)
-    switch (G.res_kind) {
-#define X(K) case K: return c->mf_ps == 0 ? launch_mf_cost<K, 0>(c, G, which) : launch_mf_cost<K, 1>(c, G, which);
-        NLLS_FOR_EACH_RES(X)
-#undef X
-    }
-    return NLLS_ERR_UNSUPPORTED;
+    return dispatch_res(G.res_kind, [&](auto k) { return c->mf_ps == 0 ? launch_mf_cost<k(), 0>(c, G, which) : launch_mf_cost<k(), 1>(c, G, which); }, NLLS_ERR_UNSUPPORTED);
 }
 size_t mf_part_doubles(int64_t nsupernodes, int64_t nrest_wg_max) { return (size_t)(nsupernodes + nrest_wg_max + 64 + 32 + 8) * MF_PW; }
 

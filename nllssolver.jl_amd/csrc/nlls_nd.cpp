@@ -19,11 +19,11 @@ struct Dissector {
     const std::vector<std::vector<int32_t>>& adj; const std::vector<int32_t>& dof;
     std::vector<int32_t> stamp, lev, q;
     int32_t cur = 0;
-    int64_t leaf_dof = [] { const char* e = getenv("NLLS_TSP_LEAF"); const int v = e ? atoi(e) : 0; return (int64_t)(v > 0 ? v : 2 * TSP_TR); }();   // parts up to here are not cut further (A/B: NLLS_TSP_LEAF=<unknowns>)
+    int64_t leaf_dof;                                  // parts up to here are not cut further (Switches::tsp_leaf)
     std::vector<std::vector<int32_t>> supernodes;      // in elimination order: parts before their separator
     std::vector<int32_t> parent;                       // the separator a part hangs under (-1: none)
     int32_t emit(std::vector<int32_t>&& nodes) { supernodes.push_back(std::move(nodes)); parent.push_back(-1); return (int32_t)supernodes.size() - 1; }
-    Dissector(const std::vector<std::vector<int32_t>>& a, const std::vector<int32_t>& d) : adj(a), dof(d), stamp(a.size(), 0), lev(a.size(), -1) {}
+    Dissector(const std::vector<std::vector<int32_t>>& a, const std::vector<int32_t>& d, int leaf) : adj(a), dof(d), stamp(a.size(), 0), lev(a.size(), -1), leaf_dof(leaf) {}
     int64_t dofsum(const std::vector<int32_t>& nodes) const { int64_t s = 0; for (int32_t v : nodes) s += dof[v]; return s; }
     // breadth-first level structure from r among the nodes stamped id; q = visiting order; returns the eccentricity
     int32_t bfs(int32_t r, int32_t id) {
@@ -90,7 +90,8 @@ struct Dissector {
 
 }  // namespace
 
-bool tsp_symbolic(const std::vector<std::vector<int32_t>>& adj, const std::vector<int32_t>& dof, int nborder, TspSym& out) {
+static_assert(Switches{}.tsp_leaf == 2 * TSP_TR, "the default leaf is two tiles");
+bool tsp_symbolic(const std::vector<std::vector<int32_t>>& adj, const std::vector<int32_t>& dof, int nborder, TspSym& out, const Switches& sw) {
     const int32_t n = (int32_t)adj.size(); const int32_t nall = n + nborder;
     if ((int32_t)dof.size() != nall) return false;
     for (int32_t d : dof) if (d < 1 || d > TSP_TR) return false;
@@ -105,13 +106,13 @@ bool tsp_symbolic(const std::vector<std::vector<int32_t>>& adj, const std::vecto
     std::vector<std::vector<int32_t>> adj_nohub;
     if (!hubs.empty()) { adj_nohub.resize(n); for (int32_t v = 0; v < n; ++v) if (!hub[v]) for (int32_t w : adj[v]) if (!hub[w]) adj_nohub[v].push_back(w); }
     const std::vector<std::vector<int32_t>>& G = hubs.empty() ? adj : adj_nohub;
-    Dissector D(G, dof);
+    Dissector D(G, dof, sw.tsp_leaf);
     { std::vector<int32_t> all; all.reserve(n); for (int32_t v = 0; v < n; ++v) if (!hub[v]) all.push_back(v); D.run(std::move(all), 0); }
     // supernodes -> tiles.  A supernode starts a tile of its own (a tile that mixed two sibling parts would chain their subtrees) -- but the nodes of its LAST,
     // poorly filled tile move up into the first tile of the separator it hangs under (they are eliminated with that front instead: any order is a valid
     // one, and a tile shared by a separator and the tails of its own parts chains nothing that was not chained already).  Without this 30 % of all tile rows
     // are padding -- 2.9 x the tile products of full tiles.
-    const int carry_max = [] { const char* e = getenv("NLLS_TSP_CARRY"); return e ? atoi(e) : 80; }();      // rows of a last tile up to which it is carried up (0: never)
+    const int carry_max = sw.tsp_carry;      // rows of a last tile up to which it is carried up (0: never)
     std::vector<std::vector<int32_t>> carried(D.supernodes.size());
     for (size_t si = 0; si < D.supernodes.size(); ++si) {
         std::vector<int32_t> sn = std::move(carried[si]); sn.insert(sn.end(), D.supernodes[si].begin(), D.supernodes[si].end());

@@ -1316,8 +1316,7 @@ __global__ __launch_bounds__(256) void schur_gather_kernel(GatherArgs a) {
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
+static int dv_or_1(int dv) { return dv == 2 || dv == 3 ? dv : 1; }      // where every fast_dv but 2 and 3 launches the one-unknown instantiation
 
 int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot) {
     int np = 0;
@@ -1329,10 +1328,9 @@ int enqueue_quadform(nlls_ctx* c, const double* d_vec, int out_slot) {
                            reuse ? c->d_blk_slowmask.p : (c->nranks > 1 ? c->d_blk_mask.p : (const uint8_t*)nullptr), c->partials.p);
         if (reuse) {
             const int np3 = (int)std::max<int64_t>(1, std::min<int64_t>((c->n_fast_members + 255) / 256, 256));
-#define LAUNCH_QP(DV) hipLaunchKernelGGL((quadform_points_kernel<DV>), dim3(np3), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_fast_members.p, \
-                c->n_fast_members, c->tE.p, d_vec, c->partials.p + np)
-            if (c->fast_dv == 3) LAUNCH_QP(3); else if (c->fast_dv == 2) LAUNCH_QP(2); else LAUNCH_QP(1);
-#undef LAUNCH_QP
+            dispatch_dv(dv_or_1(c->fast_dv), [&](auto dv) {
+                hipLaunchKernelGGL((quadform_points_kernel<dv()>), dim3(np3), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_fast_members.p,
+                                   c->n_fast_members, c->tE.p, d_vec, c->partials.p + np); });
             np += np3;
         }
     } else {
@@ -1382,9 +1380,7 @@ int enqueue_post_solve(nlls_ctx* c, double* stamps, int retract_to, int retract_
     }
     PostSolveArgs a = post_solve_args(c, retract_to, retract_from, stamps);
     const dim3 grid((unsigned)(a.np + a.np3 + a.np2 + a.nretract));
-    if (c->fast_dv == 3) hipLaunchKernelGGL((post_solve_kernel<3>), grid, dim3(256), 0, c->stream, a);
-    else if (c->fast_dv == 2) hipLaunchKernelGGL((post_solve_kernel<2>), grid, dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL((post_solve_kernel<1>), grid, dim3(256), 0, c->stream, a);
+    dispatch_dv(dv_or_1(c->fast_dv), [&](auto dv) { hipLaunchKernelGGL((post_solve_kernel<dv()>), grid, dim3(256), 0, c->stream, a); });
     if (finish) hipLaunchKernelGGL(post_solve_finish_kernel, dim3(1), dim3(256), 0, c->stream, c->partials.p, a.np + a.np3, a.part2, a.np2, c->lambda, c->scalars.p, c->d_status.p);
     HIPCHK(hipGetLastError());
     return NLLS_OK;
@@ -1440,25 +1436,23 @@ static int enqueue_solve_local_t(nlls_ctx* c, bool mf) {
         // slab + gather assembly (deterministic): (C_v + lambda I)^-1, the supernodes' shares into their slabs, one gather into the tiles
         const int64_t nel = (int64_t)c->d_elim_diag.n;
         const int64_t n60 = c->n_slab60, nnar = c->n_slabnar, nwid = c->n_slabwide;    // (small supernodes are not here: the gather forms their shares itself)
-#define LAUNCH_SLAB(DV) do { \
-            hipLaunchKernelGGL((schur_cinv_kernel<DV>), dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_dim.p, nel, c->lambda, c->Cinv.p, c->d_status.p); \
-            if (n60 > 0) hipLaunchKernelGGL((schur_elim_wave_kernel<DV, 1, 2>), dim3((unsigned)n60), dim3(64 * ELIM_NW), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_ptr.p, c->d_elim_nbr.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_group.p, c->d_slab_groups.p, c->Cinv.p, c->slab.p, c->d_slab_off.p); \
-            if (nnar > 0) hipLaunchKernelGGL((schur_elim_wave_kernel<DV, 1, 3>), dim3((unsigned)nnar), dim3(64 * ELIM_NW), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_ptr.p, c->d_elim_nbr.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_group.p, c->d_slab_groups.p + n60, c->Cinv.p, c->slab.p, c->d_slab_off.p + n60); \
-            if (nwid > 0) hipLaunchKernelGGL((schur_elim_wave_kernel<DV, 2, 3>), dim3((unsigned)nwid), dim3(64 * ELIM_NW), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_ptr.p, c->d_elim_nbr.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_group.p, c->d_slab_groups.p + n60 + nnar, c->Cinv.p, c->slab.p, c->d_slab_off.p + n60 + nnar); } while (0)
         // (the status reset rides in the gather launch; schur_cinv_kernel may flag a bad pivot before it: reset first)
         HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
-        if (c->fast_dv == 3) LAUNCH_SLAB(3); else if (c->fast_dv == 2) LAUNCH_SLAB(2); else LAUNCH_SLAB(1);
-#undef LAUNCH_SLAB
+        dispatch_dv(dv_or_1(c->fast_dv), [&](auto dv) { constexpr int DV = dv();
+            hipLaunchKernelGGL((schur_cinv_kernel<DV>), dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_dim.p, nel, c->lambda, c->Cinv.p, c->d_status.p);
+            if (n60 > 0) hipLaunchKernelGGL((schur_elim_wave_kernel<DV, 1, 2>), dim3((unsigned)n60), dim3(64 * ELIM_NW), 0, c->stream, c->A.p, c->b.p,
+                c->d_elim_ptr.p, c->d_elim_nbr.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_group.p, c->d_slab_groups.p, c->Cinv.p, c->slab.p, c->d_slab_off.p);
+            if (nnar > 0) hipLaunchKernelGGL((schur_elim_wave_kernel<DV, 1, 3>), dim3((unsigned)nnar), dim3(64 * ELIM_NW), 0, c->stream, c->A.p, c->b.p,
+                c->d_elim_ptr.p, c->d_elim_nbr.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_group.p, c->d_slab_groups.p + n60, c->Cinv.p, c->slab.p, c->d_slab_off.p + n60);
+            if (nwid > 0) hipLaunchKernelGGL((schur_elim_wave_kernel<DV, 2, 3>), dim3((unsigned)nwid), dim3(64 * ELIM_NW), 0, c->stream, c->A.p, c->b.p,
+                c->d_elim_ptr.p, c->d_elim_nbr.p, c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_group.p, c->d_slab_groups.p + n60 + nnar, c->Cinv.p, c->slab.p, c->d_slab_off.p + n60 + nnar); });
         return enqueue_gather(c);
     }
     const bool one_prepare = lead && c->info.is_sparse && c->ncopy > 0;      // status reset, s and the reduced-reduced blocks in one launch
     // ONE launch for the whole assembly (schur_elim_all_kernel): every eliminated block on the fast path with both kinds of supernode present, one rank,
-    // [S | s] carrying the right-hand side as a row (band / dense layouts).  NLLS_ELIM_SPLIT=1 keeps the three launches (A/B).
+    // [S | s] carrying the right-hand side as a row (band / dense layouts).  Switches::elim_split keeps the three launches (A/B).
     const int64_t nfast_narrow = c->n_fast_narrow, nfast_wide = c->n_fast_groups - c->n_fast_narrow;
-    const bool all_in_one = one_prepare && !c->elim_split && c->nranks == 1 && c->n_slow_groups == 0 && nfast_narrow > 0 && nfast_wide > 0 &&
+    const bool all_in_one = one_prepare && !c->sw.elim_split && c->nranks == 1 && c->n_slow_groups == 0 && nfast_narrow > 0 && nfast_wide > 0 &&
                             c->solve_mode != SOLVE_SMALL && c->fast_dv >= 1 && c->fast_dv <= 3 && (int64_t)c->d_elim_diag.n == c->n_fast_members;
     if (all_in_one) {
         if (!take(c->zero.status)) HIPCHK(hipMemsetAsync(c->d_status.p, 0, sizeof(int32_t) * 5, c->stream));
@@ -1466,9 +1460,8 @@ static int enqueue_solve_local_t(nlls_ctx* c, bool mf) {
         const int ninit = (std::max(npad, n) + 255) / 256;
         PrepArgs pa{c->d_red_boff.p, c->d_copy.p, c->lambda, ninit, (uint32_t)c->n_fast_groups, c->d_status.p, c->stamp_ptr()};
         const dim3 grid((unsigned)(c->n_fast_groups + ninit + c->ncopy));
-#define LAUNCH_ALL(DV) hipLaunchKernelGGL((schur_elim_all_kernel<DV, LAY>), grid, dim3(256), 0, c->stream, c->A.p, c->b.p, c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr(), (uint32_t)nfast_narrow, pa)
-        if (c->fast_dv == 3) LAUNCH_ALL(3); else if (c->fast_dv == 2) LAUNCH_ALL(2); else LAUNCH_ALL(1);
-#undef LAUNCH_ALL
+        dispatch_dv(c->fast_dv, [&](auto dv) {      // (all_in_one: fast_dv is 1 .. 3)
+            hipLaunchKernelGGL((schur_elim_all_kernel<dv(), LAY>), grid, dim3(256), 0, c->stream, c->A.p, c->b.p, c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr(), (uint32_t)nfast_narrow, pa); });
         HIPCHK(hipGetLastError());
         return NLLS_OK;
     }
@@ -1491,34 +1484,35 @@ static int enqueue_solve_local_t(nlls_ctx* c, bool mf) {
     }
     if (c->nelim_groups > 0) {
         if (c->n_slow_groups > 0) {
-            // (more than 64 KB of dynamic LDS has to be asked for once per process)
-            static size_t lds_granted = 0; const size_t want = std::max(c->elim_lds_acc, c->elim_lds_noacc);
-            if (want > lds_granted) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&schur_elim_kernel<LAY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want)); lds_granted = want; }
             const int64_t nacc = c->n_slow_acc, nno = c->n_slow_groups - nacc;
             if (nacc > 0) hipLaunchKernelGGL(schur_elim_kernel<LAY>, dim3((unsigned)nacc), dim3(64), c->elim_lds_acc, c->stream, c->A.p, c->b.p, c->d_elim_ptr.p, c->d_elim_nbr.p,
                                c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_dim.p, c->d_elim_group.p, c->d_slow_groups.p, c->lambda, c->max_elim_dim, c->slow_nd_acc, 1, L, c->s_ptr(), c->d_status.p);
             if (nno > 0) hipLaunchKernelGGL(schur_elim_kernel<LAY>, dim3((unsigned)nno), dim3(64), c->elim_lds_noacc, c->stream, c->A.p, c->b.p, c->d_elim_ptr.p, c->d_elim_nbr.p,
                                c->d_elim_diag.p, c->d_elim_boff.p, c->d_elim_dim.p, c->d_elim_group.p, c->d_slow_groups.p + nacc, c->lambda, c->max_elim_dim, c->slow_nd_noacc, 0, L, c->s_ptr(), c->d_status.p);
         }
-#define LAUNCH_TILED(DV) do { const int64_t nel = (int64_t)c->d_elim_diag.n; \
-            hipLaunchKernelGGL((schur_cinv_kernel<DV>), dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_dim.p, nel, c->lambda, c->Cinv.p, c->d_status.p); \
-            const int64_t nnar = c->n_fast_narrow, nwid = c->n_fast_groups - c->n_fast_narrow;   /* d_fast_groups: the narrow supernodes, then the wide ones */ \
-            if (nnar > 0 && nwid > 0) { hipLaunchKernelGGL((schur_elim_fused_kernel<DV, LAY>), dim3((unsigned)(nnar + nwid)), dim3(256), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr(), (uint32_t)nnar); break; } \
-            if (nnar > 0) hipLaunchKernelGGL((schur_elim_mfma_kernel<DV, LAY>), dim3((unsigned)nnar), dim3(64 * ELIM_MFMA_NW), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); \
-            if (nwid > 0) hipLaunchKernelGGL((schur_elim_tiled_kernel<DV, 2, 3, LAY>), dim3((unsigned)nwid), dim3(256), 0, c->stream, c->A.p, c->b.p, \
-                c->d_elim_desc.p + c->n_fast_narrow, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); } while (0)
-        if (c->n_fast_groups > 0) {
-            if (c->fast_dv == 3) LAUNCH_TILED(3); else if (c->fast_dv == 2) LAUNCH_TILED(2); else if (c->fast_dv == 1) LAUNCH_TILED(1);
-        }
-#undef LAUNCH_TILED
+        if (c->n_fast_groups > 0) dispatch_dv(c->fast_dv, [&](auto dv) { constexpr int DV = dv();      // (any other fast_dv: nothing)
+            const int64_t nel = (int64_t)c->d_elim_diag.n;
+            hipLaunchKernelGGL((schur_cinv_kernel<DV>), dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, c->stream, c->A.p, c->d_elim_diag.p, c->d_elim_dim.p, nel, c->lambda, c->Cinv.p, c->d_status.p);
+            const int64_t nnar = c->n_fast_narrow, nwid = c->n_fast_groups - c->n_fast_narrow;   // d_fast_groups: the narrow supernodes, then the wide ones
+            if (nnar > 0 && nwid > 0) { hipLaunchKernelGGL((schur_elim_fused_kernel<DV, LAY>), dim3((unsigned)(nnar + nwid)), dim3(256), 0, c->stream, c->A.p, c->b.p,
+                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr(), (uint32_t)nnar); return; }
+            if (nnar > 0) hipLaunchKernelGGL((schur_elim_mfma_kernel<DV, LAY>), dim3((unsigned)nnar), dim3(64 * ELIM_MFMA_NW), 0, c->stream, c->A.p, c->b.p,
+                c->d_elim_desc.p, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr());
+            if (nwid > 0) hipLaunchKernelGGL((schur_elim_tiled_kernel<DV, 2, 3, LAY>), dim3((unsigned)nwid), dim3(256), 0, c->stream, c->A.p, c->b.p,
+                c->d_elim_desc.p + c->n_fast_narrow, c->d_elim_rc.p, c->Cinv.p, L, c->s_ptr()); });
     }
     HIPCHK(hipGetLastError());
     return NLLS_OK;
 }
 
 int enqueue_solve_local(nlls_ctx* c, bool mf) { return c->solve_mode == SOLVE_TSPARSE ? enqueue_solve_local_t<true>(c, mf) : enqueue_solve_local_t<false>(c, mf); }
+// the generic elimination's launches take the LDS their class's widest supernode needs (up to gfx950's 160 KB): the larger of the two classes, for the layout this structure launches
+template <bool TSP> static hipError_t grant_elim_lds(size_t want) { return grant_dynamic_lds(&schur_elim_kernel<SLayoutT<TSP>>, want); }
+hipError_t grant_solve_lds(const nlls_ctx* c) {
+    if (c->n_slow_groups <= 0) return hipSuccess;
+    const size_t want = std::max(c->elim_lds_acc, c->elim_lds_noacc);
+    return c->solve_mode == SOLVE_TSPARSE ? grant_elim_lds<true>(want) : grant_elim_lds<false>(want);
+}
 
 // the reduced system itself: factorisation + both substitutions; its solution lands in s (c->s_ptr())
 int enqueue_reduced_solve(nlls_ctx* c, bool mf) {
@@ -1529,7 +1523,7 @@ int enqueue_reduced_solve(nlls_ctx* c, bool mf) {
         hipLaunchKernelGGL(small_solve_kernel, dim3(1), dim3(64), 0, c->stream, c->S.p, c->s_ptr(), n, npad, c->d_status.p);
     } else if (c->solve_mode == SOLVE_TSPARSE) {
         // (an undamped step of a gauge-free problem: vanished pivots are dropped and counted, the band solver's rule -- see below)
-        if (c->tsp.enqueue(c->stream, c->S.p, c->s_ptr(), c->d_status.p, c->lambda == 0.0 ? 1e-11 : c->damped_floor) != NLLS_OK) return herr(c, hipGetLastError(), "tile-sparse reduced solve launch");
+        if (c->tsp.enqueue(c->stream, c->S.p, c->s_ptr(), c->d_status.p, c->lambda == 0.0 ? 1e-11 : c->damped_floor) != NLLS_OK) return hip_fail(c, hipGetLastError(), "tile-sparse reduced solve launch");
     } else if (band && c->bcr.ready) {
         // an UNDAMPED step (Newton, dogleg's Gauss-Newton step) of a gauge-free problem: S is singular -- vanished pivots are dropped
         // (src/iterators.jl:47-115 asks for the Gauss-Newton step; any exact factorisation of a singular system returns rounding / rounding)
@@ -1543,7 +1537,7 @@ int enqueue_reduced_solve(nlls_ctx* c, bool mf) {
         const double pivot_floor = c->lambda == 0.0 ? 1e-11 : c->damped_floor;
         const bool tiles_direct = c->elim_slab || mf;          // (slab + gather assembly: the tiles are in place, no conversion from band storage)
         if (!tiles_direct) drop(c->zero.tiles);
-        if (c->bcr.enqueue(c->stream, tiles_direct ? (const double*)nullptr : c->S.p, c->s_ptr(), c->d_status.p, pivot_floor) != NLLS_OK) return herr(c, hipGetLastError(), "block cyclic reduction launch");
+        if (c->bcr.enqueue(c->stream, tiles_direct ? (const double*)nullptr : c->S.p, c->s_ptr(), c->d_status.p, pivot_floor) != NLLS_OK) return hip_fail(c, hipGetLastError(), "block cyclic reduction launch");
     } else if (band) {
         // bands wider than block cyclic reduction takes (more than 80 columns), and NLLS_FLAG_NO_BCR: the chain kernels of round 1 (nlls_chain.hip)
         const int rc = enqueue_chain_solve(c, L.n_band, L.bw, L.nbd, L.H); if (rc != NLLS_OK) return rc;
@@ -1563,9 +1557,9 @@ int enqueue_reduced_solve(nlls_ctx* c, bool mf) {
             for (int p = 0; p < NB128; ++p) {
                 const int whi = std::min(NB128, (128 * p + 127 + c->bw) / 128 + 1);            // first 128-row block BEHIND the band of this panel
                 DenseWin w; w.nwin = std::max(0, std::min(whi, NB128) - (p + 1)); w.strip = std::max(strip128, p + 1 + w.nwin); w.ntot = w.nwin + std::max(0, NB128 - w.strip);
-                launch_dense_panel(c->stream, c->S.p, Wbuf, LiD, npad, p, c->d_status.p, 1, Dfac, w);
+                launch_dense_panel(c->stream, c->S.p, Wbuf, LiD, npad, p, c->d_status.p, 1, Dfac, c->sw.dense_dch1, w);
                 if (w.ntot <= 0) continue;
-                if (w.ntot >= c->dense_t128_min) hipLaunchKernelGGL(syrk_update128_kernel, dim3(w.ntot * (w.ntot + 1) / 2), dim3(512), 0, c->stream, c->S.p, W0, W1, npad, 2 * p, 2 * p + 2, 0, w.nwin, w.strip);
+                if (w.ntot >= c->sw.dense_t128_min) hipLaunchKernelGGL(syrk_update128_kernel, dim3(w.ntot * (w.ntot + 1) / 2), dim3(512), 0, c->stream, c->S.p, W0, W1, npad, 2 * p, 2 * p + 2, 0, w.nwin, w.strip);
                 else { const int T = 2 * w.ntot; hipLaunchKernelGGL(syrk_update2_kernel<2>, dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->S.p, W0, W1, npad, 2 * p, 2 * p + 2, 0, 2 * w.nwin, 2 * w.strip); }
             }
             launch_dense_dcopy_all(c->stream, c->S.p, Dfac, npad, NB128, 2 * NB128, 0);
@@ -1574,19 +1568,19 @@ int enqueue_reduced_solve(nlls_ctx* c, bool mf) {
             // 128-column panels (dense_panel_kernel<8, 2>: one launch factors what used to be panel k, a narrow update of block column k + 1 and
             // panel k + 1), each followed by ONE update of everything behind it with K = 128 (128 x 128 tiles; 64 x 64 for the small tail)
             for (; k + 1 < nblk; k += 2) {
-                launch_dense_panel(c->stream, c->S.p, Wbuf, LiD, npad, k / 2, c->d_status.p, 1, Dfac);
+                launch_dense_panel(c->stream, c->S.p, Wbuf, LiD, npad, k / 2, c->d_status.p, 1, Dfac, c->sw.dense_dch1);
                 const int T = nblk - k - 2;
                 if (T <= 0) continue;
                 const int T128 = (T + 1) / 2;
-                if (T128 >= c->dense_t128_min) hipLaunchKernelGGL(syrk_update128_kernel, dim3(T128 * (T128 + 1) / 2), dim3(512), 0, c->stream, c->S.p, W0, W1, npad, k, k + 2, 0);
+                if (T128 >= c->sw.dense_t128_min) hipLaunchKernelGGL(syrk_update128_kernel, dim3(T128 * (T128 + 1) / 2), dim3(512), 0, c->stream, c->S.p, W0, W1, npad, k, k + 2, 0);
                 else hipLaunchKernelGGL(syrk_update2_kernel<2>, dim3(T * (T + 1) / 2), dim3(256), 0, c->stream, c->S.p, W0, W1, npad, k, k + 2, 0);
             }
             const int nwide = k / 2;
-            if (k < nblk) { launch_dense_panel(c->stream, c->S.p, W0, LiD, npad, k, c->d_status.p, 0, Dfac); ++k; }     // an odd last 64-column panel: nothing behind it
+            if (k < nblk) { launch_dense_panel(c->stream, c->S.p, W0, LiD, npad, k, c->d_status.p, 0, Dfac, c->sw.dense_dch1); ++k; }     // an odd last 64-column panel: nothing behind it
             launch_dense_dcopy_all(c->stream, c->S.p, Dfac, npad, nwide, 2 * nwide, nblk - 2 * nwide);
         }
         // backward substitution into acc / s (x)
-        if (c->dense_fused_bwd) {
+        if (c->sw.dense_fused_bwd) {
             // ONE launch for the whole substitution (+ one for the explicit inverses of the 128 x 128 diagonal blocks, into the slots the factored
             // diagonal blocks have just left, and the sentinel in x)
             launch_dense_bwd_fused(c->stream, c->S.p, LiD, Dfac, npad, n, c->s_ptr(), c->d_status.p);
@@ -1634,7 +1628,7 @@ int enqueue_solve_finish(nlls_ctx* c, const TrialArgs& t) {
         if (tiles_direct) { const BcrGeom& g = c->bcr.geom; zptr = g.ws + g.oD; zcount = (int64_t)(g.oBR + (size_t)g.N * g.NT * 256 - g.oD); }
         // an LM trial (TrialArgs::to / from): the retraction in this launch
         BsfRetract rt{}; unsigned nrestwg = 0; rt.stamps = c->stamp_ptr();
-        if (t.to >= 0 && (c->post_fuse || t.mf) && c->fast_all_euclid && c->nranks == 1 && nslow == 0 && c->info.is_sparse && c->n_fast_groups > 0 && c->info.nvar > 0) {
+        if (t.to >= 0 && (c->sw.post_fuse || t.mf) && c->fast_all_euclid && c->nranks == 1 && nslow == 0 && c->info.is_sparse && c->n_fast_groups > 0 && c->info.nvar > 0) {
             rt.on = 1; rt.nrest = (int)c->d_rest_var.n; rt.fast_voff = c->d_fast_voff.p; rt.rest_var = c->d_rest_var.p; rt.rest_red = c->d_rest_red.p;
             rt.vkind = c->d_var_kind.p; rt.vdim = c->d_var_dim.p; rt.voff = c->d_var_off.p; rt.vfrom = vars_ptr(c, t.from); rt.vto = vars_ptr(c, t.to);
             nrestwg = (unsigned)((rt.nrest + 63) / 64);
@@ -1645,11 +1639,10 @@ int enqueue_solve_finish(nlls_ctx* c, const TrialArgs& t) {
             mf_backsub_done(c, t.to, t.from);
             return NLLS_OK;
         }
-#define LAUNCH_BSF(DV) hipLaunchKernelGGL((schur_backsub_fast_kernel<DV>), dim3((unsigned)c->n_fast_groups + nextra + nrestwg), dim3(64), 0, c->stream, c->A.p, c->b.p, c->d_elim_desc.p, c->d_elim_rc.p, \
-                c->Cinv.p, c->s_ptr(), c->x.p, c->tE.p, (uint32_t)c->n_fast_groups, c->d_red_boff.p, n, write_red, zptr, zcount, nextra, rt)
-        if (c->n_fast_groups > 0) { if (c->fast_dv == 3) LAUNCH_BSF(3); else if (c->fast_dv == 2) LAUNCH_BSF(2); else if (c->fast_dv == 1) LAUNCH_BSF(1); }
+        if (c->n_fast_groups > 0) dispatch_dv(c->fast_dv, [&](auto dv) {      // (any other fast_dv: nothing)
+            hipLaunchKernelGGL((schur_backsub_fast_kernel<dv()>), dim3((unsigned)c->n_fast_groups + nextra + nrestwg), dim3(64), 0, c->stream, c->A.p, c->b.p, c->d_elim_desc.p, c->d_elim_rc.p,
+                               c->Cinv.p, c->s_ptr(), c->x.p, c->tE.p, (uint32_t)c->n_fast_groups, c->d_red_boff.p, n, write_red, zptr, zcount, nextra, rt); });
         backsub_done(c, c->n_fast_groups > 0, tiles_direct, zero_S, rt.on);
-#undef LAUNCH_BSF
     }
     HIPCHK(hipGetLastError());
     return NLLS_OK;

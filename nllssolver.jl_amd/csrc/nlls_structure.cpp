@@ -34,13 +34,10 @@ bool res_desc(int kind, ResDesc& d) {
 
 static int fail(nlls_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
 
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(c, NLLS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-
 // tiling parameters (see DESIGN.md "accumulate kernel")
 constexpr uint32_t LIGHT_MAX_ENTRIES = 256;    // one entry per lane of a 256-thread workgroup (192: 47.1 instead of 43.5 us in situ, 128: 60 -- tools/sweep_ab.py)
 constexpr uint32_t LIGHT_IMG_MAX     = 6144;   // doubles of LDS image (48 KiB) -> 3 workgroups per CU
 constexpr uint32_t HEAVY_ROW_ENTRIES = 128;    // rows with more entries get a workgroup of their own
-constexpr uint32_t HEAVY_MAX_ENTRIES_DEFAULT = 1024;   // entries per heavy tile (two wavefronts x 8 pipeline stages); longer rows are split (PARTIAL)
 
 // ---- the hot set ------------------------------------------------------------------------------------------------------------
 // every device buffer the LM loop reads or writes, in the order they are laid out in the arena.  NOT in it: the cost-order arrays of a
@@ -72,9 +69,9 @@ void hot_set(nlls_ctx* c, std::vector<HotItem>& v) {
     if (c->bcr.ready) { hot(v, c->bcr.ws); hot(v, c->bcr.d_upd); hot(v, c->bcr.d_elim); } else hot(v, c->Lwork);
 }
 }  // namespace
-// move the hot set into one allocation (called at the end of a successful upload; NLLS_NO_ARENA=1: leave every buffer where hipMalloc put it)
+// move the hot set into one allocation (called at the end of a successful upload; Switches::no_arena: leave every buffer where hipMalloc put it)
 static int compact_hot_set(nlls_ctx* c) {
-    if (getenv("NLLS_NO_ARENA")) { std::vector<HotItem> v; hot_set(c, v); size_t t = 0; for (const HotItem& it : v) t += it.bytes; c->hot_bytes = (int64_t)t; return NLLS_OK; }
+    if (c->sw.no_arena) { std::vector<HotItem> v; hot_set(c, v); size_t t = 0; for (const HotItem& it : v) t += it.bytes; c->hot_bytes = (int64_t)t; return NLLS_OK; }
     std::vector<HotItem> v; hot_set(c, v);
     size_t total = 0; for (const HotItem& it : v) if (*it.owned) total += (it.bytes + 255) & ~(size_t)255;
     c->hot_bytes = (int64_t)total;
@@ -108,7 +105,7 @@ struct SlotHost { std::vector<uint32_t> dest; std::vector<Tile> light, heavy; };
 static int build_fold(nlls_ctx* c, Group& G, const ResDesc& d, const nlls_cost_group& in, const uint64_t* bi, std::vector<HostList>& hls, std::vector<SlotHost>& sh,
                       const std::vector<int64_t>& segs, const std::vector<int32_t>& row_nlists, std::vector<uint8_t>& row_zero, int32_t flags) {
     G.fold = false; G.fold_ls = -1; G.fold_nh = 0; G.nfrows = 0;
-    const char* env = getenv("NLLS_SWEEP_FOLD"); const int mode = env ? atoi(env) : -1;
+    const int mode = c->sw.sweep_fold;
     if (mode == 0 || (mode < 0 && d.ndeps < 3) || d.ndeps < 2 || d.ndeps > FOLD_MAX_HEAVY + 1 || (flags & NLLS_FLAG_FORCE_ATOMIC)) return NLLS_OK;
     const int nd = d.ndeps; const int64_t nb = (int64_t)c->blocksizes.size();
     int ls = -1; for (int s = 0; s < nd; ++s) { const EntryList& E = G.lists[s]; if (E.n == 0) continue;
@@ -318,7 +315,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
 
     // ---- device buffers ----------------------------------------------------------------------------------
     HIPCHK(hipSetDevice(c->device));
-    if (!getenv("NLLS_NO_ARENA")) {
+    if (!c->sw.no_arena) {
         // reserve the hot arena first (compact_hot_set fills it at the end of the upload).  Estimate: A, b, x, three variable sets, per (cost, slot)
         // incidence its list record, the cost-order arrays, per block the elimination's inverse + descriptors, and for the reduced system the
         // band / tile workspaces -- generous (the slack is never touched), and harmless when short
@@ -455,7 +452,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
                 light.push_back(t); if (partial) all_owner = false;
             };
             // (NLLS_HEAVY_MAX_ENTRIES: A/B knob -- shorter heavy tiles spread a few long rows over more workgroups, at the price of atomic flushes)
-            const uint32_t HEAVY_MAX_ENTRIES = [] { const char* e = getenv("NLLS_HEAVY_MAX_ENTRIES"); const int v = e ? atoi(e) : 0; return v >= 128 ? (uint32_t)v : HEAVY_MAX_ENTRIES_DEFAULT; }();
+            const uint32_t HEAVY_MAX_ENTRIES = (uint32_t)c->sw.heavy_max_entries;
             size_t r = 0;
             while (r < nrows) {
                 int64_t br = L.rows[r]; int64_t ne = L.rowptr[r + 1] - L.rowptr[r]; int64_t seglen = segs[br + 1] - segs[br];
@@ -603,6 +600,8 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     if (rc != NLLS_OK) return rc;
     rc = build_mf(c, ngroups, groups, bi, flags);
     if (rc != NLLS_OK) return rc;
+    // every launch of this structure that takes more dynamic LDS than a kernel gets unasked: granted here, on the context's device, once the sizes are known
+    HIPCHK(grant_sweep_lds(c)); HIPCHK(grant_solve_lds(c)); HIPCHK(grant_mf_lds(c)); HIPCHK(grant_chain_lds(c)); HIPCHK(grant_bcr_lds(c->bcr));
     rc = compact_hot_set(c);
     if (rc != NLLS_OK) return rc;
     c->ready = true;
@@ -943,7 +942,7 @@ int build_schur(nlls_ctx* c, int32_t flags) {
         // back-substitution.  Runs are cut into balanced pieces of about nelim / 384 members, never below 24 (every piece pays its own flush of the packed image: 1830 atomics at
         // ten cameras) -- measured at config 3: 5903 (99 members per workgroup), 6346 (50), 6478 (25), 6330 (16), 5706 (8) LM iterations/s; configs 4 and 5 (991 / 500 runs)
         // lose with ANY cut (2848 -> 2667 / 2505 -> 2332 at 64) and are not cut.  NLLS_SUPERNODE_PIECE=n: the piece size by hand (A/B).
-        { const char* pe = getenv("NLLS_SUPERNODE_PIECE"); const int piece_env = pe ? atoi(pe) : 0;      // (read per upload: an A/B switch that holds for the next upload, not the process)
+        { const int piece_env = c->sw.supernode_piece;
           const int64_t total = (int64_t)ediag.size();
           const int64_t piece = piece_env > 0 ? piece_env : std::min<int64_t>(128, std::max<int64_t>(24, (total + 383) / 384));
           if (piece < 128 && c->nranks == 1) {
@@ -1140,11 +1139,11 @@ int build_schur(nlls_ctx* c, int32_t flags) {
             // tiles per block: the cheapest dependent chain, NT x levels (levels = ceil(log2(N + 1)) for N blocks), among the block sizes the structure allows
             // (NLLS_BCR_NT_FULL=1: always ceil(bw / 16), rounds 2-5)
             const int nt_full = std::max(1, ((int)bw + 15) / 16); int nt_best = nt_full;
-            if (!getenv("NLLS_BCR_NT_FULL")) {
+            if (!c->sw.bcr_nt_full) {
                 auto chain = [&](int t) { const int64_t N = (c->n_band + 16 * t - 1) / (16 * t); int lv = 0; while (((int64_t)1 << lv) < N + 1) ++lv; return (int64_t)t * lv; };
                 for (int t = nt_full - 1; t >= 1; --t) if (bt_bad[t] == 0.0 && chain(t) < chain(nt_best)) nt_best = t;
             }
-            std::string e; const int rc = c->bcr.build(c->n_band, (int)bw, c->nbd, c->band_H, &e, nt_best);
+            std::string e; const int rc = c->bcr.build(c->n_band, (int)bw, c->nbd, c->band_H, &e, c->sw, nt_best);
             if (rc != NLLS_OK) return fail(c, rc, e.c_str());
         }
         // ---- slab + gather assembly (NLLS_FLAG_DETERMINISTIC: no atomics, x is bit-reproducible; 15 % slower than the atomic flush at
@@ -1212,25 +1211,25 @@ int build_schur(nlls_ctx* c, int32_t flags) {
         // dense storage, column-major, the rhs riding along as row n.  When the (re-ordered) reduced system is a WIDE band -- too wide for the band
         // kernels, much narrower than the system: a 2-D camera grid, a loop closure -- the blocked LDL' is restricted to the band and the border strip
         // (enqueue_reduced_solve, `dense_window`): O(n w^2) work instead of n^3 / 3.  The reference's LDL' takes any sparsity (src/linearsolver.jl:28-32).
-        c->dense_window = I0.is_sparse && c->nelim_all > 0 && c->n_band >= 1024 && !(flags & NLLS_FLAG_NO_BAND) && 2 * (bw + 256) < c->n_band && !getenv("NLLS_NO_DENSE_WINDOW");
+        c->dense_window = I0.is_sparse && c->nelim_all > 0 && c->n_band >= 1024 && !(flags & NLLS_FLAG_NO_BAND) && 2 * (bw + 256) < c->n_band && !c->sw.no_dense_window;
         c->dense_pad128 = c->dense_window;
         const int64_t npad = c->dense_pad128 ? ((n + 1 + 127) / 128) * 128 : ((n + 1 + 63) / 64) * 64;   // +1: the rhs rides along as an extra row
         // TILE-SPARSE: nested dissection of the reduced blocks' graph, the factorisation level by level of its elimination tree (nlls_tsp.hip).  Taken when its
         // dependent chain (levels of the tree) and its tile products come out clearly below what the dense / windowed factorisation of the same system costs
         // (rough launch + matrix-core times, in us).
-        if (I0.is_sparse && c->nelim_all > 0 && n >= 512 && !red_adj_blocks.empty() && !(flags & (NLLS_FLAG_NO_BAND | NLLS_FLAG_NO_TILE_SPARSE)) && !getenv("NLLS_NO_TSPARSE")) {
+        if (I0.is_sparse && c->nelim_all > 0 && n >= 512 && !red_adj_blocks.empty() && !(flags & (NLLS_FLAG_NO_BAND | NLLS_FLAG_NO_TILE_SPARSE)) && !c->sw.no_tsparse) {
             std::vector<int32_t> ndof, noff;
             for (int64_t k : red_adj_blocks) { ndof.push_back((int32_t)c->blocksizes[k]); noff.push_back((int32_t)red_of[k]); }
             int nbdn = 0; for (int64_t k = 0; k < nb; ++k) if (!c->is_elim[k] && red_of[k] >= c->n_band) { ndof.push_back((int32_t)c->blocksizes[k]); noff.push_back((int32_t)red_of[k]); ++nbdn; }
             TspSym sym;
-            if (tsp_symbolic(red_adj, ndof, nbdn, sym) && sym.nt > 0 && sym.nt <= 4096) {
+            if (tsp_symbolic(red_adj, ndof, nbdn, sym, c->sw) && sym.nt > 0 && sym.nt <= 4096) {
                 const double NB128 = (double)(npad / 128 + (npad % 128 ? 1 : 0));
                 // (calibrated on camera grids of 24 x 24 ... 100 x 100: a level = panel 30 + update 12 + backward 10 us; a 128^3 product of an update 0.09 us of the chip
                 //  with the empty chunks skipped, of a panel 0.07; the dense trailing update 0.12 us per tile product)
                 const double t_tsp = 52.0 * sym.nlevels + 0.09 * (double)sym.nupd_products + 0.07 * (double)(sym.ntiles_lower - sym.nt);
                 double t_dense = 32.0 * NB128 + 0.12 * NB128 * NB128 * NB128 / 6.0;
                 if (c->dense_window) { const double wt = (double)((bw + 127) / 128 + 1 + (c->nbd + 1 + 127) / 128); t_dense = std::min(t_dense, NB128 * (40.0 + 0.17 * wt * (wt + 1) / 2.0)); }
-                const bool force = getenv("NLLS_FORCE_TSPARSE") != nullptr;
+                const bool force = c->sw.force_tsparse;
                 if (t_tsp < 0.8 * t_dense || force) {
                     // (what the device holds decides: the tiles twice -- S and W -- + slots per tile; a system whose tiles do not fit falls back to the dense / windowed solver,
                     //  which then declines by its own size check)
@@ -1238,7 +1237,7 @@ int build_schur(nlls_ctx* c, int32_t flags) {
                     // (under sharding every rank must arrive at the SAME solver -- the layout of the summed [S | s] depends on it --, so nothing rank-local may decide:
                     //  no look at this device's free memory, and an allocation that fails is an error of the upload, not a quiet change of solver)
                     const bool fits = c->nranks > 1 || hipMemGetInfo(&mfree, &mtotal) != hipSuccess || want + ((size_t)2 << 30) <= mfree;
-                    std::string e; const int rc = fits ? c->tsp.build(sym, noff, ndof, (int)n, &e, &red_adj, nbdn) : NLLS_ERR_UNSUPPORTED;
+                    std::string e; const int rc = fits ? c->tsp.build(sym, noff, ndof, (int)n, &e, c->sw, &red_adj, nbdn) : NLLS_ERR_UNSUPPORTED;
                     if (rc == NLLS_ERR_HIP && c->nranks == 1) { (void)hipGetLastError(); c->tsp.release(); }        // an allocation that failed after all: the other solvers
                     else if (rc != NLLS_OK && rc != NLLS_ERR_UNSUPPORTED) return fail(c, rc, e.c_str());
                 }
@@ -1273,7 +1272,7 @@ int build_schur(nlls_ctx* c, int32_t flags) {
     c->info.solve_mode = c->solve_mode; c->info.bandwidth = c->bw; c->info.nborder_dof = c->nbd;
     // the small dense system's own route (nlls_ctx::tiny_dense): one image of [A | b] per sweep workgroup, summed by one gathering launch
     c->tiny_dense = false; c->dense_slab_wgs = 0;
-    if (c->tiny_dense_on && !c->info.is_sparse && c->solve_mode == SOLVE_SMALL && c->nranks == 1 && c->nelim == 0 && c->info.ndof > 0 && c->nred == c->info.ndof) {
+    if (c->sw.tiny_dense_on && !c->info.is_sparse && c->solve_mode == SOLVE_SMALL && c->nranks == 1 && c->nelim == 0 && c->info.ndof > 0 && c->nred == c->info.ndof) {
         bool ok = true; int64_t wgs = 0;
         for (const Group& G : c->groups) { if (is_dyn_kind(G.res_kind)) ok = false; if (G.dense.n > 0) wgs += std::min<int64_t>((G.dense.n + 255) / 256, TINY_DENSE_MAX_WGS); }
         if (ok && wgs > 0) {

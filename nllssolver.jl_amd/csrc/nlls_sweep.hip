@@ -720,8 +720,6 @@ __global__ void unpack_reduce0_kernel(double* __restrict__ A, double* __restrict
 // ================================================================================================
 // host-side enqueue
 // ================================================================================================
-static int herr(nlls_ctx* c, hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; }
-#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return herr(c, e_, #expr); } while (0)
 
 template <int KIND>
 static GhArgs gh_args(nlls_ctx* c, const Group& G, const EntryList& E, const double* vars, bool heavy, double* partials) {
@@ -855,11 +853,7 @@ int enqueue_sweep_gradhess(nlls_ctx* c, bool want_cost, int which, int mode) {
     else if (prof) (void)hipEventRecord(c->prof_ev[2 * pslot], c->stream);
     for (const Group& G : c->groups) {
         if (is_dyn_kind(G.res_kind)) { enqueue_dyn_gradhess(c, G, vars, pbase); enqueue_fixedcost(c, G, vars, pbase); continue; }   // (into the dense system, or the variable's diagonal block of a block-sparse one)
-        switch (G.res_kind) {
-#define X(K) case K: launch_gh<K>(c, G, vars, pbase, mode); break;
-            NLLS_FOR_EACH_RES(X)
-#undef X
-        }
+        dispatch_res(G.res_kind, [&](auto k) { launch_gh<k()>(c, G, vars, pbase, mode); });
     }
     if (prof) {
         if (c->prof_e0) { (void)hipEventRecord(c->prof_e0, c->stream); c->prof_e0 = nullptr; c->prof_taken = false; c->prof_e1 = nullptr; }   // (no launch took the pair: bracket what ran -- late, but both events exist)
@@ -897,5 +891,19 @@ int enqueue_unpack_reduce0(nlls_ctx* c, bool with_cost) {
                            c->d_red_dst.p, c->d_red_which.p, with_cost ? c->scalars.p : (double*)nullptr, c->redbuf.p);
     HIPCHK(hipGetLastError());
     return NLLS_OK;
+}
+// a heavy row's launch stages HROWS images of up to LIGHT_IMG_MAX doubles (gh_heavy_lds: up to 124 KB); the light, fused and folded launches stay below what a kernel gets unasked
+template <int KIND, int SLOT>
+static hipError_t grant_gh_slot(const EntryList& E) {
+    if (E.nheavy == 0) return hipSuccess;
+    const size_t lds = gh_heavy_lds(E.heavy_lds) * sizeof(double);
+    const hipError_t e = grant_dynamic_lds(&gh_heavy_kernel<KIND, SLOT>, lds);
+    return e != hipSuccess ? e : grant_dynamic_lds(&gh_heavy_fin_kernel<KIND, SLOT>, lds);
+}
+hipError_t grant_sweep_lds(const nlls_ctx* c) {
+    hipError_t e = hipSuccess;
+    for (const Group& G : c->groups) if (!is_dyn_kind(G.res_kind)) dispatch_res(G.res_kind, [&](auto k) { constexpr int K = k();
+        [&]<int... S>(std::integer_sequence<int, S...>) { ((e = e != hipSuccess ? e : grant_gh_slot<K, S>(G.lists[S])), ...); }(std::make_integer_sequence<int, Res<K>::NDEPS>{}); });
+    return e;
 }
 }  // namespace nlls

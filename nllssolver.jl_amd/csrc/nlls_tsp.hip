@@ -357,7 +357,7 @@ __global__ __launch_bounds__(512) void tsp_backward_kernel(const double* __restr
 // host
 // ---------------------------------------------------------------------------------------------------
 int TspSolver::build(const TspSym& sym, const std::vector<int32_t>& node_red_off, const std::vector<int32_t>& dof, int n_red, std::string* err,
-                     const std::vector<std::vector<int32_t>>* adj, int nborder) {
+                     const Switches& sw, const std::vector<std::vector<int32_t>>* adj, int nborder) {
     release();
     n = n_red; nt = sym.nt;
     if (nt <= 0 || nt > 4096) { if (err) *err = "tile-sparse solver: tile count out of range"; return NLLS_ERR_UNSUPPORTED; }
@@ -396,10 +396,8 @@ int TspSolver::build(const TspSym& sym, const std::vector<int32_t>& node_red_off
     std::vector<std::vector<int32_t>> by_level(sym.nlevels), rowlist(nt);
     for (int k = 0; k < nt; ++k) { by_level[sym.level[k]].push_back(k); for (int32_t i : sym.cstruct[k]) rowlist[i].push_back(k); }
     products = 0;
-    // (A/B switches, read at every build: a context's upload decides, not the process)
-    const int force_scheme = [] { const char* e = getenv("NLLS_TSP_SCHEME"); return e ? atoi(e) : 0; }();      // 1 / 2 / 3 for every level
-    const int slots = [] { const char* e = getenv("NLLS_TSP_SLOTS"); return e ? atoi(e) : 256; }();             // workgroups of one round of the chip (a panel workgroup fills a CU's LDS)
-    quad_max = [] { const char* e = getenv("NLLS_TSP_QUAD_MAX"); return e ? atoi(e) : 160; }();                 // target tiles of a level up to which a workgroup takes a quarter tile
+    const int force_scheme = sw.tsp_scheme, slots = sw.tsp_slots;      // 1 / 2 / 3 for every level; workgroups of one round of the chip (a panel workgroup fills a CU's LDS)
+    quad_max = sw.tsp_quad_max; chunk_masks = !sw.tsp_no_masks;
     for (int lv = 0; lv < sym.nlevels; ++lv) {
         TspLevel& L = levels[lv]; L.panel0 = pj.size(); L.upd0 = uj.size(); L.bwd0 = bj.size(); L.trsm0 = tj.size();
         std::map<std::pair<int32_t, int32_t>, std::vector<TspCon>> tgt; std::map<int32_t, std::vector<TspCon>> rhs;
@@ -423,8 +421,7 @@ int TspSolver::build(const TspSym& sym, const std::vector<int32_t>& node_red_off
         // keeps a CU busy ~14 us, so with P products in the level a workgroup should not hold more than ~P / 256 of them; longer lists are cut and their pieces add
         // atomically (the elimination's flush into S is atomic as well: x is reproducible to rounding, not to the bit)
         int64_t P = 0; for (auto& kv : tgt) P += (int64_t)kv.second.size();
-        const int cap_env = [] { const char* e = getenv("NLLS_TSP_CAP"); return e ? atoi(e) : 0; }();
-        const int64_t cap = cap_env > 0 ? cap_env : std::max<int64_t>(2, (P + 255) / 256);
+        const int64_t cap = sw.tsp_cap > 0 ? sw.tsp_cap : std::max<int64_t>(2, (P + 255) / 256);
         std::vector<std::pair<int64_t, std::pair<int32_t, int32_t>>> order;
         for (auto& kv : tgt) order.push_back({-(int64_t)kv.second.size(), kv.first});
         std::sort(order.begin(), order.end());                 // heaviest targets first (a launch ends with its longest workgroup)
@@ -442,7 +439,6 @@ int TspSolver::build(const TspSym& sym, const std::vector<int32_t>& node_red_off
     rest0 = plist.size(); nrest = (int)rest.size(); plist.insert(plist.end(), rest.begin(), rest.end());
     if (uc.empty()) uc.push_back(TspCon{0, 0}); if (uj.empty()) uj.push_back(TspUpdJob{}); if (padpos.empty()) padpos.push_back(0); if (tj.empty()) tj.push_back(TspTrsmJob{});
     oW = 0; oLiD = s_elems(); oDfac = oLiD + (size_t)nt * 8 * 256; oDinv = oDfac + (size_t)nt * TSP_TE; oxt = oDinv + (size_t)nt * TSP_TE; oacc = oxt + (size_t)nt * TSP_TR; odg = oacc + (size_t)nt * TSP_TR; omask = odg + (size_t)nt * TSP_TR;
-    chunk_masks = getenv("NLLS_TSP_NO_MASKS") == nullptr;
     if (hipSuccess != d_map.upload(map) || hipSuccess != d_ipos.upload(ipos) || hipSuccess != d_panel.upload(pj) || hipSuccess != d_upd.upload(uj) || hipSuccess != d_con.upload(uc) ||
         hipSuccess != d_bwd.upload(bj) || hipSuccess != d_trsm.upload(tj) || hipSuccess != d_plist.upload(plist) || hipSuccess != d_padpos.upload(padpos) ||
         hipSuccess != ws.alloc(omask + (size_t)(nslots + 1) / 2 + 64)) {

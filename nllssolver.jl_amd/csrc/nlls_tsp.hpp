@@ -9,6 +9,7 @@
 
 #include "../../include/nlls_amd.h"
 #include "nlls_devbuf.hpp"
+#include "nlls_switches.hpp"
 
 namespace nlls {
 
@@ -30,8 +31,8 @@ struct TspSym {
     int64_t nupd_products = 0;                     // 128^3 tile products of the whole factorisation (sum over k of |cstruct| (|cstruct| + 1) / 2)
 };
 // adj: symmetric adjacency among the n non-border nodes (sorted, no self loops); border nodes (coupled to everything) are appended behind them:
-// dof.size() = n + nborder.  Returns false when a node has more than TSP_TR unknowns.
-bool tsp_symbolic(const std::vector<std::vector<int32_t>>& adj, const std::vector<int32_t>& dof, int nborder, TspSym& out);
+// dof.size() = n + nborder.  Returns false when a node has more than TSP_TR unknowns.  sw: tsp_leaf, tsp_carry
+bool tsp_symbolic(const std::vector<std::vector<int32_t>>& adj, const std::vector<int32_t>& dof, int nborder, TspSym& out, const Switches& sw);
 
 // ---- device side (nlls_tsp.hip) ----------------------------------------------------------------------------------------------------------
 struct TspPanelJob { int64_t doff, xoff; int32_t k, xld, rx, lead; };      // one workgroup of a level's panel launch: pivot tile k (diagonal tile at doff), 16 rx rows of X at xoff (leading dimension xld)
@@ -56,14 +57,15 @@ struct TspSolver {
     DevBuf<int64_t> d_padpos;                      // offsets (in S) of the padding's diagonal entries
     DevBuf<double> ws;                             // W tiles + strips (as S) | LiD | Dfac | Dinv | xt | acc
     size_t oW = 0, oLiD = 0, oDfac = 0, oDinv = 0, oxt = 0, oacc = 0, odg = 0, omask = 0;
-    int quad_max = 160;                            // NLLS_TSP_QUAD_MAX (A/B): target tiles of a level up to which an update workgroup takes a quarter tile
-    bool chunk_masks = true;                       // NLLS_TSP_NO_MASKS=1 (A/B): every tile product in full
+    int quad_max = 160;                            // Switches::tsp_quad_max: target tiles of a level up to which an update workgroup takes a quarter tile
+    bool chunk_masks = true;                       // !Switches::tsp_no_masks (off: every tile product in full)
     int64_t npad_entries = 0;
     int launches = 0; int64_t products = 0;
     size_t s_elems() const { return (size_t)nslots * TSP_TE + (size_t)nt * TSP_STRIP; }     // tiles, then one right-hand-side strip per tile column
     // adj / nborder (as given to tsp_symbolic): the tiles the ASSEMBLY writes into (a coupling of S before fill; the border's rows; every diagonal tile) take the first
     // nslots_assembled slots -- under sharding only that prefix of the tiles is summed over ranks, the fill tiles are zero on every rank until the factorisation
-    int build(const TspSym& sym, const std::vector<int32_t>& node_red_off, const std::vector<int32_t>& dof, int n_red, std::string* err,
+    // sw: tsp_scheme, tsp_slots, tsp_quad_max, tsp_cap, tsp_no_masks
+    int build(const TspSym& sym, const std::vector<int32_t>& node_red_off, const std::vector<int32_t>& dof, int n_red, std::string* err, const Switches& sw,
               const std::vector<std::vector<int32_t>>* adj = nullptr, int nborder = 0);
     int64_t nslots_assembled = 0;
     // S: [tiles | strips] assembled by the elimination through SLayout::at (mode SOLVE_TSPARSE), s: the reduced right-hand side in, the solution out

@@ -55,13 +55,12 @@ __global__ __launch_bounds__(UPD_TPB) void upd_wave_kernel(const UpdArgs a, int 
 
 // n records at c->upd_stage (and, `indexed`, their blocks at c->upd_index) into every copy of group G
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed) {
-    auto herr = [c](hipError_t e, const char* what) { c->err = std::string(what) + ": " + hipGetErrorString(e); return NLLS_ERR_HIP; };
     if (!G.pos_on_device) {         // the first update of this upload: the maps go to the device (hipMalloc of their own: nothing of the hot arena moves or grows)
         hipError_t e = hipSuccess;
         for (int s = 0; s < MAX_SLOTS && e == hipSuccess; ++s) if (!G.pos_list[s].empty()) e = G.d_pos_list[s].upload(G.pos_list[s]);
         if (e == hipSuccess && !G.pos_dense.empty()) e = G.d_pos_dense.upload(G.pos_dense);
         if (e == hipSuccess && !G.pos_mf.empty()) e = G.d_pos_mf.upload(G.pos_mf);
-        if (e != hipSuccess) return herr(e, "nlls_set_cost_data: position maps");
+        if (e != hipSuccess) return hip_fail(c, e, "nlls_set_cost_data: position maps");
         G.pos_on_device = true;
     }
     UpdArgs a{}; int nc = 0;
@@ -82,7 +81,7 @@ int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed) {
     if (timed) { (void)hipEventRecord(c->phase_ev[9], c->stream); c->upd_pending = true; }
     c->upd_copies = nc;
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? NLLS_OK : herr(e, "nlls_set_cost_data: scatter launch");
+    return e == hipSuccess ? NLLS_OK : hip_fail(c, e, "nlls_set_cost_data: scatter launch");
 }
 
 }  // namespace nlls

@@ -721,7 +721,8 @@ def test_folded_sweep_switch(fold, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("env", [{"NLLS_DENSE_T128_MIN": "1"}, {"NLLS_BCR_CHROWS_SLOTS": "0"},
                                  {"NLLS_DENSE_STEP_BACKWARD": "1"}, {"NLLS_BCR_LEVEL_BACKWARD": "1"}, {"NLLS_ELIM_SPLIT": "1"}, {"NLLS_POST_SPLIT": "1"},
-                                 {"NLLS_HEAVY_MAX_ENTRIES": "256"}, {"NLLS_SUPERNODE_PIECE": "128"}, {"NLLS_SUPERNODE_PIECE": "5"}])
+                                 {"NLLS_HEAVY_MAX_ENTRIES": "256"}, {"NLLS_SUPERNODE_PIECE": "128"}, {"NLLS_SUPERNODE_PIECE": "5"},
+                                 {"NLLS_COST_GRID_MAX": "3"}, {"NLLS_DENSE_DCH1": "0"}])      # (these two are read at upload like the rest: a cost sweep of three workgroups, two-row panels everywhere)
 def test_ab_switches_select_paths_that_still_match_the_oracle(env, monkeypatch):
     """The environment switches read by nlls_create (the 128 x 128-tile dense update from the first pass on, three X rows per panel workgroup at every
     level of the block cyclic reduction, one backward launch per block / per level instead of the one-launch substitutions, the assembly in three
@@ -787,6 +788,49 @@ def test_matrix_free_trial_against_the_materialised_one_and_the_oracle(ncam, npt
         seq[name] = (a, b, c2, ctx.get_step())
     assert np.allclose(seq["mf"][:3], seq["mat"][:3], rtol=1e-9, atol=1e-13 * abs(c0)) and rel(seq["mf"][3], seq["mat"][3]) < 1e-8
     ctx.close()
+
+
+def test_an_option_set_before_an_upload_survives_it():
+    """nlls_set_option writes fields of the context's switches that only nlls_ctx_create reads from the environment: an upload (which reads the upload-time
+    switches afresh) leaves NLLS_OPT_MATERIALIZE as the caller set it, on the first upload and on the next, until the caller sets it back."""
+    p = _ba(120, 3000, 0.06, 11)
+    bi = np.arange(1, p.nvariables + 1, dtype=np.uint64)
+    ctx = _capi.Context(); ctx.set_option(_capi.OPT_MATERIALIZE, 1)
+
+    def trial():
+        ctx.set_variables(p.variables); ctx.sweep_gradhess(); ctx.lm_trial(1e-6 * ctx.max_abs_diag())
+        return ctx.solve_stats()["mf_trials"]
+    for _ in range(2):
+        info = ctx.upload(p.var_kind, p.var_dim, bi, p.groups())
+        assert info.has_schur and trial() == 0
+    ctx.set_option(_capi.OPT_MATERIALIZE, 0)
+    assert trial() == 1, "the structure should qualify for the matrix-free trial"
+    ctx.close()
+
+
+def test_lds_grants_are_per_upload_not_per_process():
+    """Two contexts in one process whose uploads both reach the generic LDS-staged elimination (every point listed before its cameras), the one with the wider
+    supernodes uploaded first: each upload grants the launch's dynamic LDS for what IT needs, and the grant only grows -- a solve in the second context, then one in
+    the first, both against the oracle at check_problem's tolerances."""
+    from tests.helpers import permute_variables, eliminated_mask, NAMED_ORDERS
+    made = []
+    for ncam, npts, prop, seed in ((20, 150, 0.6, 21), (12, 80, 0.3, 5)):            # about twelve cameras per point, then about four
+        p = synthetic.perturb_ba_problem(synthetic.create_ba_problem(ncam, npts, prop, seed=seed, robust=N.HuberKernel(0.05), outlier_frac=0.1, outlier_sigma=0.05), 1e-3, 1e-3)
+        q, _ = permute_variables(p, NAMED_ORDERS["elim_first"](eliminated_mask(p)))
+        bi = blockindices(q, None); ctx = _capi.Context()
+        made.append((q, bi, ctx, ctx.upload(q.var_kind, q.var_dim, bi, q.groups())))
+    for q, bi, ctx, info in reversed(made):
+        ols = oracle_problem(q).linear_system(bi)
+        ctx.set_variables(q.variables)
+        assert np.isclose(ctx.sweep_gradhess(), ols.costgradhess(), rtol=RTOL, atol=1e-300)
+        A_ora = ols.data.copy()
+        assert info.is_sparse and info.has_schur and rel(ctx.get_bsm_data(), A_ora) < RTOL and rel(ctx.get_grad(), ols.b) < RTOL
+        lam = ols.max_abs_diag() * 1e-4; ctx.damp(lam); x = ctx.solve(want_x=True)
+        st = ctx.solve_stats()
+        assert st["elim_slow_acc"] + st["elim_slow_noacc"] > 0, st
+        check_step(ctx, info, ols, A_ora, lam, x, f"two contexts, {info.nreduced_dof} reduced dof")
+        assert ols.solve(lam) == 0 and rel(x, ols.x) < RTOL_X
+    for _, _, ctx, _ in made: ctx.close()
 
 
 def test_optimize_singles_invalidates_a_lookahead_sweep():

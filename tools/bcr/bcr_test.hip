@@ -56,7 +56,8 @@ static int run_case(int n, int bw, int nbd, int reps, unsigned seed) {
     std::vector<double> xc; cpu_solve(n, bw, nbd, H, Sb, xc);
     if (!BcrSolver::supports(n, bw, nbd)) { printf("case n=%d bw=%d nbd=%d: unsupported\n", n, bw, nbd); return 0; }
     BcrSolver S; std::string err;
-    if (S.build(n, bw, nbd, H, &err) != 0) { printf("build failed: %s\n", err.c_str()); return 1; }
+    if (S.build(n, bw, nbd, H, &err, Switches{}) != 0) { printf("build failed: %s\n", err.c_str()); return 1; }
+    if (grant_bcr_lds(S) != hipSuccess) { printf("LDS grant failed\n"); return 1; }
     double *dS, *dx; int* dst;
     hipMalloc(&dS, Sb.size() * 8); hipMalloc(&dx, (n + nbd + 16) * 8); hipMalloc(&dst, 512);
     hipMemcpy(dS, Sb.data(), Sb.size() * 8, hipMemcpyHostToDevice); hipMemset(dst, 0, 512); hipMemset(dx, 0, (n + nbd + 16) * 8);

@@ -21,7 +21,7 @@ int main() {
         for (auto& l : adj) { std::sort(l.begin(), l.end()); l.erase(std::unique(l.begin(), l.end()), l.end()); }
         int nb = rng() % 3;
         std::vector<int32_t> dof(n + nb, d); for (int q = 0; q < nb; ++q) dof[n + q] = 1 + rng() % 6;
-        TspSym sym; bool ok = tsp_symbolic(adj, dof, nb, sym);
+        TspSym sym; bool ok = tsp_symbolic(adj, dof, nb, sym, Switches{});
         if (!ok) { printf("case %d declined\n", it); continue; }
         for (int v = 0; v < n + nb; ++v) if (sym.tile_of[v] < 0 || sym.tile_of[v] >= sym.nt || sym.row_in_tile[v] + dof[v] > 128) { printf("BAD placement case %d\n", it); return 1; }
         for (int k = 0; k < sym.nt; ++k) for (int32_t i : sym.cstruct[k]) if (i <= k || i >= sym.nt || sym.level[i] <= sym.level[k]) { printf("BAD struct case %d\n", it); return 1; }
