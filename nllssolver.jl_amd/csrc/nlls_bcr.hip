@@ -132,9 +132,15 @@ BCR_DEV void bcr_factor(const double* T0, bool from_regs, const bdouble4_t Ain, 
     const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
     // FLOOR: fl = the floor of pivot li, a fraction of the ORIGINAL diagonal entry of that unknown (handed in by the caller: see bcr_panel_kernel)
     if constexpr (!FLOOR) fl = 0.0;
-    bdouble4_t A, Bt;
+    bdouble4_t A = Ain, Bt;
+    // (from_regs is uniform: a branch around the four LDS reads, not a select behind them -- the look-ahead's tile, every column but the first, starts its chain
+    //  without an LDS round trip in front of the first pivot)
+    if (!from_regs) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const double t = T0[(lk + 4 * r) * BP + li]; A[r] = from_regs ? Ain[r] : t; Bt[r] = (lk + 4 * r == li) ? 1.0 : 0.0; }
+        for (int r = 0; r < 4; ++r) A[r] = T0[(lk + 4 * r) * BP + li];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Bt[r] = (lk + 4 * r == li) ? 1.0 : 0.0;
     // Delta is read off the diagonal of the finished tile (entry (k, k) is final once pivot k - 1 has been applied), 1 / Delta is
     // formed again by sixteen lanes at once (same instructions, same bits), zero / NaN pivots are looked for there too.
     // The floor (round 5: on EVERY solve, damped ones too) stays off the chain: the tile is factored as if no pivot could vanish, the sixteen pivots it used are held
@@ -159,13 +165,15 @@ BCR_DEV void bcr_factor(const double* T0, bool from_regs, const bdouble4_t Ain, 
             if (report) { const unsigned long long m = __ballot(dropped && (li & 3) == lk); if (m != 0 && (threadIdx.x & 63) == 0) atomicAdd(status + 4, __popcll(m)); }   // status[4]: pivots dropped by the floor (nlls_get_solve_stats)
         }
     }
+    // the tile and its inverse go to LDS FIRST: the eight stores are on their way while the sixteen lanes of the diagonal form 1 / Delta (four dependent f64
+    // instructions), and the barrier behind this function waits for the two together instead of one after the other
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { Wd[(lk + 4 * r) * BP + li] = A[r]; Lid[li * BP + (lk + 4 * r)] = Bt[r]; }
     if ((li & 3) == lk) {
         const double rd = bcr_refine_rcp(dsel, __builtin_amdgcn_rcp(dsel));
         dd[li] = dsel; dd[16 + li] = rd;
         if (report && !(fabs(dsel) > 0.0)) atomicCAS(status, 0, 1 + pivbase + li);
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { Wd[(lk + 4 * r) * BP + li] = A[r]; Lid[li * BP + (lk + 4 * r)] = Bt[r]; }
 }
 // W = T inv(L)'   (one wavefront, one tile)
 BCR_DEV void bcr_panel_tile(const double* T, const double* Lid, double* Wt) {
@@ -302,8 +310,11 @@ __global__ __launch_bounds__(BCR_T) void bcr_panel_kernel(BcrPanelArgs a) {
         if (job.l < 0 && job.r < 0 && tid < g.nbd) g.ws[g.oxb + tid] = __longlong_as_double((long long)BCR_X_SENTINEL);      // (the root: the border's unknowns)
     }
 #ifdef BCR_STAMPS
+#ifndef BCR_STAMP_M
+#define BCR_STAMP_M a.ch.m                        // -DBCR_STAMP_M=<chain length>: the stamps of that level's launch alone (default: every level writes, the root's stay)
+#endif
     const unsigned long long st0 = __builtin_amdgcn_s_memtime(); int stn = 0;
-#define BCR_STAMP() do { if (blockIdx.x == gridDim.x - 1 && lane == 0 && wave <= 1 && stn < 20) a.status[16 + 20 * wave + stn++] = (int)(__builtin_amdgcn_s_memtime() - st0); } while (0)   // (status holds 96 ints: slots 16..55 and 56..71 are the instrumented build's)
+#define BCR_STAMP() do { if (a.ch.m == BCR_STAMP_M && blockIdx.x == gridDim.x - 1 && lane == 0 && wave <= 1 && stn < 20) a.status[16 + 20 * wave + stn++] = (int)(__builtin_amdgcn_s_memtime() - st0); } while (0)   // (status holds 96 ints: slots 16..55 and 56..71 are the instrumented build's)
 #else
 #define BCR_STAMP() do {} while (0)
 #endif
@@ -407,7 +418,7 @@ __global__ __launch_bounds__(BCR_T) void bcr_panel_kernel(BcrPanelArgs a) {
         else if (helper) { if (J > 0) { BCR_STAMP(); updates(J - 1, hw, 6); BCR_STAMP(); exports(J - 1, hw, 6); } else land_rest(); }
         BCR_STAMP();
 #ifdef BCR_STAMPS
-        if (blockIdx.x == gridDim.x - 1 && lane == 0 && J < 2) a.status[56 + 8 * J + wave] = (int)(__builtin_amdgcn_s_memtime() - st0);
+        if (a.ch.m == BCR_STAMP_M && blockIdx.x == gridDim.x - 1 && lane == 0 && J < 2) a.status[56 + 8 * J + wave] = (int)(__builtin_amdgcn_s_memtime() - st0);
 #endif
         bcr_lds_barrier();                                // diagonal tile factored; block column J final
         BCR_STAMP();
@@ -787,13 +798,22 @@ __global__ __launch_bounds__(64 * NT) void bcr_backward_kernel(BcrBackArgs a) {
     double* Mdl = xi + NT * 16;                    // [NO][256]
     double* Cl = Mdl + NO * 256;                   // [16][16] corner (root only)
     double* xb = Cl + 256;                         // [16]
+    double* Crl = xb + 16;                         // [16][16] the root block's own share of the corner (root only)
     // this wave's column of the X part of the factor: rows gq, gq + 4, .. of every tile (absent neighbours: block i's own tiles, weight 0)
     const double* Mxg = g.ws + g.oMx + (size_t)job.i * RXT * NT * 256 + (size_t)wave * 256 + c;
     double mx[RXT][4];
+    // (the root has no neighbours and nothing writes its slot of Mx: its rows are zeros here, its border / rhs row comes from the prologue below -- no load stands in front of that)
 #pragma unroll
     for (int R = 0; R < RXT; ++R) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) mx[R][q] = Mxg[(size_t)R * NT * 256 + (gq + 4 * q) * 16];
+        for (int q = 0; q < 4; ++q) mx[R][q] = 0.0;
+    }
+    if (!root) {
+#pragma unroll
+        for (int R = 0; R < RXT; ++R) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mx[R][q] = Mxg[(size_t)R * NT * 256 + (gq + 4 * q) * 16];
+        }
     }
     // the unknowns of the neighbours and of the border that this block's rows multiply: requested NOW, beside the factor's tiles (one memory
     // round trip per level instead of two; the root forms the border unknowns itself first and takes the loop below)
@@ -804,7 +824,47 @@ __global__ __launch_bounds__(64 * NT) void bcr_backward_kernel(BcrBackArgs a) {
         else if (R < 2 * NT) { if (job.r >= 0) { const int row = b * job.r + 16 * (R - NT) + q; if (row < g.n_band) xpre = a.xr[row]; } }
         else xpre = q < nbd ? g.ws[g.oxb + q] : (q == nbd ? -1.0 : 0.0);
     }
-    {   // the block's own triangle: global -> registers -> LDS, every load in flight at once
+    if (root) {
+        // The root block's factor is read by this workgroup alone, so it is pre-multiplied HERE instead of by an update launch of its own between the root's
+        // panel and the backward pass (one dependent launch fewer per solve): the same tile products in the same order as bcr_update_body's (mode 3, and mode 2
+        // for the corner's share), so the same bits.  The accumulator layout of M = L inv(L_JJ) is the layout mx wants (register q of lane (c, gq) = M[gq + 4 q][c]):
+        // wave J's tile of the border / rhs row never leaves its registers; the triangle goes straight into Mdl, the corner's share into Crl.  The root has no
+        // neighbours: the other rows of mx multiply zeros.
+        auto ld4 = [&](size_t off) { return *reinterpret_cast<const bdouble4_t*>(g.ws + off + 4 * lane); };
+        auto mul = [&](const bdouble4_t& av, const bdouble4_t& bv, bdouble4_t& acc, bdouble4_t& acc2) {
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], bv[0], acc, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[1], bv[1], acc2, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[2], bv[2], acc, 0, 0, 0);
+            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[3], bv[3], acc2, 0, 0, 0); };
+        const size_t oLi = g.oLi + (size_t)job.i * NT * 256, oLd = g.oLd + (size_t)job.i * NO * 256;
+        const size_t oWxr = g.oWx + (size_t)2 * NT * NT * 256, oLxr = g.oLx + (size_t)2 * NT * NT * 256;      // the border / rhs row of slot 0 (the root's launch has one block)
+        constexpr int MDQ = (NO + NT - 1) / NT;                                                               // tiles of the triangle per wave
+        const bool corner = nbd > 0 && wave == NT - 1;                                                        // (the wave with the fewest tiles of the triangle)
+        const bdouble4_t xa = ld4(oLxr + 256 * wave), xl = ld4(oLi + 256 * wave);
+        bdouble4_t da[MDQ > 0 ? MDQ : 1], dl[MDQ > 0 ? MDQ : 1], ca[NT], cb[NT];
+#pragma unroll
+        for (int q = 0; q < MDQ; ++q) { const int t = wave + NT * q;
+            if (t < NO) { int I = 1; while ((I + 1) * I / 2 <= t) ++I; da[q] = ld4(oLd + 256 * t); dl[q] = ld4(oLi + 256 * (t - I * (I - 1) / 2)); } }
+        if (corner) {
+#pragma unroll
+            for (int J = 0; J < NT; ++J) { ca[J] = ld4(oWxr + 256 * J); cb[J] = ld4(oLxr + 256 * J); }
+        }
+        { bdouble4_t acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0}; mul(xa, xl, acc, acc2);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) mx[RXT - 1][q] = acc[q] + acc2[q]; }
+#pragma unroll
+        for (int q = 0; q < MDQ; ++q) { const int t = wave + NT * q;
+            if (t < NO) { bdouble4_t acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0}; mul(da[q], dl[q], acc, acc2);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Mdl[t * 256 + (gq + 4 * r) * 16 + c] = acc[r] + acc2[r]; } }
+        if (corner) {
+            bdouble4_t acc = {0, 0, 0, 0}, acc2 = {0, 0, 0, 0};
+#pragma unroll
+            for (int J = 0; J < NT; ++J) mul(ca[J], cb[J], acc, acc2);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Crl[(gq + 4 * r) * 16 + c] = acc[r] + acc2[r];
+        }
+    } else {   // the block's own triangle: global -> registers -> LDS, every load in flight at once
         constexpr int MQ = (NO * 256 + NTH - 1) / NTH;
         const double* Mdg = g.ws + g.oMd + (size_t)job.i * NO * 256;
         double mdv[MQ > 0 ? MQ : 1];
@@ -835,20 +895,22 @@ __global__ __launch_bounds__(64 * NT) void bcr_backward_kernel(BcrBackArgs a) {
             // (round 5: the N blocks' shares dealt over the lanes -- each entry of rows 0 .. nbd, the rows read below, as `parts` partial sums formed side by side and combined in a
             //  fixed order: reproducible.  One thread per entry stepping through the N shares was a chain of N dependent loads on the path every other block of the backward pass
             //  waits for: 28 us at BASELINE config 5 -- the adaptive kernel's variable is the border -- where six levels without a border take ~18.)
+            __syncthreads();                       // Crl: the root's own share, formed above, stands in for its slot of cp at the same place of the sum
+            auto share = [&](int i, int e) { return i == job.i ? Crl[e] : g.ws[g.ocp + (size_t)(1 + i) * 256 + e]; };
             {
                 const int ne = 16 * nbr; int parts = NTH / ne; if (parts > 8) parts = 8; if (parts * ne > NT * 64) parts = (NT * 64) / ne;     // (the partial sums go through `red`: NT * 64 doubles, not in use yet)
                 if (parts >= 2) {
                     const int e = tid % ne, pt = tid / ne;
                     if (pt < parts) {
                         double v0 = 0.0, v1 = 0.0; int i = pt;
-                        for (; i + parts < g.N; i += 2 * parts) { v0 += g.ws[g.ocp + (size_t)(1 + i) * 256 + e]; v1 += g.ws[g.ocp + (size_t)(1 + i + parts) * 256 + e]; }
-                        if (i < g.N) v0 += g.ws[g.ocp + (size_t)(1 + i) * 256 + e];
+                        for (; i + parts < g.N; i += 2 * parts) { v0 += share(i, e); v1 += share(i + parts, e); }
+                        if (i < g.N) v0 += share(i, e);
                         red[pt * ne + e] = v0 + v1;
                     }
                     __syncthreads();
                     if (tid < ne) { double v = g.ws[g.ocp + tid]; for (int q = 0; q < parts; ++q) v -= red[q * ne + tid]; Cl[tid] = v; }
                 } else {
-                    for (int e = tid; e < 256; e += NTH) { double v = g.ws[g.ocp + e]; for (int i = 0; i < g.N; ++i) v -= g.ws[g.ocp + (size_t)(1 + i) * 256 + e]; Cl[e] = v; }
+                    for (int e = tid; e < 256; e += NTH) { double v = g.ws[g.ocp + e]; for (int i = 0; i < g.N; ++i) v -= share(i, e); Cl[e] = v; }
                 }
             }
             __syncthreads();
@@ -1145,25 +1207,24 @@ int BcrSolver::build(int64_t n_band_, int bw_, int nbd_, int H_, std::string* er
         std::vector<int> next; for (size_t idx = 1 - first; idx < m; idx += 2) next.push_back(active[idx]);
         active.swap(next);
     }
-    {   // the root block
+    {   // the root block: no update launch -- nothing of the forward pass reads what it would write.  The root's share of the corner and its pre-multiplied
+        // factor are formed by the backward pass's root workgroup (bcr_backward_kernel), which alone reads them
         BcrLevel lv; lv.elim_off = elims.size(); lv.upd_off = upds.size();
         lv.o = active[0]; lv.s = 1; lv.m = 1; lv.first = 0;
         slot_of[active[0]] = 0;
         elims.push_back(BcrElim{active[0], -1, -1, 0});
-        if (nbd > 0) corner_job(active[0]);
-        premul_jobs(elims.back());
-        lv.nelim = 1; lv.nupd = (int)(upds.size() - lv.upd_off);
+        lv.nelim = 1; lv.nupd = 0;
         levels.push_back(lv);
     }
     if (hipSuccess != ws.alloc(off) || hipSuccess != d_elim.upload(elims) || hipSuccess != d_upd.upload(upds)) { if (err) *err = "block cyclic reduction workspace alloc"; return NLLS_ERR_HIP; }
     if (hipSuccess != hipMemset(ws.p, 0, off * sizeof(double))) { if (err) *err = "workspace memset"; return NLLS_ERR_HIP; }
     fused_backward = !sw.bcr_level_backward;                   // (off: one backward launch per level, as in round 2)
-    // (the dispatch order of workgroups is not a contract: the fused pass is taken only while ALL its workgroups are resident at once -- 23 KB of LDS
-    //  and 5 wavefronts each, six per CU -- so that nothing waits on a workgroup that has not started)
+    // (the dispatch order of workgroups is not a contract: the fused pass is taken only while ALL its workgroups are resident at once -- 30 KB of LDS
+    //  (back_lds at NT = 5, the root's corner share included) and 5 wavefronts each, five per CU of 160 KB -- so that nothing waits on a workgroup that has not started)
     if (N > 4 * 256) fused_backward = false;
     geom.ws = ws.p;
     panel_lds = sizeof(double) * ((size_t)(ND + BCR_CH * NT) * BTS + 2 * (size_t)(NT + BCR_CH) * 16 * BP + 64 + 2 * 16 * BP + BTS + 128);
-    back_lds = sizeof(double) * ((size_t)RXT * 16 + NT * 64 + 2 * NT * 16 + (size_t)NO * 256 + 256 + 16);
+    back_lds = sizeof(double) * ((size_t)RXT * 16 + NT * 64 + 2 * NT * 16 + (size_t)NO * 256 + 256 + 16 + 256);
     chrows_slots = sw.bcr_chrows_slots;
     launches = 1; for (auto& lv : levels) launches += 1 + (lv.nupd > 0) + (fused_backward ? 0 : 1);
     launches += fused_backward ? 1 : 0;
@@ -1189,6 +1250,7 @@ int BcrSolver::build(int64_t n_band_, int bw_, int nbd_, int H_, std::string* er
             }
         }
         for (const BcrUpd& u : upds) mfma_issued += u.mode == 3 ? 4 : 4 * (int64_t)NT * u.nc;
+        mfma_issued += 4 * (NT + NO) + (nbd > 0 ? 4 * NT : 0);                 // the backward pass's root workgroup: the root's NT + NO pre-multiplied tiles, its share of the corner
     }
     ready = true;
     return NLLS_OK;

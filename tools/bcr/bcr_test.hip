@@ -1,14 +1,19 @@
 // Stand-alone check + timing of the block cyclic reduction solver (nlls_bcr.hip) against a CPU bordered-band LDL'.
-// build: hipcc -O3 -std=c++20 --offload-arch=gfx950 -o tools/bcr/bcr_test tools/bcr/bcr_test.hip ; run on the GPU box.
+// build: hipcc -O3 -std=c++20 --offload-arch=gfx950 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form -o tools/bcr/bcr_test tools/bcr/bcr_test.hip (__graft_entry__.build() does); run on the GPU box.
+// bcr_test: the case list below; bcr_test n bw nbd [reps [level]]: that case alone (level: per-level backward launches); bcr_test list ...: several.  Every case: x against the CPU, and x of the
+// last of its repeated solves against x of the first, bit for bit.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
 #include "../../nllssolver.jl_amd/csrc/nlls_bcr.hip"
 
 using namespace nlls;
+
+#define CHK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { printf("%s: %s\n", #expr, hipGetErrorString(e_)); return 1; } } while (0)
 
 static double cpu_solve(int n, int bw, int nbd, int H, const std::vector<double>& Sb, std::vector<double>& x) {
     const int nbr = nbd + 1;
@@ -41,7 +46,7 @@ static double cpu_solve(int n, int bw, int nbd, int H, const std::vector<double>
     return 0;
 }
 
-static int run_case(int n, int bw, int nbd, int reps, unsigned seed) {
+static int run_case(int n, int bw, int nbd, int reps, unsigned seed, bool level_backward = false) {
     const int H = bw + 1 + nbd + 1, nbr = nbd + 1;
     std::mt19937_64 rng(seed); std::uniform_real_distribution<double> U(-1.0, 1.0);
     std::vector<double> Sb((size_t)n * H + (size_t)nbr * nbr, 0.0);
@@ -56,38 +61,52 @@ static int run_case(int n, int bw, int nbd, int reps, unsigned seed) {
     std::vector<double> xc; cpu_solve(n, bw, nbd, H, Sb, xc);
     if (!BcrSolver::supports(n, bw, nbd)) { printf("case n=%d bw=%d nbd=%d: unsupported\n", n, bw, nbd); return 0; }
     BcrSolver S; std::string err;
-    if (S.build(n, bw, nbd, H, &err, Switches{}) != 0) { printf("build failed: %s\n", err.c_str()); return 1; }
+    Switches sw{}; sw.bcr_level_backward = level_backward;       // (one backward launch per level instead of the fused one: NLLS_BCR_LEVEL_BACKWARD=1 of the library)
+    if (S.build(n, bw, nbd, H, &err, sw) != 0) { printf("build failed: %s\n", err.c_str()); return 1; }
     if (grant_bcr_lds(S) != hipSuccess) { printf("LDS grant failed\n"); return 1; }
     double *dS, *dx; int* dst;
-    hipMalloc(&dS, Sb.size() * 8); hipMalloc(&dx, (n + nbd + 16) * 8); hipMalloc(&dst, 512);
-    hipMemcpy(dS, Sb.data(), Sb.size() * 8, hipMemcpyHostToDevice); hipMemset(dst, 0, 512); hipMemset(dx, 0, (n + nbd + 16) * 8);
-    hipStream_t st; hipStreamCreate(&st);
-    S.enqueue(st, dS, dx, dst);
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { printf("kernel failed: %s\n", hipGetErrorString(e)); return 1; }
+    CHK(hipMalloc(&dS, Sb.size() * 8)); CHK(hipMalloc(&dx, (n + nbd + 16) * 8)); CHK(hipMalloc(&dst, 512));
+    CHK(hipMemcpy(dS, Sb.data(), Sb.size() * 8, hipMemcpyHostToDevice)); CHK(hipMemset(dst, 0, 512)); CHK(hipMemset(dx, 0, (n + nbd + 16) * 8));
+    hipStream_t st; CHK(hipStreamCreate(&st));
+    if (S.enqueue(st, dS, dx, dst) != 0) { printf("enqueue failed\n"); return 1; }
+    CHK(hipStreamSynchronize(st));
     std::vector<double> xg(n + nbd); int status[80];
-    hipMemcpy(xg.data(), dx, (n + nbd) * 8, hipMemcpyDeviceToHost); hipMemcpy(status, dst, 320, hipMemcpyDeviceToHost);
+    CHK(hipMemcpy(xg.data(), dx, (n + nbd) * 8, hipMemcpyDeviceToHost)); CHK(hipMemcpy(status, dst, 320, hipMemcpyDeviceToHost));
 #ifdef BCR_STAMPS
     for (int w = 0; w < 2; ++w) { printf("   stamps wave %d:", w); for (int i = 0; i < 20; ++i) printf(" %d", status[16 + 20 * w + i]); printf("\n"); }
     printf("   arrivals at barrier B, J=0:"); for (int i = 0; i < 8; ++i) printf(" %d", status[56 + i]); printf("   J=1:"); for (int i = 0; i < 8; ++i) printf(" %d", status[64 + i]); printf("\n");
 #endif
+    if (const char* dump = getenv("BCR_TEST_DUMP")) { FILE* f = fopen(dump, "wb"); if (!f || fwrite(xg.data(), 8, xg.size(), f) != xg.size()) { printf("cannot write %s\n", dump); return 1; } fclose(f); }      // x of the first solve, raw: two builds compare with cmp
     double num = 0, den = 0; int worst = -1;
     for (int i = 0; i < n + nbd; ++i) { const double d = std::fabs(xg[i] - xc[i]); if (d > num || d != d) { num = d; worst = i; } den = std::max(den, std::fabs(xc[i])); }
-    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) S.enqueue(st, dS, dx, dst);
-    hipEventRecord(e0, st);
-    for (int i = 0; i < reps; ++i) S.enqueue(st, dS, dx, dst);
-    hipEventRecord(e1, st); hipEventSynchronize(e1);
-    float ms = 0; hipEventElapsedTime(&ms, e0, e1);
-    const bool ok = num <= 1e-9 * den && status[0] == 0;
-    printf("case n=%5d bw=%3d nbd=%2d  N=%4d NT=%d levels=%2zu launches=%2d  err=%.3e (|x|=%.3e, worst %d) status=%d  %.1f us/solve  %s\n",
-           n, bw, nbd, S.N, S.NT, S.levels.size(), S.launches, num, den, worst, status[0], 1e3 * ms / reps, ok ? "OK" : "FAIL");
+    hipEvent_t e0, e1; CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
+    int rc = 0;
+    for (int i = 0; i < 3; ++i) rc |= S.enqueue(st, dS, dx, dst);
+    CHK(hipEventRecord(e0, st));
+    for (int i = 0; i < reps; ++i) rc |= S.enqueue(st, dS, dx, dst);
+    CHK(hipEventRecord(e1, st)); CHK(hipEventSynchronize(e1));
+    float ms = 0; CHK(hipEventElapsedTime(&ms, e0, e1));
+    // the same system solved again (3 + reps times): no atomics anywhere in the cyclic reduction, so x of the last solve must be x of the first, bit for bit, and the status still 0
+    std::vector<double> xl(n + nbd); int status2[4];
+    CHK(hipMemcpy(xl.data(), dx, (n + nbd) * 8, hipMemcpyDeviceToHost)); CHK(hipMemcpy(status2, dst, 16, hipMemcpyDeviceToHost));
+    const bool same = memcmp(xl.data(), xg.data(), (size_t)(n + nbd) * 8) == 0;
+    const bool ok = num <= 1e-9 * den && status[0] == 0 && status2[0] == 0 && rc == 0 && same;
+    printf("case n=%5d bw=%3d nbd=%2d  N=%4d NT=%d levels=%2zu launches=%2d %s  err=%.3e (|x|=%.3e, worst %d) status=%d  repeat=%s  %.1f us/solve  %s\n",
+           n, bw, nbd, S.N, S.NT, S.levels.size(), S.launches, S.fused_backward ? "fused" : "per-level", num, den, worst, status[0] | status2[0], same ? "identical" : "DIFFERS", 1e3 * ms / reps, ok ? "OK" : "FAIL");
     hipFree(dS); hipFree(dx); hipFree(dst); hipStreamDestroy(st);
     return ok ? 0 : 1;
 }
 
 int main(int argc, char** argv) {
     int fails = 0;
+    // bcr_test n bw nbd [reps [level]]: that case alone, "level" = one backward launch per level (the stamps of a -DBCR_STAMPS build are the first solve's; -DBCR_STAMP_M=<chain length> selects the level)
+    // bcr_test list n bw nbd fused|level [n bw nbd fused|level ...]: those cases in one process, two timed solves each (tests/test_gpu_bcr_panel.py)
+    if (argc >= 2 && !strcmp(argv[1], "list")) {
+        if ((argc - 2) % 4 != 0 || argc < 6) { printf("usage: bcr_test list n bw nbd fused|level ...\n"); return 2; }
+        for (int a = 2; a < argc; a += 4) fails += run_case(atoi(argv[a]), atoi(argv[a + 1]), atoi(argv[a + 2]), 2, 11 + a, !strcmp(argv[a + 3], "level"));
+        printf(fails ? "FAILED %d\n" : "all ok\n", fails); return fails ? 1 : 0;
+    }
+    if (argc >= 4) { const int rc = run_case(atoi(argv[1]), atoi(argv[2]), atoi(argv[3]), argc >= 5 ? atoi(argv[4]) : 200, 11, argc >= 6 && !strcmp(argv[5], "level")); printf(rc ? "FAILED\n" : "all ok\n"); return rc; }
     const int cases[][3] = {{16, 5, 0}, {80, 65, 0}, {81, 65, 0}, {160, 65, 0}, {200, 17, 3}, {128, 5, 0}, {333, 40, 1}, {600, 65, 0}, {1000, 80, 15},
                             {3000, 65, 1}, {6000, 65, 0}, {6000, 65, 2}, {60000, 65, 0}, {5000, 33, 0}, {777, 1, 0}, {4096, 64, 7}};
     unsigned seed = 1;
