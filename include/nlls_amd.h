@@ -319,6 +319,33 @@ int  nlls_eval_blocks(nlls_ctx* ctx, int32_t which, int32_t group, double* r_out
  * Under nlls_set_shard with nranks > 1 (not replicas): NLLS_ERR_UNSUPPORTED. */
 int  nlls_adaptive_em(nlls_ctx* ctx, int32_t which, int64_t kernel_var, int32_t maxiters, double storage_out[3], int32_t* iters_out);
 
+/* ---- the linearisation of single cost blocks -----------------------------------------------------------------------------
+ * What the sweeps sum into A.data and b, per block and before any sum: to inspect the Jacobian of one outlier block, to hand J to a solver of the caller's own, to
+ * propagate a measurement covariance, to check a user residual header against finite differences.
+ * Both calls: `group`, `n`, `index` as in nlls_set_cost_data -- index[i] is 1-based, in the caller's upload order of that group; index == NULL: the first n blocks.
+ * Nothing is written through the index: it may be in any order and may name a block more than once.  Output record i belongs to index[i].  Evaluated at variable set
+ * `which` with EVERY slot treated as free (the kept entries of a varflags specialisation are identical: drop the rows and columns of fixed slots); blocks whose
+ * variables are all fixed are evaluated like the others.  Derivatives are with respect to the tangent of update() at 0.  One launch, no atomics: two calls return
+ * identical bytes.  Any output pointer may be NULL; all NULL is NLLS_ERR_INVALID_ARG.  n == 0: NLLS_OK.  NLLS_ERR_INVALID_ARG -- nothing enqueued, no output byte
+ * written -- for a bad group, n < 0, n > ncost with index == NULL, or an index outside 1 .. ncost.  NLLS_ERR_UNSUPPORTED: nlls_eval_jacobians on a non-squared cost
+ * kind (NLLS_COST_LINEAR3: it has no residual); both calls on the dynamic-size kinds (their Jacobian is their own payload); both calls under nlls_set_shard with
+ * nranks > 1 (a rank holds only its own blocks).  Need an upload, no sweep (NLLS_ERR_NOT_READY before one); read only, like nlls_eval_blocks: no validity state of
+ * the context changes, scratch of their own, a call between a sweep and a trial leaves the trial as it was.  Synchronous on return.
+ *
+ * replaces: computeresjac(varflags = all free, residual, vars...)  src/autodiff.jl:78-93, src/NLLSsolver.jl:16
+ *   r_out[i * M + m]              the residual, the same values as nlls_eval_blocks' r (M = nlls_res_nres),
+ *   J_out[i * M * NJ + m + M * j] the Jacobian, column-major M x NJ: NJ = nlls_res_jac_cols = the sum of the dof of the non-kernel slots, in slot order. */
+int  nlls_eval_jacobians(nlls_ctx* ctx, int32_t which, int32_t group, int64_t n, const int64_t* index, double* r_out, double* J_out);
+/* replaces: computecostgradhess / computerescostgradhess, all variables free  src/residual.jl:57-111, src/autodiff.jl:144-159
+ *   cost_out[i]        0.5 rho (a non-squared cost kind: the value itself),
+ *   g_out[i * P ..]    the robustified gradient, P = nlls_res_gh_dim,
+ *   H_out[i * P * P ..] the robustified Hessian, full symmetric, column-major P x P.
+ * Adaptive kinds: P = NJ + 3, the kernel's three entries first, the border as src/residual.jl:79-88,103-107.  NLLS_COST_LINEAR3: value, gradient and Hessian of the cost. */
+int  nlls_eval_gradhess(nlls_ctx* ctx, int32_t which, int32_t group, int64_t n, const int64_t* index, double* cost_out, double* g_out, double* H_out);
+/* static helpers, no context: columns of J; length of g (= order of H).  Negative (NLLS_ERR_UNSUPPORTED) for an unknown or a dynamic-size kind. */
+int  nlls_res_jac_cols(int32_t res_kind);
+int  nlls_res_gh_dim(int32_t res_kind);
+
 /* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
  * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
  *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.
@@ -380,7 +407,9 @@ int  nlls_solve(nlls_ctx* ctx, double* x_out);
  * elimination assembles through slabs + gather (NLLS_FLAG_DETERMINISTIC took effect).  Accumulate sweep, summed over cost groups and their slots:
  * [37] light tiles, [38] heavy tiles that carry an LDS image, [39] heavy tiles that write straight to memory (rows too long for an image), [40] tiles (light or
  * heavy) whose rows are shared or split and flushed with atomics, [41] cost groups swept folded, [42] cost groups the last full accumulate sweep ran as one fused
- * launch (0 before the first sweep). */
+ * launch (0 before the first sweep).  nlls_eval_jacobians / nlls_eval_gradhess: [43] doubles of LDS in which a wavefront stages its lanes' records before it
+ * writes them out contiguously, [44], [45], [46] lanes of a wavefront staged at a time for the J / g / H of the last call that asked for them (64: all at once;
+ * 0: stored directly, or not asked for yet). */
 int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
 /* Run-time switches of a context (A/B measurements, parity tests through both paths on ONE upload):
  *   NLLS_OPT_MATERIALIZE  value != 0: nlls_lm_trial eliminates from the materialised A.data (the round-5 path) although the structure qualifies for the
@@ -394,7 +423,8 @@ int  nlls_get_time_buckets(nlls_ctx* ctx, int64_t* out, int32_t n);
 #define NLLS_OPT_PHASE_EVENTS 3   /* value != 0: the COLLECTIVE nlls_lm_trial records stream events at its phase boundaries (resets the sums); nlls_get_phase_times reads them */
 /* out[0..4]: milliseconds summed over the trials since NLLS_OPT_PHASE_EVENTS was set -- [0] this rank's assembly of [S | s] (elimination), [1] the all-reduce of [S | s] (wait included),
  * [2] the reduced solve (every rank), [3] back-substitution + retraction, [4] trial tail (statistics, cost sweep, the scalars' gather); [5] gradient sweeps (ms summed), [6] trials, [7] sweeps counted.
- * [8] milliseconds of the last nlls_set_cost_data's scatter launch alone (an event pair around it, while the option is set; waits for it), [9] the device copies of the payload the last such launch wrote. */
+ * [8] milliseconds of the last nlls_set_cost_data's scatter launch alone (an event pair around it, while the option is set; waits for it), [9] the device copies of the payload the last such launch wrote.
+ * [10] milliseconds of the last nlls_eval_jacobians / nlls_eval_gradhess launch alone (the same: an event pair, while the option is set), [11] the bytes of records that call's launch wrote. */
 int  nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n);
 int  nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value);
 int  nlls_set_step(nlls_ctx* ctx, const double* x);               /* host-formed steps (dogleg, GD) */

@@ -32,7 +32,8 @@ nlls_get_step nlls_step_maxabs nlls_step_norm nlls_quadform nlls_retract nlls_sw
 nlls_sweep_gradhess_finish nlls_sweep_cost_local nlls_sweep_cost_finish nlls_solve_local nlls_solve_finish
 nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_owned nlls_trial_local nlls_solve_finish_async nlls_lm_trial nlls_optimize_singles nlls_time_sweep_gradhess nlls_time_sweep_accumulate nlls_time_sweep_cost nlls_time_solve nlls_time_reduced_solve nlls_profile_sweep nlls_profile_sweep_dispatch nlls_solve_finish_replicated nlls_get_variables_owned nlls_lm_iterations
 nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
-nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params""".split()
+nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
+nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -127,6 +128,8 @@ def lib():
         L.nlls_set_option.argtypes = [vp, i32, i64]; L.nlls_get_time_buckets.argtypes = [vp, vp, i32]; L.nlls_get_phase_times.argtypes = [vp, vp, i32]
         L.nlls_eval_blocks.argtypes = [vp, i32, i32, vp, vp, vp, vp]; L.nlls_adaptive_em.argtypes = [vp, i32, i64, i32, vp, vp]
         L.nlls_set_cost_data.argtypes = [vp, i32, i64, vp, vp]; L.nlls_set_robust_params.argtypes = [vp, i32, vp]
+        L.nlls_eval_jacobians.argtypes = [vp, i32, i32, i64, vp, vp, vp]; L.nlls_eval_gradhess.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp]
+        L.nlls_res_jac_cols.argtypes = [i32]; L.nlls_res_gh_dim.argtypes = [i32]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -190,6 +193,7 @@ class Context:
             for k in range(4):
                 arr[i].robust_params[k] = float(rp[k])
             arr[i].ncost = vi.shape[0]; arr[i].varind = vi.ctypes.data; arr[i].data = da.ctypes.data
+        self._kinds = [int(g["res_kind"]) for g in groups]      # (eval_jacobians / eval_gradhess: the record sizes of a group's kind)
         self._groups = []; self._ndata = [int(da.size // max(vi.shape[0], 1)) for vi, da in zip(keep[3::2], keep[4::2])]     # doubles of payload per block, per group (set_cost_data)
         self._chk(self.L.nlls_upload_structure(self.h, len(vk), _p(vk), _p(vd), _p(bi), len(groups), arr, flags))
         for i, g in enumerate(groups):             # (ncost, residuals per block) of every group, for eval_blocks; a dynamic kind's nres is its variable's run-time length
@@ -246,6 +250,40 @@ class Context:
         n, nres = (g if g is not None else (0, 1))
         out = {k: np.zeros((n, nres) if k == "r" else n) for k in want}
         self._chk(self.L.nlls_eval_blocks(self.h, int(which), int(group), *(_p(out.get(k)) if k in out else None for k in ("r", "sqerr", "rho", "weight"))))
+        return out
+
+    def _lin_select(self, group, index):
+        """(n, index array or None, res_kind) of a selection of blocks of `group`: index 1-BASED, any order, repeats allowed; None: every block"""
+        ncost = self._groups[group][0] if 0 <= group < len(self._groups) else 0
+        kind = self._kinds[group] if 0 <= group < len(self._groups) else -1
+        ix = None if index is None else np.ascontiguousarray(index, np.int64).ravel()
+        return (int(ix.size) if ix is not None else ncost), ix, kind
+
+    def eval_jacobians(self, group, which=VARS_CURRENT, index=None, want=("r", "J")):
+        """nlls_eval_jacobians: computeresjac of blocks of cost group `group` (0-based) at variable set `which`, every slot free -- a dict with the entries of `want`:
+        "r" (n, M) the residual and "J" (n, M, NJ), J[i, m, j] = d r_m / d (tangent entry j of the non-kernel slots, in slot order).  index: 1-BASED blocks in upload
+        order (any order, repeats allowed), None: every block; record i belongs to index[i]."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        assert want and set(want) <= {"r", "J"}
+        n, ix, kind = self._lin_select(group, index)
+        M, NJ = max(self.L.nlls_res_nres(kind), 0), max(self.L.nlls_res_jac_cols(kind), 0)
+        out = {k: np.zeros((n, M) if k == "r" else (n, NJ, M)) for k in want}           # (J comes column-major: M x NJ per block)
+        self._chk(self.L.nlls_eval_jacobians(self.h, int(which), int(group), n, _p(ix), _p(out.get("r")), _p(out.get("J"))))
+        if "J" in out:
+            out["J"] = np.ascontiguousarray(out["J"].transpose(0, 2, 1))
+        return out
+
+    def eval_gradhess(self, group, which=VARS_CURRENT, index=None, want=("cost", "g", "H")):
+        """nlls_eval_gradhess: computecostgradhess of blocks of cost group `group` (0-based) at variable set `which`, every slot free -- "cost" (n,) 0.5 rho (a cost kind:
+        the value), "g" (n, P) the robustified gradient, "H" (n, P, P) the robustified Hessian; adaptive kinds: the kernel's three entries first.  index as in eval_jacobians."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        assert want and set(want) <= {"cost", "g", "H"}
+        n, ix, kind = self._lin_select(group, index)
+        P = max(self.L.nlls_res_gh_dim(kind), 0)
+        out = {k: np.zeros({"cost": (n,), "g": (n, P), "H": (n, P, P)}[k]) for k in want}
+        self._chk(self.L.nlls_eval_gradhess(self.h, int(which), int(group), n, _p(ix), _p(out.get("cost")), _p(out.get("g")), _p(out.get("H"))))
+        if "H" in out:
+            out["H"] = np.ascontiguousarray(out["H"].transpose(0, 2, 1))                 # (column-major P x P per block -> H[i, row, column])
         return out
 
     def adaptive_em(self, kernel_var=1, which=VARS_NEXT, maxiters=10):
@@ -378,10 +416,11 @@ class Context:
 
     def phase_times(self):
         """nlls_get_phase_times: microseconds per collective trial by phase (stream events; NLLS_OPT_PHASE_EVENTS) and per gradient sweep"""
-        out = np.zeros(10); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 10)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
+        out = np.zeros(12); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 12)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
         return dict(trials=int(out[6]), sweeps=int(out[7]), elimination_us=1e3 * out[0] / nt, allreduce_S_us=1e3 * out[1] / nt, reduced_solve_us=1e3 * out[2] / nt,
                     backsub_retraction_us=1e3 * out[3] / nt, trial_tail_us=1e3 * out[4] / nt, gradient_sweep_us=1e3 * out[5] / ns,
-                    update_scatter_us=1e3 * out[8], update_copies=int(out[9]))
+                    update_scatter_us=1e3 * out[8], update_copies=int(out[9]),
+                    linearize_us=1e3 * out[10], linearize_bytes=int(out[11]))
 
     def time_buckets(self):
         """device-timed NLLSResult buckets since the upload: seconds (gradient, cost, solver) and the trials counted"""
@@ -389,7 +428,7 @@ class Context:
         return dict(timegradient=out[0] * 1e-9, timecost=out[1] * 1e-9, timesolver=out[2] * 1e-9, trials=int(out[3]))
 
     def solve_stats(self):
-        out = np.zeros(43, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 43))
+        out = np.zeros(47, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 47))
         return dict(status=int(out[0]), band_factor_cycles=int(out[1]), band_backward_cycles=int(out[2]), solve_mode=int(out[3]),
                     elim_supernodes=int(out[4]), bandwidth=int(out[5]), bcr_mfma_issued=int(out[6]), bcr_launches=int(out[7]), bcr_levels=int(out[8]),
                     band_dof=int(out[9]), dropped_pivots=int(out[10]), reduced_row_sums=int(out[11]), lazy_trials=int(out[12]),
@@ -402,7 +441,9 @@ class Context:
                     elim_fast60=int(out[29]), elim_fast_narrow=int(out[30]), elim_fast_wide=int(out[31]), elim_slow_acc=int(out[32]), elim_slow_noacc=int(out[33]),
                     elim_nbrs_transposed=int(out[34]), elim_nbrs=int(out[35]), elim_slab=int(out[36]),
                     sweep_light_tiles=int(out[37]), sweep_image_tiles=int(out[38]), sweep_direct_tiles=int(out[39]), sweep_partial_tiles=int(out[40]),
-                    sweep_fold_groups=int(out[41]), sweep_fused_groups=int(out[42]))
+                    sweep_fold_groups=int(out[41]), sweep_fused_groups=int(out[42]),
+                    # eval_jacobians / eval_gradhess: doubles of LDS a wavefront stages records in, lanes staged at a time for the last J / g / H asked for (0: stored directly)
+                    linearize_slab=int(out[43]), linearize_batch_J=int(out[44]), linearize_batch_g=int(out[45]), linearize_batch_H=int(out[46]))
 
     def set_step(self, x):
         x = np.ascontiguousarray(x, np.float64); assert x.size == self.info.ndof

@@ -35,6 +35,39 @@ int ensure_grad(nlls_ctx* ctx, int level) {
 // phase events (nlls_ctx::phase_on): record event k on the stream
 void phase_mark(nlls_ctx* ctx, int k) { if (ctx->phase_on && (size_t)k < ctx->phase_ev.size()) (void)hipEventRecord(ctx->phase_ev[k], ctx->stream); }
 // is this trial matrix-free?  (nlls_ctx::mf_ok: the structure qualifies; mf_on: not switched off; the trial starts at CURRENT, one rank, no collective route)
+// nlls_eval_jacobians / nlls_eval_gradhess: everything checked on the host before anything is enqueued or written; then the listed blocks to the device, one launch
+// (nlls_linearize.hip), the records home.  out[k] (null: not wanted) takes rec[k] doubles per block.  Reads only: no event of nlls_state.hpp.
+int linearize_call(nlls_ctx* ctx, const char* name, int32_t which, int32_t group, int64_t n, const int64_t* index, bool jac, double* const out[3]) {
+    const std::string nm(name);
+    if (!valid_set(which)) return fail(ctx, NLLS_ERR_INVALID_ARG, nm + ": bad variable set");
+    if (!out[0] && !out[1] && !out[2]) return fail(ctx, NLLS_ERR_INVALID_ARG, nm + ": no output asked for");
+    if (ctx->nranks > 1) return fail(ctx, NLLS_ERR_UNSUPPORTED, nm + " under nlls_set_shard: a rank holds only its own cost blocks");
+    if (group < 0 || group >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, nm + ": bad cost group");
+    const Group& G = ctx->groups[(size_t)group];
+    LinSizes s;
+    if (is_dyn_kind(G.res_kind) || !lin_sizes(G.res_kind, s)) return fail(ctx, NLLS_ERR_UNSUPPORTED, nm + ": the Jacobian of a dynamic-size kind is its own payload");
+    if (jac && s.m == 0) return fail(ctx, NLLS_ERR_UNSUPPORTED, nm + ": a non-squared cost kind has no residual");
+    if (n < 0 || (!index && n > G.ncost)) return fail(ctx, NLLS_ERR_INVALID_ARG, nm + ": n outside 0 .. ncost");
+    if (n == 0) return NLLS_OK;
+    std::vector<int64_t> blocks;                        // the listed blocks as they were checked (any order, repeats allowed: nothing is written through them)
+    if (index) { blocks.assign(index, index + n);
+        for (int64_t k : blocks) if (k < 1 || k > G.ncost) return fail(ctx, NLLS_ERR_INVALID_ARG, nm + ": index outside 1 .. ncost"); }
+    const size_t rec[3] = {jac ? (size_t)s.m : 1, jac ? (size_t)s.m * (size_t)s.nj : (size_t)s.p, jac ? 0 : (size_t)s.p * (size_t)s.p};
+    size_t need = 0, off[3]; double bytes = 0;
+    for (int k = 0; k < 3; ++k) { off[k] = need; if (out[k]) { need += (size_t)n * rec[k]; bytes += 8.0 * (double)n * (double)rec[k]; } }
+    // (DevBuf::alloc records the new size before it allocates: a buffer that could not be had is released, so that the next call asks again instead of launching on null)
+    if (ctx->lin_out.n < need || !ctx->lin_out.p) { const hipError_t e = ctx->lin_out.alloc(need); if (e != hipSuccess) { ctx->lin_out.release(); (void)hipGetLastError(); return hip_fail(ctx, e, (nm + ": scratch for the records").c_str()); } }
+    if (index && (ctx->lin_index.n < (size_t)n || !ctx->lin_index.p)) { const hipError_t e = ctx->lin_index.alloc((size_t)n); if (e != hipSuccess) { ctx->lin_index.release(); (void)hipGetLastError(); return hip_fail(ctx, e, (nm + ": scratch for the index").c_str()); } }
+    if (index) HIP_TRY(ctx, hipMemcpyAsync(ctx->lin_index.p, blocks.data(), sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    double* d[3]; for (int k = 0; k < 3; ++k) d[k] = out[k] ? ctx->lin_out.p + off[k] : nullptr;
+    if (jac) TRY(enqueue_linearize(ctx, G, which, n, index ? ctx->lin_index.p : nullptr, d[0], d[1], nullptr, nullptr, nullptr));
+    else TRY(enqueue_linearize(ctx, G, which, n, index ? ctx->lin_index.p : nullptr, nullptr, nullptr, d[0], d[1], d[2]));
+    if (ctx->phase_on) ctx->lin_bytes = bytes;          // (beside the event pair: nlls_get_phase_times [10], [11])
+    if (jac) { if (out[1]) ctx->lin_batch[0] = s.batch_j; } else { if (out[1]) ctx->lin_batch[1] = s.batch_g; if (out[2]) ctx->lin_batch[2] = s.batch_h; }
+    for (int k = 0; k < 3; ++k) if (out[k]) HIP_TRY(ctx, hipMemcpyAsync(out[k], d[k], sizeof(double) * (size_t)n * rec[k], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (`blocks` and the caller's arrays are in use until here)
+    return NLLS_OK;
+}
 bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->sw.mf_on && !ctx->lin.stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
 }  // namespace
 
@@ -107,6 +140,8 @@ int nlls_robust_nparams(int32_t k) { NLLS_API_BEGIN return robust_nparams(k) >= 
 int nlls_res_ndeps(int32_t k) { NLLS_API_BEGIN ResDesc d; return res_desc(k, d) ? d.ndeps : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
 int nlls_res_nres(int32_t k) { NLLS_API_BEGIN ResDesc d; return res_desc(k, d) ? d.nres : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
 int nlls_res_ndata(int32_t k) { NLLS_API_BEGIN ResDesc d; return res_desc(k, d) ? d.ndata : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
+int nlls_res_jac_cols(int32_t k) { NLLS_API_BEGIN LinSizes z; return lin_sizes(k, z) ? z.nj : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
+int nlls_res_gh_dim(int32_t k) { NLLS_API_BEGIN LinSizes z; return lin_sizes(k, z) ? z.p : NLLS_ERR_UNSUPPORTED; NLLS_API_END(nullptr) }
 int nlls_res_slot_kind(int32_t k, int32_t slot, int32_t* vk, int32_t* vd) { NLLS_API_BEGIN
     ResDesc d; if (!res_desc(k, d)) return NLLS_ERR_UNSUPPORTED;
     if (slot < 0 || slot >= d.ndeps) return NLLS_ERR_INVALID_ARG;
@@ -288,6 +323,19 @@ int nlls_eval_blocks(nlls_ctx* ctx, int32_t which, int32_t group, double* r_out,
     if (weight_out) HIP_TRY(ctx, hipMemcpyAsync(weight_out, d_w, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+// computeresjac / computecostgradhess of the listed blocks of one cost group, every slot free (nlls_linearize.hip).  Read only, like nlls_eval_blocks.
+int nlls_eval_jacobians(nlls_ctx* ctx, int32_t which, int32_t group, int64_t n, const int64_t* index, double* r_out, double* J_out) { NLLS_API_BEGIN
+    NEED_READY();
+    double* const out[3] = {r_out, J_out, nullptr};
+    return linearize_call(ctx, "nlls_eval_jacobians", which, group, n, index, true, out);
+    NLLS_API_END(ctx)
+}
+int nlls_eval_gradhess(nlls_ctx* ctx, int32_t which, int32_t group, int64_t n, const int64_t* index, double* cost_out, double* g_out, double* H_out) { NLLS_API_BEGIN
+    NEED_READY();
+    double* const out[3] = {cost_out, g_out, H_out};
+    return linearize_call(ctx, "nlls_eval_gradhess", which, group, n, index, false, out);
     NLLS_API_END(ctx)
 }
 // optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)  src/robustadaptive.jl:48-73 on the device (nlls_eval.hip): one synchronisation
@@ -632,8 +680,11 @@ int nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
     if (!ctx || !out || n < 1) return NLLS_ERR_INVALID_ARG;
     if (take(ctx->upd_pending) && ctx->phase_ev.size() >= 10) { float ms = 0.f; (void)hipSetDevice(ctx->device);
         if (hipEventSynchronize(ctx->phase_ev[9]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[8], ctx->phase_ev[9]) == hipSuccess) ctx->upd_ms = ms; else (void)hipGetLastError(); }
-    const double v[10] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies};
-    for (int i = 0; i < n && i < 10; ++i) out[i] = v[i];
+    if (take(ctx->lin_pending) && ctx->phase_ev.size() >= 12) { float ms = 0.f; (void)hipSetDevice(ctx->device);
+        if (hipEventSynchronize(ctx->phase_ev[11]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[10], ctx->phase_ev[11]) == hipSuccess) ctx->lin_ms = ms; else (void)hipGetLastError(); }
+    const double v[12] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies,
+                          ctx->lin_ms, ctx->lin_bytes};
+    for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -644,7 +695,7 @@ int nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value) { NLLS_API_BEG
     case NLLS_OPT_LOOKAHEAD:   ctx->sw.spec_on = value != 0; return NLLS_OK;
     case NLLS_OPT_PHASE_EVENTS:
         ctx->phase_on = value != 0; (void)hipSetDevice(ctx->device);
-        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(10); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
+        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(12); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
         if (ctx->phase_on) { for (double& v : ctx->phase_ms) v = 0.0; ctx->phase_trials = ctx->phase_sweeps = 0; }
         return NLLS_OK;
     }
@@ -656,7 +707,7 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
     int32_t status[16] = {0};
     HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t vals[43] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
+    const int64_t vals[47] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
@@ -670,8 +721,10 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
                               ctx->n_elim_nbrs_trans, ctx->n_elim_nbrs, ctx->elim_slab ? 1 : 0,
                               // [37..42] the accumulate sweep, summed over groups (and slots): light tiles, heavy tiles with an LDS image, TILE_DIRECT tiles, TILE_PARTIAL tiles (light or heavy),
                               // folded groups, groups whose last full sweep was one fused launch
-                              ctx->n_tiles_light, ctx->n_tiles_image, ctx->n_tiles_direct, ctx->n_tiles_partial, ctx->n_fold_groups, ctx->sweep_fused_groups};
-    for (int i = 0; i < n && i < 43; ++i) out[i] = vals[i];
+                              ctx->n_tiles_light, ctx->n_tiles_image, ctx->n_tiles_direct, ctx->n_tiles_partial, ctx->n_fold_groups, ctx->sweep_fused_groups,
+                              // [43..46] nlls_eval_jacobians / nlls_eval_gradhess: doubles of LDS a wavefront stages records in; lanes per staged sub-batch of the last call's J / g / H (0: stored directly)
+                              lin_wave_slab(), ctx->lin_batch[0], ctx->lin_batch[1], ctx->lin_batch[2]};
+    for (int i = 0; i < n && i < 47; ++i) out[i] = vals[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

@@ -380,4 +380,9 @@ struct nlls_ctx {
     // the pair of the last launch has not been read yet (nlls_get_phase_times [8], [9])
     nlls::DevBuf<double> upd_stage; nlls::DevBuf<uint32_t> upd_index;
     bool upd_pending = false; double upd_ms = 0.0; int upd_copies = 0;     // upd_copies: device copies the last launch wrote
+    // nlls_eval_jacobians / nlls_eval_gradhess (nlls_linearize.hip): the call's records and the listed blocks (1-based, as they came from the host), scratch of their own like
+    // eval_out -- outside the arena, sized at first use and kept.  Under NLLS_OPT_PHASE_EVENTS the launch sits between phase_ev[10] and [11] (nlls_get_phase_times [10], [11]:
+    // milliseconds and bytes written of the last launch); lin_batch: lanes per staged sub-batch of the last call's J / g / H (nlls_get_solve_stats [44..46]; 0: stored directly)
+    nlls::DevBuf<double> lin_out; nlls::DevBuf<int64_t> lin_index;
+    bool lin_pending = false; double lin_ms = 0.0, lin_bytes = 0.0; int lin_batch[3] = {0, 0, 0};
 };

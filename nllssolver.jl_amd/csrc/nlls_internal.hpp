@@ -61,6 +61,11 @@ int enqueue_iters_to_double(nlls_ctx* c, const int64_t* d_it, const int64_t* d_p
 int eval_nres(const Group& G);                 // residuals per block of the group (dynamic kinds: the run-time n)
 int enqueue_eval_blocks(nlls_ctx* c, const Group& G, int which, double* d_r, double* d_sq, double* d_rho, double* d_w);
 int enqueue_adaptive_em(nlls_ctx* c, int which, uint32_t kvoff, int maxiters);
+// per-block linearisation (nlls_linearize.hip): n selected blocks of a group (d_index: their 1-based blocks on the device, null: the first n); device output pointers (null: not wanted)
+struct LinSizes { int m, nj, p; int batch_r, batch_j, batch_g, batch_h; };   // rows and columns of J (m 0: no residual), length of g; lanes per staged sub-batch of each output (0: stored directly)
+bool lin_sizes(int kind, LinSizes& s);         // false: unknown or dynamic-size kind
+int lin_wave_slab();                           // doubles of LDS a wavefront stages records in
+int enqueue_linearize(nlls_ctx* c, const Group& G, int which, int64_t n, const int64_t* d_index, double* d_r, double* d_J, double* d_cost, double* d_g, double* d_H);
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);

@@ -146,6 +146,23 @@ function blockvalues(ls::MultiVariateLSgpu, which::Integer, group::Integer, ncos
     check(ls.ctx, ccall((:nlls_eval_blocks, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, r, sqerr, rho, weight))
     return r, sqerr, rho, weight
 end
+# computeresjac (src/NLLSsolver.jl:16, src/autodiff.jl:78-93) of blocks of cost group `group` (0-based) at device variable set `which`, every variable of a block free: the
+# blocks `index` (1-based, the order of problem.costs.data[T]; any order, repeats allowed; nothing: the first n).  nres, ncols: nlls_res_nres / nlls_res_jac_cols of the
+# kind.  Returns r (nres x n) and J (nres x ncols x n): J[:, :, i] is the Jacobian of block index[i] in Julia's own column-major layout.
+function NLLSsolver.computeresjac(ls::MultiVariateLSgpu, which::Integer, group::Integer, n::Integer, nres::Integer, ncols::Integer, index::Union{Nothing, Vector{Int64}}=nothing)
+    n = index === nothing ? n : length(index)
+    r = zeros(nres, n); J = zeros(nres, ncols, n)
+    check(ls.ctx, ccall((:nlls_eval_jacobians, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, n, index === nothing ? C_NULL : index, r, J))
+    return r, J
+end
+# computecostgradhess / computerescostgradhess (src/residual.jl:57-111, src/autodiff.jl:144-159) of the same selection: cost (n), g (p x n), H (p x p x n) with
+# p = nlls_res_gh_dim of the kind (adaptive kinds: the kernel's three entries first), robustified, every variable free.
+function NLLSsolver.computecostgradhess(ls::MultiVariateLSgpu, which::Integer, group::Integer, n::Integer, p::Integer, index::Union{Nothing, Vector{Int64}}=nothing)
+    n = index === nothing ? n : length(index)
+    cost = zeros(n); g = zeros(p, n); H = zeros(p, p, n)
+    check(ls.ctx, ccall((:nlls_eval_gradhess, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, n, index === nothing ? C_NULL : index, cost, g, H))
+    return cost, g, H
+end
 # optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
 # re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
 function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)

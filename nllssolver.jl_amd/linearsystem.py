@@ -41,6 +41,14 @@ class MultiVariateLSgpu:
         """computeresidual / r'r / robustify / rho' of every block of a cost group, in the problem's order   src/NLLSsolver.jl:16, src/residual.jl:52"""
         return self.ctx.eval_blocks(group, which, want)
 
+    def eval_jacobians(self, group, which=VARS_CURRENT, index=None, want=("r", "J")):
+        """computeresjac of blocks of a cost group, every variable free (index 1-based, None: all; nlls_eval_jacobians)   src/autodiff.jl:78-93"""
+        return self.ctx.eval_jacobians(group, which, index, want)
+
+    def eval_gradhess(self, group, which=VARS_CURRENT, index=None, want=("cost", "g", "H")):
+        """computecostgradhess of blocks of a cost group, every variable free (index 1-based, None: all; nlls_eval_gradhess)   src/residual.jl:57-111"""
+        return self.ctx.eval_gradhess(group, which, index, want)
+
     def adaptive_em(self, kernel_var=1, which=VARS_NEXT, maxiters=10):
         """optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)   src/robustadaptive.jl:48-73"""
         return self.ctx.adaptive_em(kernel_var, which, maxiters)

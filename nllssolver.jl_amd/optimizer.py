@@ -310,6 +310,16 @@ class Solver:
         """as N.squarederrors"""
         return self._blockvalues(group, "sqerr")
 
+    def jacobians(self, group, index=None):
+        """as N.computeresjac, on the kept linear system"""
+        self._start()
+        return self.ls.eval_jacobians(int(group), VARS_CURRENT, _one_based(index))
+
+    def gradhess(self, group, index=None):
+        """as N.computecostgradhess, on the kept linear system"""
+        self._start()
+        return self.ls.eval_gradhess(int(group), VARS_CURRENT, _one_based(index))
+
     def set_data(self, group, data, index=None):
         """New data (measurements) for blocks of cost group `group` (0-based, the order of problem.costs): `data` (n x ndata) for the blocks `index` (0-BASED here, as
         `group` is; distinct) or, index=None, for the first n.  Written to the device (nlls_set_cost_data) and to the problem's CostGroup: the two never disagree."""
@@ -441,3 +451,69 @@ def residuals(problem, group=None, device=0):
 def squarederrors(problem, group=None, device=0):
     """r'r of every cost block at problem.variables -- cost(residual, vars) before the robust kernel, src/residual.jl:52; shaped like residuals()."""
     return _blockvalues(problem, group, "sqerr", device)
+
+
+def _one_based(index):
+    """a 0-BASED selection of blocks (None: all) as the library takes it"""
+    return None if index is None else np.asarray(index, np.int64).ravel() + 1
+
+
+def computeresjac(problem, group=0, index=None, unfixed=None, device=0):
+    """computeresjac of blocks of cost group `group` at problem.variables (src/NLLSsolver.jl:16, src/autodiff.jl:78-93): {"r": (n, M), "J": (n, M, NJ)} for the blocks
+    `index` (0-BASED, in the order the blocks were added; any order, repeats allowed; None: all).  Every variable of a block is treated as free, whatever `unfixed`
+    says (it only shapes the linear system that is built for the call): the columns are the tangent entries of the block's non-kernel variables, in slot order."""
+    ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
+    try:
+        return ls.eval_jacobians(int(group), VARS_CURRENT, _one_based(index))
+    finally:
+        ls.close()
+
+
+def computecostgradhess(problem, group=0, index=None, unfixed=None, device=0):
+    """computecostgradhess of blocks of cost group `group` at problem.variables (src/residual.jl:57-111, src/autodiff.jl:144-159): {"cost": (n,), "g": (n, P),
+    "H": (n, P, P)}, robustified, every variable of a block free; adaptive kinds carry the kernel's three entries first.  `index`, `unfixed` as computeresjac."""
+    ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
+    try:
+        return ls.eval_gradhess(int(group), VARS_CURRENT, _one_based(index))
+    finally:
+        ls.close()
+
+
+def jacobian(problem, unfixed=None, weighted=False, device=0):
+    """The Jacobian of the whole problem at problem.variables as COO triplets (rows, cols, vals, r): rows are residual rows in group order, then the order the blocks
+    were added, then m; cols are 0-based positions in the gradient b of the linear system (boffsets of nlls_get_bsm_index); the columns of fixed variables are dropped.
+    r is the stacked residual: J'J is the Gauss-Newton Hessian and J'r the gradient of an unrobustified problem.  weighted=True: each block's rows of J and r times
+    sqrt(rho') of its robust kernel (the IRLS weight of nlls_eval_blocks), so that the two products are the first-order robustified ones.  The values come from the
+    device (nlls_eval_jacobians); the indices are assembled here.  Adaptive, non-squared and dynamic-size groups have no such Jacobian: ValueError."""
+    from . import kinds as K
+    gl = list(problem.costs.values())
+    for gi, g in enumerate(gl):
+        if g.res_kind in K.ADAPTIVE_KINDS or g.res_kind in (K.COST_LINEAR3, K.COST_DYN_LINEAR, K.RES_DYN_LINEAR, K.RES_DYN_NORM, K.RES_DYN_LINEARSQ):
+            raise ValueError(f"jacobian: cost group {gi} is of an adaptive, non-squared or dynamic-size kind")
+    ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
+    try:
+        bo = np.asarray(ls.ctx.bsm_index()[3], np.int64) - 1; bi = np.asarray(ls.blockindices, np.int64)
+        vkind, vdim = problem.var_kind, problem.var_dim
+        rows, cols, vals, rs = [], [], [], []; row0 = 0
+        for gi, g in enumerate(gl):
+            vi, _ = g.arrays(); n = vi.shape[0]
+            if n == 0:
+                continue
+            out = ls.eval_jacobians(gi, VARS_CURRENT); J, r = out["J"], out["r"]; M = r.shape[1]
+            if weighted:
+                w = np.sqrt(ls.eval_blocks(gi, VARS_CURRENT, ("weight",))["weight"]); J = J * w[:, None, None]; r = r * w[:, None]
+            rr = row0 + M * np.arange(n)[:, None] + np.arange(M)[None, :]                   # (n, M) row of every residual entry
+            j0 = 0
+            for s in range(vi.shape[1]):
+                v = vi[:, s] - 1; dof = K.var_dof(int(vkind[v[0]]), int(vdim[v[0]])); free = bi[v] > 0
+                if np.any(free):
+                    cc = bo[bi[v[free]] - 1][:, None] + np.arange(dof)[None, :]             # (nfree, dof) column of every tangent entry
+                    rows.append(np.broadcast_to(rr[free][:, :, None], (cc.shape[0], M, dof)).ravel())
+                    cols.append(np.broadcast_to(cc[:, None, :], (cc.shape[0], M, dof)).ravel())
+                    vals.append(J[free][:, :, j0:j0 + dof].ravel())
+                j0 += dof
+            rs.append(r.ravel()); row0 += n * M
+        cat = lambda a, t: np.concatenate(a).astype(t) if a else np.zeros(0, t)
+        return cat(rows, np.int64), cat(cols, np.int64), cat(vals, np.float64), cat(rs, np.float64)
+    finally:
+        ls.close()
