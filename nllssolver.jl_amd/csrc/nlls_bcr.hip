@@ -343,6 +343,7 @@ __global__ __launch_bounds__(BCR_T) void bcr_panel_kernel(BcrPanelArgs a) {
     constexpr int LANDQ = (BCR_CH * (BCR_MAXNT - 1) * 256 + 6 * 64 - 1) / (6 * 64);      // words per helper thread of the deferred part
     double lv[LANDQ];
     const int nB = RX * (NT - 1) * 256;
+    bdouble4_t diag = {0, 0, 0, 0};                   // wave 0: the diagonal tile it factors next, in the accumulator layout (bcr_factor)
     if (helper) {
 #pragma unroll
         for (int q = 0; q < LANDQ; ++q) {
@@ -360,12 +361,25 @@ __global__ __launch_bounds__(BCR_T) void bcr_panel_kernel(BcrPanelArgs a) {
                 dv[q] = Dg[w]; } }
 #pragma unroll
         for (int q = 0; q < XQ; ++q) { const int w = tid + q * BCR_T; xv[q] = w < RX * 256 ? xsrc(rowRg(w >> 8), 0, (w >> 4) & 15, w & 15) : 0.0; }
+        // Tile column 0 has NO barrier of its own behind the landing.  Wave 0 takes the first diagonal tile of D_i (tile 0 of Dg, row-major) straight into the accumulator
+        // layout -- register r of lane (li, lk) = T[lk + 4 r][li], the words the from-LDS entry of bcr_factor would read back -- and, FLOOR, its sixteen floors as the same
+        // product flds holds (same operands, same bits).  The loads go out with its share of the landing loads: wave 0 has no store in flight yet, so nothing stands in
+        // front of them (what keeps the floors of columns 1 .. in LDS: flds above).  It factors column 0 from registers and reads no LDS word in front of barrier B of J = 0.
+        // Every LDS word read BEHIND that barrier is written in front of it, by a wave whose bcr_lds_barrier() has waited for its own LDS traffic (lgkmcnt(0)):
+        //   Dt, column 0 of Xt, flds  by the landing stores below, of all eight waves (wave 0's before it enters bcr_factor, wave 4's before it goes to the barrier);
+        //   columns 1 .. of Xt         by land_rest() of the six helper waves: words disjoint from the ones below, first read by the panel tiles of J = 1;
+        //   Wb row 0, Lid, db          by wave 0's bcr_factor: disjoint from all of the above (Wp, Li, dvec against Dt, Xt, flds).
+        // Nothing reads LDS in front of that barrier, so no store can overtake a read either.
+        if (wave == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) diag[r] = Dg[((lane >> 4) + 4 * r) * 16 + (lane & 15)];
+            if constexpr (FLOOR) flc = g.ws[g.odg + 16 * NT * job.i + (lane & 15)] * a.relfloor;
+        }
 #pragma unroll
         for (int q = 0; q < DQ; ++q) { const int w = tid + q * BCR_T; if (w < ND * 256) Dt[(w >> 8) * BTS + ((w >> 4) & 15) * BP + (w & 15)] = dv[q]; }
 #pragma unroll
         for (int q = 0; q < XQ; ++q) { const int w = tid + q * BCR_T; if (w < RX * 256) *xdst(w >> 8, rowRg(w >> 8), 0, (w >> 4) & 15, w & 15) = xv[q]; }
     }
-    __syncthreads();
     BCR_STAMP();
     auto land_rest = [&]() {
 #pragma unroll
@@ -410,11 +424,11 @@ __global__ __launch_bounds__(BCR_T) void bcr_panel_kernel(BcrPanelArgs a) {
                 bcr_export_tile(Wprev + (NT + R) * 16 * BP, rd, Wxg + (size_t)(Rg * NT + Jp) * 256, Lxg + (size_t)(Rg * NT + Jp) * 256); }
         }
     };
-    bdouble4_t diag = {0, 0, 0, 0};
     for (int J = 0; J < NT; ++J) {
         double* Wb = Wp + (J & 1) * PR * 16 * BP; double* Lid = Li + (J & 1) * 16 * BP; double* db = dvec + (J & 1) * 32;
-        if (wave == 0) { if constexpr (FLOOR) flc = flds[16 * J + (lane & 15)];
-                         bcr_factor<FLOOR>(Dt + bcr_dtile(J, J) * BTS, J > 0, diag, Wb + J * 16 * BP, Lid, db, a.status, 16 * NT * job.i + 16 * J, lead, flc); }
+        // (every column enters from registers: column 0 from the landing's loads, the others from the look-ahead)
+        if (wave == 0) { if constexpr (FLOOR) if (J > 0) flc = flds[16 * J + (lane & 15)];
+                         bcr_factor<FLOOR>(Dt + bcr_dtile(J, J) * BTS, true, diag, Wb + J * 16 * BP, Lid, db, a.status, 16 * NT * job.i + 16 * J, lead, flc); }
         else if (helper) { if (J > 0) { BCR_STAMP(); updates(J - 1, hw, 6); BCR_STAMP(); exports(J - 1, hw, 6); } else land_rest(); }
         BCR_STAMP();
 #ifdef BCR_STAMPS

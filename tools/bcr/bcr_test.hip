@@ -1,6 +1,6 @@
 // Stand-alone check + timing of the block cyclic reduction solver (nlls_bcr.hip) against a CPU bordered-band LDL'.
 // build: hipcc -O3 -std=c++20 --offload-arch=gfx950 -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form -o tools/bcr/bcr_test tools/bcr/bcr_test.hip (__graft_entry__.build() does); run on the GPU box.
-// bcr_test: the case list below; bcr_test n bw nbd [reps [level]]: that case alone (level: per-level backward launches); bcr_test list ...: several.  Every case: x against the CPU, and x of the
+// bcr_test: the case list below; bcr_test n bw nbd [reps [level]]: that case alone (level: per-level backward launches); bcr_test list ...: several; bcr_test floor: the pivot floor on two singular unknowns.  Every case: x against the CPU, and x of the
 // last of its repeated solves against x of the first, bit for bit.
 #include <cmath>
 #include <cstdio>
@@ -46,7 +46,13 @@ static double cpu_solve(int n, int bw, int nbd, int H, const std::vector<double>
     return 0;
 }
 
-static int run_case(int n, int bw, int nbd, int reps, unsigned seed, bool level_backward = false) {
+// sing (nsing of them): unknowns made singular and solved with the pivot floor on (relfloor > 0: the panel's FLOOR instantiation, the guarded re-factorisation of the tile that
+// meets one).  An EXACTLY zero row, column and diagonal does not get there: a zero pivot makes the unguarded chain's tile NaN, NaN is above no floor, and the solve reports
+// it (bcr_factor: "a NaN pivot is left alone").  So unknown u = sing[q] is singular the way a gauge direction is, by cancellation: u and u - 1 are cut off from everything
+// else and form the block [1 1; 1 1 + 2^-40] with the consistent right-hand side (0.5, 0.5) -- the pivot of u is 2^-40 exactly, not zero, and below 1e-11 of its diagonal
+// entry.  Expected: x_u = 0 exactly (dropped), x_{u-1} = 0.5 and every other unknown as the CPU's LDL' of the system without the unknowns u, every dropped pivot counted
+// once per solve (status[4]), and the last solve bit for bit the first.
+static int run_case(int n, int bw, int nbd, int reps, unsigned seed, bool level_backward = false, const int* sing = nullptr, int nsing = 0, double relfloor = 0.0) {
     const int H = bw + 1 + nbd + 1, nbr = nbd + 1;
     std::mt19937_64 rng(seed); std::uniform_real_distribution<double> U(-1.0, 1.0);
     std::vector<double> Sb((size_t)n * H + (size_t)nbr * nbr, 0.0);
@@ -58,7 +64,15 @@ static int run_case(int n, int bw, int nbd, int reps, unsigned seed, bool level_
     for (int j = 0; j < nbd; ++j) { Sb[(size_t)n * H + j + nbr * j] = rowsum[n + j] + 1.0; Sb[(size_t)n * H + nbd + nbr * j] = U(rng); }
     // make it safely positive definite: add a multiple of the identity found from Gershgorin
     for (int j = 0; j < n; ++j) Sb[(size_t)j * H] += 0.45 * rowsum[j];
-    std::vector<double> xc; cpu_solve(n, bw, nbd, H, Sb, xc);
+    for (int q = 0; q < nsing; ++q) for (int u = sing[q] - 1; u <= sing[q]; ++u) {
+        for (int c = 0; c < H; ++c) Sb[(size_t)u * H + c] = 0.0;                                              // column u below the diagonal, its border entries, its rhs
+        for (int e = 1; e <= bw && u - e >= 0; ++e) Sb[(size_t)(u - e) * H + e] = 0.0; }                     // row u left of the diagonal
+    for (int q = 0; q < nsing; ++q) { double* c0 = &Sb[(size_t)(sing[q] - 1) * H]; double* c1 = c0 + H;
+        c0[0] = 1.0; c0[1] = 1.0; c1[0] = 1.0 + std::ldexp(1.0, -40); c0[bw + 1 + nbd] = 0.5; c1[bw + 1 + nbd] = 0.5; }
+    std::vector<double> xc;
+    {   std::vector<double> Sc = Sb;                                                                          // the system without them: x = 0 there, nothing else moves
+        for (int q = 0; q < nsing; ++q) { double* c0 = &Sc[(size_t)(sing[q] - 1) * H]; double* c1 = c0 + H; c0[1] = 0.0; c1[0] = 1.0; c1[bw + 1 + nbd] = 0.0; }
+        cpu_solve(n, bw, nbd, H, Sc, xc); }
     if (!BcrSolver::supports(n, bw, nbd)) { printf("case n=%d bw=%d nbd=%d: unsupported\n", n, bw, nbd); return 0; }
     BcrSolver S; std::string err;
     Switches sw{}; sw.bcr_level_backward = level_backward;       // (one backward launch per level instead of the fused one: NLLS_BCR_LEVEL_BACKWARD=1 of the library)
@@ -68,7 +82,7 @@ static int run_case(int n, int bw, int nbd, int reps, unsigned seed, bool level_
     CHK(hipMalloc(&dS, Sb.size() * 8)); CHK(hipMalloc(&dx, (n + nbd + 16) * 8)); CHK(hipMalloc(&dst, 512));
     CHK(hipMemcpy(dS, Sb.data(), Sb.size() * 8, hipMemcpyHostToDevice)); CHK(hipMemset(dst, 0, 512)); CHK(hipMemset(dx, 0, (n + nbd + 16) * 8));
     hipStream_t st; CHK(hipStreamCreate(&st));
-    if (S.enqueue(st, dS, dx, dst) != 0) { printf("enqueue failed\n"); return 1; }
+    if (S.enqueue(st, dS, dx, dst, relfloor) != 0) { printf("enqueue failed\n"); return 1; }
     CHK(hipStreamSynchronize(st));
     std::vector<double> xg(n + nbd); int status[80];
     CHK(hipMemcpy(xg.data(), dx, (n + nbd) * 8, hipMemcpyDeviceToHost)); CHK(hipMemcpy(status, dst, 320, hipMemcpyDeviceToHost));
@@ -81,16 +95,26 @@ static int run_case(int n, int bw, int nbd, int reps, unsigned seed, bool level_
     for (int i = 0; i < n + nbd; ++i) { const double d = std::fabs(xg[i] - xc[i]); if (d > num || d != d) { num = d; worst = i; } den = std::max(den, std::fabs(xc[i])); }
     hipEvent_t e0, e1; CHK(hipEventCreate(&e0)); CHK(hipEventCreate(&e1));
     int rc = 0;
-    for (int i = 0; i < 3; ++i) rc |= S.enqueue(st, dS, dx, dst);
+    for (int i = 0; i < 3; ++i) rc |= S.enqueue(st, dS, dx, dst, relfloor);
     CHK(hipEventRecord(e0, st));
-    for (int i = 0; i < reps; ++i) rc |= S.enqueue(st, dS, dx, dst);
+    for (int i = 0; i < reps - 1; ++i) rc |= S.enqueue(st, dS, dx, dst, relfloor);
+    int dropped_before = 0;                                       // (status[4] adds up over the solves: the last solve's own count is the difference)
+    if (nsing) { CHK(hipStreamSynchronize(st)); CHK(hipMemcpy(&dropped_before, dst + 4, 4, hipMemcpyDeviceToHost)); }
+    rc |= S.enqueue(st, dS, dx, dst, relfloor);
     CHK(hipEventRecord(e1, st)); CHK(hipEventSynchronize(e1));
     float ms = 0; CHK(hipEventElapsedTime(&ms, e0, e1));
     // the same system solved again (3 + reps times): no atomics anywhere in the cyclic reduction, so x of the last solve must be x of the first, bit for bit, and the status still 0
     std::vector<double> xl(n + nbd); int status2[4];
     CHK(hipMemcpy(xl.data(), dx, (n + nbd) * 8, hipMemcpyDeviceToHost)); CHK(hipMemcpy(status2, dst, 16, hipMemcpyDeviceToHost));
     const bool same = memcmp(xl.data(), xg.data(), (size_t)(n + nbd) * 8) == 0;
-    const bool ok = num <= 1e-9 * den && status[0] == 0 && status2[0] == 0 && rc == 0 && same;
+    bool ok = num <= 1e-9 * den && status[0] == 0 && status2[0] == 0 && rc == 0 && same;
+    if (nsing) {
+        int dropped_all = 0; CHK(hipMemcpy(&dropped_all, dst + 4, 4, hipMemcpyDeviceToHost));
+        bool zero = true; for (int q = 0; q < nsing; ++q) zero = zero && xg[sing[q]] == 0.0;
+        const int d1 = status[4], dl = dropped_all - dropped_before;
+        printf("   floor %.1e: dropped first=%d last=%d  x at the singular unknowns %s\n", relfloor, d1, dl, zero ? "zero" : "NOT ZERO");
+        ok = ok && zero && d1 >= 1 && d1 == dl;
+    }
     printf("case n=%5d bw=%3d nbd=%2d  N=%4d NT=%d levels=%2zu launches=%2d %s  err=%.3e (|x|=%.3e, worst %d) status=%d  repeat=%s  %.1f us/solve  %s\n",
            n, bw, nbd, S.N, S.NT, S.levels.size(), S.launches, S.fused_backward ? "fused" : "per-level", num, den, worst, status[0] | status2[0], same ? "identical" : "DIFFERS", 1e3 * ms / reps, ok ? "OK" : "FAIL");
     hipFree(dS); hipFree(dx); hipFree(dst); hipStreamDestroy(st);
@@ -104,6 +128,12 @@ int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "list")) {
         if ((argc - 2) % 4 != 0 || argc < 6) { printf("usage: bcr_test list n bw nbd fused|level ...\n"); return 2; }
         for (int a = 2; a < argc; a += 4) fails += run_case(atoi(argv[a]), atoi(argv[a + 1]), atoi(argv[a + 2]), 2, 11 + a, !strcmp(argv[a + 3], "level"));
+        printf(fails ? "FAILED %d\n" : "all ok\n", fails); return fails ? 1 : 0;
+    }
+    // bcr_test floor: NT = 4, N = 4, pivot floor 1e-11 (the library's), one dropped unknown in tile column 0 of an eliminated block (block 1) and one in its last tile column, both backward forms
+    if (argc >= 2 && !strcmp(argv[1], "floor")) {
+        const int sing[2] = {64 + 5, 64 + 48 + 9};
+        for (int lvl = 0; lvl < 2; ++lvl) fails += run_case(256, 64, 0, 2, 11, lvl != 0, sing, 2, 1e-11);
         printf(fails ? "FAILED %d\n" : "all ok\n", fails); return fails ? 1 : 0;
     }
     if (argc >= 4) { const int rc = run_case(atoi(argv[1]), atoi(argv[2]), atoi(argv[3]), argc >= 5 ? atoi(argv[4]) : 200, 11, argc >= 6 && !strcmp(argv[5], "level")); printf(rc ? "FAILED\n" : "all ok\n"); return rc; }
