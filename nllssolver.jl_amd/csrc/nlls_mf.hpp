@@ -19,6 +19,13 @@ template <int KIND, int PS> constexpr bool mf_kind_ok = Res<KIND>::NDEPS == 2 &&
 // a wavefront's own LDS traffic: writes of some lanes, then reads by others.  The LDS pipe serves one wavefront's instructions in order; the compiler must not
 // move them across this point, and the counter wait covers the returned data
 NLLS_DEV void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+// slot S of a block's variables, loaded once in front of a loop over batches, made a NEW value to the compiler in every batch: the block's arithmetic is then compiled as if
+// the slot had just been loaded per batch -- the same contractions, hence the same bits, as with a reload in every batch (notes/r16.md)
+template <int KIND, int S>
+NLLS_DEV void mf_pin_slot(double (*st)[MAXST]) {
+#pragma unroll
+    for (int q = 0; q < var_storage(Res<KIND>::SK[S], Res<KIND>::SD[S]); ++q) { double v = st[S][q]; asm volatile("" : "+v"(v)); st[S][q] = v; }
+}
 NLLS_DEV double mf_rcp(double d) { const double r = __builtin_amdgcn_rcp(d); const double e = fma(-d, r, 1.0); return fma(r, fma(e, e, e), r); }   // v_rcp_f64 (2^-24) + one cubic step: 1.1e-16
 
 

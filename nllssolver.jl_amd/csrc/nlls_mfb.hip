@@ -26,7 +26,8 @@ namespace nlls {
 struct MfBackArgs {
     const double* vars; const double* odata; const uint32_t* ovoff; RobustSpec rk;
     const MfDesc* desc; const uint32_t* rcflat; const double* Cinv; const double* b; const double* xr; double* x; double* part;
-    uint32_t ngroups; const uint32_t* red_boff; int nred, write_red; double* Szero; int64_t nzero; uint32_t nextra, nrest_wg; BsfRetract rt;
+    uint32_t ngroups, nbig;                                                      // supernodes; of them, those of several batches (one workgroup each) come first, then those of ONE batch (one wavefront each)
+    const uint32_t* red_boff; int nred, write_red; double* Szero; int64_t nzero; uint32_t nextra, nrest_wg; BsfRetract rt;
     double* stamps;
     const double* A; const SchurCopy* copies; int64_t ncopy; int npq, nps;      // the reduced blocks' share of the statistics: npq workgroups for x_R' B x_R, nps for max / |x|^2 / g'x over the reduced unknowns
 };
@@ -48,6 +49,22 @@ NLLS_DEV void mfb_row(double* __restrict__ row, double q, double cost, double mx
         for (int k = 0; k < 6; ++k) row[k] = t[k];
     }
 }
+// the same row from ONE wavefront that had its supernode to itself (a packed workgroup: no workgroup barrier anywhere): the wavefront's sums, then the combination with the
+// MF_NW - 1 zero partials the empty wavefronts of a workgroup of its own would have left -- written out: -0.0 + 0.0 is +0.0, the row must hold the bits that workgroup wrote.
+// The zero is opaque: this file's flags would fold a literal away.
+NLLS_DEV void mfb_row_wave(double* __restrict__ row, double q, double cost, double mx, double nan, double ss, double bx) {
+    q = wave_sum_dpp63(q); cost = wave_sum_dpp63(cost); ss = wave_sum_dpp63(ss); bx = wave_sum_dpp63(bx); mx = mfb_wave_max(mx); nan = mfb_wave_max(nan);
+    if ((threadIdx.x & 63) == 63) {
+        double z = 0.0; asm volatile("" : "+v"(z));
+        double t[6] = {q, cost, mx, nan, ss, bx};
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+#pragma unroll
+            for (int u = 1; u < MF_NW; ++u) t[k] = (k == 2 || k == 3) ? fmax(t[k], z) : t[k] + z; }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) row[k] = t[k];
+    }
+}
 
 // does the back-substitution take the trial point's cost along?  Only where the reduced variable's retraction is the plain sum it can repeat bit for bit (Euclidean: src/variable.jl:5);
 // other kinds (an SO(3) pose) get mf_cost_kernel behind it -- the SAME lanes, batches and sums, so that every cost the matrix-free path reports is one fixed sum of the same per-block values
@@ -59,10 +76,14 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
     constexpr int CS = 1 - PS, DP = I::dof(PS), DC = I::dof(CS);
     __shared__ double red[MF_NW][64 * DP], xpw[MF_NW][MF_BMAX * DP], stage[MF_NW][MF_SLOTS][2 * DP]; __shared__ uint32_t stpv[MF_NW][MF_SLOTS]; __shared__ double rowred[6][MF_NW];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    double* const row = a.part + (size_t)blockIdx.x * MF_PW;
+    // the grid: nbig workgroups of one supernode each, then the supernodes of ONE batch MF_NW to a workgroup (one wavefront each: in a workgroup of its own three wavefronts
+    // fell through the batch loop and sat in the row's barriers, holding a quarter of a SIMD's registers each), then the role workgroups.  Rows of `part` are indexed by
+    // SUPERNODE, the role workgroups' rows follow them: what mf_finish_body sums does not know how the supernodes were packed.
+    const uint32_t nsg = a.nbig + (a.ngroups - a.nbig + MF_NW - 1) / MF_NW;
     if (blockIdx.x == 0 && tid == 0) time_stamp(a.stamps, 1);
-    if (blockIdx.x >= a.ngroups) {
-        const uint32_t w = blockIdx.x - a.ngroups;
+    if (blockIdx.x >= nsg) {
+        const uint32_t w = blockIdx.x - nsg;
+        double* const row = a.part + (size_t)(a.ngroups + w) * MF_PW;
         if (w < a.nrest_wg) {                                  // x_R = -s scattered, S / the tiles zero-filled for the next solve, the other variables retracted (64-thread roles)
             backsub_rest_roles(w * MF_NW + wave, a.nextra, lane, a.xr, a.x, a.red_boff, a.nred, a.write_red, a.Szero, a.nzero, a.rt);
             if (tid < 6) row[tid] = 0.0;
@@ -80,7 +101,14 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
         mfb_row(row, 0.0, 0.0, mx, nan, ss, bx, rowred);
         return;
     }
-    const MfDesc d = a.desc[blockIdx.x];
+    // a packed workgroup: wavefront w has supernode nbig + MF_NW (blockIdx.x - nbig) + w to itself, if there is one -- its one batch, its stores, its row; no path below reaches a
+    // workgroup barrier with it (the LDS scratch is per wavefront).  first / stride: the batches this wavefront takes
+    const bool packed = blockIdx.x >= a.nbig;
+    const uint32_t sn = packed ? a.nbig + (blockIdx.x - a.nbig) * MF_NW + (uint32_t)wave : blockIdx.x;
+    if (sn >= a.ngroups) return;
+    const int first = packed ? 0 : wave, stride = packed ? 1 : MF_NW;
+    double* const row = a.part + (size_t)sn * MF_PW;
+    const MfDesc d = a.desc[sn];
     const int nd = (int)d.nd, nmem = (int)d.nmem, ncb = nd / DC;
     const int B = (int)d.B;
     const int ml = lane / ncb, j = lane - ml * ncb; const bool lane_in = ml < B;
@@ -101,14 +129,19 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
         r.vo[0] = ovoff[e * 2]; r.vo[1] = ovoff[e * 2 + 1];
     };
     Rec r0, r1; St s0, s1;
-    load_rec(wave * B, r0);
+    load_rec(first * B, r0);
     BlockGH<KIND>::load(vars, r0.vo, s0);
+    // The lane's reduced variable is the same in every batch (camera j of the supernode), like sc[]: where it is Euclidean it is loaded with the first batch's records only, and
+    // each batch loads the eliminated slot alone; mf_pin_slot keeps the bits of a reload per batch (nlls_mf.hpp).  A pose (twelve doubles: they do not fit the 168 registers
+    // across the loop) is reloaded per batch.
+    constexpr bool HOIST = Res<KIND>::SK[CS] == NLLS_VAR_EUCLIDEAN;
     double qacc = 0.0, cacc = 0.0, macc = 0.0, nacc = 0.0, sacc = 0.0, bacc = 0.0; int slot0 = 0;
 #pragma unroll 1
-    for (int mb = wave * B; mb < nmem; mb += MF_NW * B, slot0 += B) {
+    for (int mb = first * B; mb < nmem; mb += stride * B, slot0 += B) {
         const int nlive = min(B, nmem - mb);
         const bool active = lane_in && ml < nlive, head = active && j == 0;
-        load_rec(mb + MF_NW * B, r1);
+        if constexpr (HOIST) mf_pin_slot<KIND, CS>(s0);
+        load_rec(mb + stride * B, r1);
         // the member's right-hand side and inverse block, by its first lane: requested now, used behind the sum
         double bv[DP], ci[DP * DP];
         { const size_t m = (size_t)(mb + (head ? ml : 0));
@@ -132,7 +165,7 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
         if (active) {
 #pragma unroll
             for (int k = 0; k < DP; ++k) red[wave][lane * DP + k] = ts[k]; }
-        BlockGH<KIND>::load(vars, r1.vo, s1);
+        if constexpr (HOIST) BlockGH<KIND>::template load_only<PS>(vars, r1.vo, s1); else BlockGH<KIND>::load(vars, r1.vo, s1);
         wave_lds_sync();
         if (head) {
             double accv[DP];
@@ -147,6 +180,9 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
 #pragma unroll
                 for (int k = 0; k < DP; ++k) t = fma(ci[i + DP * k], bv[k] - accv[k], t);
                 xp[i] = -t; }
+            // The retraction below adds the step AS STORED.  At DP = 1 the step is one product, and the compiler contracted it into the sum (one rounding): the stored variable was
+            // then not old + x, and not the point whose cost the lanes take below (they add the rounded x from LDS) -- nlls_sweep_cost of the trial point missed the trial's cost by an ulp.
+            if constexpr (DP == 1) asm volatile("" : "+v"(xp[0]));
 #pragma unroll
             for (int k = 0; k < DP; ++k) { xpw[wave][ml * DP + k] = xp[k]; stage[wave][slot0 + ml][k] = xp[k]; stage[wave][slot0 + ml][DP + k] = s0[PS][k] + xp[k];   // the retraction of a Euclidean block (src/variable.jl:5)
                 if (is_nan_bits(xp[k])) nacc = 1.0; macc = fmax(macc, fabs(xp[k])); sacc = fma(xp[k], xp[k], sacc); bacc = fma(bv[k], xp[k], bacc); }
@@ -180,14 +216,16 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
         }
         wave_lds_sync();
         r0 = r1;
+        if constexpr (HOIST) BlockGH<KIND>::template copy_only<PS>(s1, s0);
+        else {
 #pragma unroll
-        for (int q = 0; q < MAXST; ++q) { s0[0][q] = s1[0][q]; s0[1][q] = s1[1][q]; }
+            for (int q = 0; q < MAXST; ++q) { s0[0][q] = s1[0][q]; s0[1][q] = s1[1][q]; } }
     }
     // results leave behind the loop: a store between the loads would make every wait a full vmcnt(0) (finding 3)
     {
-        const int nb_all = (nmem + B - 1) / B;                        // batches of the supernode; this wavefront took wave, wave + 4, ...
+        const int nb_all = (nmem + B - 1) / B;                        // batches of the supernode; this wavefront took first, first + stride, ...
         for (int sl = lane; sl < MF_SLOTS; sl += 64) {
-            const int bi = sl / B, mi = sl - bi * B; const int batch = wave + MF_NW * bi; const int m = batch * B + mi;
+            const int bi = sl / B, mi = sl - bi * B; const int batch = first + stride * bi; const int m = batch * B + mi;
             if (batch >= nb_all || m >= nmem) continue;
 #pragma unroll
             for (int k = 0; k < DP; ++k) a.x[eb0 + (size_t)m * DP + k] = stage[wave][sl][k];
@@ -196,7 +234,8 @@ __global__ __launch_bounds__(64 * MF_NW) __attribute__((amdgpu_waves_per_eu(3, 3
                 for (int k = 0; k < DP; ++k) a.rt.vto[pv + k] = stage[wave][sl][DP + k]; }
         }
     }
-    mfb_row(row, qacc, cacc, macc, nacc, sacc, bacc, rowred);
+    if (packed) mfb_row_wave(row, qacc, cacc, macc, nacc, sacc, bacc);
+    else mfb_row(row, qacc, cacc, macc, nacc, sacc, bacc, rowred);
 }
 
 // cost(vars, costs) (src/cost.jl:10-13) in the lanes, batches and sums of the back-substitution: row bid of `part` gets the supernode's cost in column 1 (only == 0: the other
@@ -271,9 +310,12 @@ static int launch_mf_backsub(nlls_ctx* c, const Group& G, const BsfRetract& rt, 
         a.nrest_wg = (nextra + nrestwg + MF_NW - 1) / MF_NW;
         a.A = c->A.p; a.copies = c->d_copy.p; a.ncopy = c->ncopy;
         a.npq = (int)std::max<int64_t>(1, std::min<int64_t>((c->ncopy * QF_COLS + 255) / 256, 64)); a.nps = (int)std::max<int64_t>(1, std::min<int64_t>((c->nred + 255) / 256, 32));
-        const unsigned grid = (unsigned)c->n_fast_groups + a.nrest_wg + (unsigned)a.npq + (unsigned)a.nps;
-        if ((size_t)grid * MF_PW > c->mf_q.n) { c->err = "matrix-free trial: partials buffer too small"; return NLLS_ERR_HIP; }
-        c->mf_rows = (int)grid;
+        // rows of partials: one per supernode + one per role workgroup; the grid packs the supernodes of one batch MF_NW to a workgroup (mf_backsub_kernel)
+        a.nbig = (uint32_t)c->mf_nbig;
+        const unsigned nrole = a.nrest_wg + (unsigned)a.npq + (unsigned)a.nps, rows = (unsigned)c->n_fast_groups + nrole;
+        const unsigned grid = a.nbig + (unsigned)((c->n_fast_groups - c->mf_nbig + MF_NW - 1) / MF_NW) + nrole;
+        if ((size_t)rows * MF_PW > c->mf_q.n) { c->err = "matrix-free trial: partials buffer too small"; return NLLS_ERR_HIP; }
+        c->mf_rows = (int)rows;
         hipLaunchKernelGGL((mf_backsub_kernel<KIND, PS>), dim3(grid), dim3(64 * MF_NW), 0, c->stream, a);
         HIPCHK(hipGetLastError());
         if constexpr (!mf_fuses_cost<KIND, PS>) {      // (the trial point is in memory now: its cost by the same lanes and sums, into column 1 of the supernodes' rows)
