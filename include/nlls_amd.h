@@ -346,6 +346,41 @@ int  nlls_eval_gradhess(nlls_ctx* ctx, int32_t which, int32_t group, int64_t n, 
 int  nlls_res_jac_cols(int32_t res_kind);
 int  nlls_res_gh_dim(int32_t res_kind);
 
+/* ---- matrix-free products with the linearisation ---------------------------------------------------------------------------
+ * The linearisation applied to vectors, without A.data: a residual ||(H + lambda I) x + g|| of any solve, Krylov methods of the caller's own (CG, LSQR, Lanczos,
+ * Hutchinson probes), the model decrease of a step the caller formed.  No full accumulate sweep on a context that runs the matrix-free trial, no copy of A.data, no
+ * matrix rebuilt from the BlockSparseMatrix index.
+ * H = sum over cost blocks of P' H_blk P, H_blk exactly what nlls_eval_gradhess returns for the block (robustified, second-order term included; adaptive kinds: with
+ * the kernel's three rows and columns; NLLS_COST_LINEAR3: the cost's own Hessian); P keeps the unknowns of the block's free slots and drops the fixed ones, a block
+ * without a free slot contributes nothing.  lambda * v is added on every unknown (uniformscaling!, src/BlockSparseMatrix.jl:83-99).  J is that of
+ * nlls_eval_jacobians: unrobustified, non-kernel slots only; fixed slots contribute 0 to J v and have no row in J' u, the kernel variable's rows of J' u are 0.
+ * EVALUATED at variable set `which` at the time of the call, not read from a stored A.data: the products equal those with the sweep's A only while `which` still
+ * holds what the sweep saw.  lambda is the argument, not the damping nlls_damp has accumulated.
+ * Layouts: vectors over the unknowns have length ndof, in the order of b and x; vector k starts at v + k * ndof.  A group's u holds ncost * M doubles per vector
+ * (M = nlls_res_nres): block i of the caller's upload order at u + k * ncost * M + i * M.  d_out holds the unfixed blocks in block order, block b at offset
+ * sum_{c<b} dof_c^2, column-major dof_b x dof_b, full symmetric.  All pointers are host pointers; synchronous on return.
+ * Two launches per chunk of vectors and no atomics: one lane per cost block leaves a record per block and vector, then every unknown's records are summed in
+ * ascending (group, block, slot) order -- rows of fewer than NLLS_OPT_APPLY_WAVE_MIN incidences one lane per unknown, longer rows a wavefront each with a fixed
+ * tree over its lanes (a row of more than 4096 incidences: a wavefront per segment of 4096, the segments added in order).  Two calls return identical bytes; vector k of a call of nvec equals the call on v_k alone, byte for byte; so does a call whose vectors were
+ * cut into chunks because their records exceed NLLS_OPT_APPLY_SCRATCH bytes.
+ * NLLS_ERR_INVALID_ARG -- nothing enqueued, no output byte written -- for a null context or pointer, `which` outside 0 .. 2, a bad group, nvec < 1 or
+ * nvec > NLLS_APPLY_MAX_VEC, a non-finite lambda.  NLLS_ERR_NOT_READY before an upload.  NLLS_ERR_UNSUPPORTED: nlls_jac_apply / nlls_jact_apply on a non-squared cost
+ * kind or a dynamic-size kind; nlls_hess_apply / nlls_hess_block_diag when any group is of a dynamic-size kind (no per-block Hessian: nlls_eval_gradhess refuses
+ * them too); all four under nlls_set_shard with nranks > 1.  ndof == 0: NLLS_OK, nothing written.  Need an upload, no sweep; read only, like the nlls_eval_* calls:
+ * no validity state of the context changes, scratch and an index of their own (built at the first call after an upload), a call between a sweep and a trial
+ * leaves the trial as it was. */
+#define NLLS_APPLY_MAX_VEC 8
+/* replaces: hessian * x of the iterators (gethessgrad, src/linearsystem.jl:180-190, src/iterators.jl:47-115) and, as v . y, fast_bAb (src/utils.jl:71-106)
+ *   y_k = (H + lambda I) v_k, k < nvec */
+int  nlls_hess_apply(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* v, double* y_out);
+/* replaces: the Jacobian-vector product behind the iterators' predicted residual (src/iterators.jl:47-115): u_k = J v_k, per block of one group */
+int  nlls_jac_apply(nlls_ctx* ctx, int32_t which, int32_t group, int32_t nvec, const double* v, double* u_out);
+/* replaces: the gradient J' r of gethessgrad (src/linearsystem.jl:180-190) for any u: y_k = J' u_k, this group's blocks alone */
+int  nlls_jact_apply(nlls_ctx* ctx, int32_t which, int32_t group, int32_t nvec, const double* u, double* y_out);
+/* replaces: the diagonal blocks of gethessgrad's hessian (block(A, i, i), src/BlockSparseMatrix.jl; src/linearsystem.jl:180-190) under uniformscaling!:
+ *   the diagonal blocks of H + lambda I, a block-Jacobi preconditioner */
+int  nlls_hess_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d_out);
+
 /* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
  * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
  *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.
@@ -409,22 +444,29 @@ int  nlls_solve(nlls_ctx* ctx, double* x_out);
  * heavy) whose rows are shared or split and flushed with atomics, [41] cost groups swept folded, [42] cost groups the last full accumulate sweep ran as one fused
  * launch (0 before the first sweep).  nlls_eval_jacobians / nlls_eval_gradhess: [43] doubles of LDS in which a wavefront stages its lanes' records before it
  * writes them out contiguously, [44], [45], [46] lanes of a wavefront staged at a time for the J / g / H of the last call that asked for them (64: all at once;
- * 0: stored directly, or not asked for yet). */
+ * 0: stored directly, or not asked for yet).  The last matrix-free product (nlls_hess_apply, ...): [47] rows its gather summed one lane per unknown, [48] rows that
+ * took a wavefront each, [49] chunks its vectors were cut into, [50] doubles of record scratch it used (nlls_jac_apply gathers nothing: 0, 0, 1, 0). */
 int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
 /* Run-time switches of a context (A/B measurements, parity tests through both paths on ONE upload):
  *   NLLS_OPT_MATERIALIZE  value != 0: nlls_lm_trial eliminates from the materialised A.data (the round-5 path) although the structure qualifies for the
  *                         matrix-free trial; 0 (default): matrix-free where nlls_upload_structure found it applicable (NLLS_FLAG_MATERIALIZE: never).
  *   NLLS_OPT_LOOKAHEAD    value == 0: no look-ahead sweep behind an LM trial (the environment's NLLS_NO_LOOKAHEAD_SWEEP=1).
- *   NLLS_OPT_PHASE_EVENTS see below. */
+ *   NLLS_OPT_PHASE_EVENTS see below.
+ *   NLLS_OPT_APPLY_SCRATCH  bytes of record scratch the matrix-free products may hold (default 256 MiB): a call whose vectors need more is cut into chunks of
+ *                         vectors (one vector's records are always held).  NLLS_OPT_APPLY_WAVE_MIN  incidences from which an unknown's row is summed by a
+ *                         wavefront of its own (default 64; values below 1 count as 1).  Both outlive an upload. */
 /* Device-timed NLLSResult buckets since the upload, nanoseconds: out[0] gradient, [1] cost, [2] solver, [3] trials counted (single-GPU sparse trials; others leave them untouched). */
 int  nlls_get_time_buckets(nlls_ctx* ctx, int64_t* out, int32_t n);
 #define NLLS_OPT_MATERIALIZE 1
 #define NLLS_OPT_LOOKAHEAD   2
+#define NLLS_OPT_APPLY_SCRATCH  4
+#define NLLS_OPT_APPLY_WAVE_MIN 5
 #define NLLS_OPT_PHASE_EVENTS 3   /* value != 0: the COLLECTIVE nlls_lm_trial records stream events at its phase boundaries (resets the sums); nlls_get_phase_times reads them */
 /* out[0..4]: milliseconds summed over the trials since NLLS_OPT_PHASE_EVENTS was set -- [0] this rank's assembly of [S | s] (elimination), [1] the all-reduce of [S | s] (wait included),
  * [2] the reduced solve (every rank), [3] back-substitution + retraction, [4] trial tail (statistics, cost sweep, the scalars' gather); [5] gradient sweeps (ms summed), [6] trials, [7] sweeps counted.
  * [8] milliseconds of the last nlls_set_cost_data's scatter launch alone (an event pair around it, while the option is set; waits for it), [9] the device copies of the payload the last such launch wrote.
- * [10] milliseconds of the last nlls_eval_jacobians / nlls_eval_gradhess launch alone (the same: an event pair, while the option is set), [11] the bytes of records that call's launch wrote. */
+ * [10] milliseconds of the last nlls_eval_jacobians / nlls_eval_gradhess launch alone (the same: an event pair, while the option is set), [11] the bytes of records that call's launch wrote.
+ * [12] milliseconds of the last matrix-free product's launches (nlls_hess_apply, nlls_jac_apply, nlls_jact_apply, nlls_hess_block_diag: one event pair around all of them), [13] the bytes of records and output they wrote. */
 int  nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n);
 int  nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value);
 int  nlls_set_step(nlls_ctx* ctx, const double* x);               /* host-formed steps (dogleg, GD) */

@@ -21,6 +21,8 @@ FLAG_NO_TILE_SPARSE = 512
 FLAG_NO_PIVOT_FLOOR = 1024
 FLAG_MATERIALIZE = 2048
 OPT_MATERIALIZE, OPT_LOOKAHEAD, OPT_PHASE_EVENTS = 1, 2, 3
+OPT_APPLY_SCRATCH, OPT_APPLY_WAVE_MIN = 4, 5
+APPLY_MAX_VEC = 8
 VARS_CURRENT, VARS_NEXT, VARS_BEST = 0, 1, 2
 
 # every symbol include/nlls_amd.h declares (checked by tests/test_capi_symbols.py)
@@ -33,7 +35,8 @@ nlls_sweep_gradhess_finish nlls_sweep_cost_local nlls_sweep_cost_finish nlls_sol
 nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_owned nlls_trial_local nlls_solve_finish_async nlls_lm_trial nlls_optimize_singles nlls_time_sweep_gradhess nlls_time_sweep_accumulate nlls_time_sweep_cost nlls_time_solve nlls_time_reduced_solve nlls_profile_sweep nlls_profile_sweep_dispatch nlls_solve_finish_replicated nlls_get_variables_owned nlls_lm_iterations
 nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
 nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
-nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim""".split()
+nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim
+nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -130,6 +133,8 @@ def lib():
         L.nlls_set_cost_data.argtypes = [vp, i32, i64, vp, vp]; L.nlls_set_robust_params.argtypes = [vp, i32, vp]
         L.nlls_eval_jacobians.argtypes = [vp, i32, i32, i64, vp, vp, vp]; L.nlls_eval_gradhess.argtypes = [vp, i32, i32, i64, vp, vp, vp, vp]
         L.nlls_res_jac_cols.argtypes = [i32]; L.nlls_res_gh_dim.argtypes = [i32]
+        L.nlls_hess_apply.argtypes = [vp, i32, dbl, i32, vp, vp]; L.nlls_jac_apply.argtypes = [vp, i32, i32, i32, vp, vp]
+        L.nlls_jact_apply.argtypes = [vp, i32, i32, i32, vp, vp]; L.nlls_hess_block_diag.argtypes = [vp, i32, dbl, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -286,6 +291,50 @@ class Context:
             out["H"] = np.ascontiguousarray(out["H"].transpose(0, 2, 1))                 # (column-major P x P per block -> H[i, row, column])
         return out
 
+    # ---- matrix-free products with the linearisation (include/nlls_amd.h) ------------------------------------
+    def _apply(self, fn, head, vin, nin, nout):
+        """vin (nin,) or (nvec, nin) -> (nout,) or (nvec, nout) through fn(ctx, *head, nvec, in, out), at most APPLY_MAX_VEC vectors per call"""
+        a = np.ascontiguousarray(vin, np.float64); one = a.ndim == 1
+        a = a.reshape(1, -1) if one else a
+        assert a.ndim == 2 and a.shape[1] == nin, f"expected vectors of length {nin}"
+        out = np.zeros((a.shape[0], nout))
+        for k0 in range(0, a.shape[0], APPLY_MAX_VEC):
+            ak = np.ascontiguousarray(a[k0:k0 + APPLY_MAX_VEC]); ok = out[k0:k0 + APPLY_MAX_VEC]
+            self._chk(fn(self.h, *head, ak.shape[0], _p(ak), _p(ok)))
+        return out[0] if one else out
+
+    def _group_rows(self, group):
+        """doubles of u per vector for cost group `group`: ncost * M (0 for a group the library will refuse)"""
+        if not 0 <= group < len(self._groups):
+            return 0
+        return self._groups[group][0] * max(self.L.nlls_res_nres(self._kinds[group]), 0)
+
+    def hess_apply(self, v, lam=0.0, which=VARS_CURRENT):
+        """nlls_hess_apply: (H + lam I) v at variable set `which`, H the sum of the blocks' nlls_eval_gradhess Hessians over the free unknowns -- evaluated, not read
+        from A.data.  v (ndof,) -> (ndof,); (nvec, ndof) -> (nvec, ndof)."""
+        n = self.info.ndof
+        return self._apply(self.L.nlls_hess_apply, (int(which), float(lam)), v, n, n)
+
+    def jac_apply(self, group, v, which=VARS_CURRENT):
+        """nlls_jac_apply: J v per block of cost group `group` (0-based): (ndof,) -> (ncost * M,), block i at [i * M, (i + 1) * M); 2-D input: one row per vector"""
+        return self._apply(self.L.nlls_jac_apply, (int(which), int(group)), v, self.info.ndof, self._group_rows(int(group)))
+
+    def jact_apply(self, group, u, which=VARS_CURRENT):
+        """nlls_jact_apply: J' u of cost group `group`'s blocks alone: (ncost * M,) -> (ndof,); 2-D input: one row per vector"""
+        return self._apply(self.L.nlls_jact_apply, (int(which), int(group)), u, self._group_rows(int(group)), self.info.ndof)
+
+    def hess_block_diag(self, lam=0.0, which=VARS_CURRENT):
+        """nlls_hess_block_diag: the diagonal blocks of H + lam I, one (dof, dof) array per unfixed block, in block order"""
+        bs = self.block_sizes(); out = np.zeros(int((bs * bs).sum()))
+        self._chk(self.L.nlls_hess_block_diag(self.h, int(which), float(lam), _p(out)))
+        off = np.concatenate(([0], np.cumsum(bs * bs)))
+        return [out[off[b]:off[b + 1]].reshape(bs[b], bs[b]).T.copy() for b in range(bs.size)]
+
+    def block_sizes(self):
+        """dof of every unfixed block, in block order (from nlls_get_bsm_index's offsets)"""
+        bo = np.asarray(self.bsm_index()[3], np.int64) - 1
+        return np.diff(np.concatenate((bo, [self.info.ndof]))).astype(np.int64)
+
     def adaptive_em(self, kernel_var=1, which=VARS_NEXT, maxiters=10):
         """nlls_adaptive_em: the ContaminatedGaussian variable `kernel_var` (1-based) of set `which` re-estimated by Expectation-Maximization on the device, written
         back into that set.  Returns (storage (1/sigma1, 1/sigma2, w), passes made)."""
@@ -411,16 +460,18 @@ class Context:
         return dict(nranks=int(out[0]), rank=int(out[1]), device=int(out[2]), transport={0: "none", 1: "rccl", 2: "caller-installed all-reduce"}[int(out[3])])
 
     def set_option(self, option, value):
-        """nlls_set_option: OPT_MATERIALIZE (1: nlls_lm_trial eliminates from the materialised A.data, 0: matrix-free where it applies), OPT_LOOKAHEAD"""
+        """nlls_set_option: OPT_MATERIALIZE (1: nlls_lm_trial eliminates from the materialised A.data, 0: matrix-free where it applies), OPT_LOOKAHEAD,
+        OPT_APPLY_SCRATCH (bytes of record scratch of the matrix-free products), OPT_APPLY_WAVE_MIN (incidences from which a row gets a wavefront)"""
         self._chk(self.L.nlls_set_option(self.h, int(option), int(value)))
 
     def phase_times(self):
         """nlls_get_phase_times: microseconds per collective trial by phase (stream events; NLLS_OPT_PHASE_EVENTS) and per gradient sweep"""
-        out = np.zeros(12); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 12)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
+        out = np.zeros(14); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 14)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
         return dict(trials=int(out[6]), sweeps=int(out[7]), elimination_us=1e3 * out[0] / nt, allreduce_S_us=1e3 * out[1] / nt, reduced_solve_us=1e3 * out[2] / nt,
                     backsub_retraction_us=1e3 * out[3] / nt, trial_tail_us=1e3 * out[4] / nt, gradient_sweep_us=1e3 * out[5] / ns,
                     update_scatter_us=1e3 * out[8], update_copies=int(out[9]),
-                    linearize_us=1e3 * out[10], linearize_bytes=int(out[11]))
+                    linearize_us=1e3 * out[10], linearize_bytes=int(out[11]),
+                    apply_us=1e3 * out[12], apply_bytes=int(out[13]))
 
     def time_buckets(self):
         """device-timed NLLSResult buckets since the upload: seconds (gradient, cost, solver) and the trials counted"""
@@ -428,7 +479,7 @@ class Context:
         return dict(timegradient=out[0] * 1e-9, timecost=out[1] * 1e-9, timesolver=out[2] * 1e-9, trials=int(out[3]))
 
     def solve_stats(self):
-        out = np.zeros(47, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 47))
+        out = np.zeros(51, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 51))
         return dict(status=int(out[0]), band_factor_cycles=int(out[1]), band_backward_cycles=int(out[2]), solve_mode=int(out[3]),
                     elim_supernodes=int(out[4]), bandwidth=int(out[5]), bcr_mfma_issued=int(out[6]), bcr_launches=int(out[7]), bcr_levels=int(out[8]),
                     band_dof=int(out[9]), dropped_pivots=int(out[10]), reduced_row_sums=int(out[11]), lazy_trials=int(out[12]),
@@ -443,7 +494,9 @@ class Context:
                     sweep_light_tiles=int(out[37]), sweep_image_tiles=int(out[38]), sweep_direct_tiles=int(out[39]), sweep_partial_tiles=int(out[40]),
                     sweep_fold_groups=int(out[41]), sweep_fused_groups=int(out[42]),
                     # eval_jacobians / eval_gradhess: doubles of LDS a wavefront stages records in, lanes staged at a time for the last J / g / H asked for (0: stored directly)
-                    linearize_slab=int(out[43]), linearize_batch_J=int(out[44]), linearize_batch_g=int(out[45]), linearize_batch_H=int(out[46]))
+                    linearize_slab=int(out[43]), linearize_batch_J=int(out[44]), linearize_batch_g=int(out[45]), linearize_batch_H=int(out[46]),
+                    # the last matrix-free product: rows gathered one lane per unknown / a wavefront each, chunks its vectors were cut into, doubles of record scratch
+                    apply_short_rows=int(out[47]), apply_wave_rows=int(out[48]), apply_chunks=int(out[49]), apply_scratch=int(out[50]))
 
     def set_step(self, x):
         x = np.ascontiguousarray(x, np.float64); assert x.size == self.info.ndof

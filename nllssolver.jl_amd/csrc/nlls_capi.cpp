@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 
 #include "nlls_internal.hpp"
 
@@ -67,6 +68,12 @@ int linearize_call(nlls_ctx* ctx, const char* name, int32_t which, int32_t group
     for (int k = 0; k < 3; ++k) if (out[k]) HIP_TRY(ctx, hipMemcpyAsync(out[k], d[k], sizeof(double) * (size_t)n * rec[k], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (`blocks` and the caller's arrays are in use until here)
     return NLLS_OK;
+}
+// staging of the matrix-free products' vectors: grown on demand, kept until the next upload (a buffer that could not be had is released, as in linearize_call)
+int apply_io(nlls_ctx* ctx, size_t need, double** out) {
+    DevBuf<double>& io = ctx->app.io;
+    if (io.n < need || !io.p) { const hipError_t e = io.alloc(need); if (e != hipSuccess) { io.release(); (void)hipGetLastError(); return hip_fail(ctx, e, "matrix-free products: staging for the vectors"); } }
+    *out = io.p; return NLLS_OK;
 }
 bool mf_trial(const nlls_ctx* ctx, int32_t from) { return ctx->mf_ok && ctx->sw.mf_on && !ctx->lin.stale_point && from == NLLS_VARS_CURRENT && ctx->nranks == 1 && !ctx->reduce_fn && ctx->info.is_sparse && !ctx->tiny_dense; }
 }  // namespace
@@ -336,6 +343,69 @@ int nlls_eval_gradhess(nlls_ctx* ctx, int32_t which, int32_t group, int64_t n, c
     NEED_READY();
     double* const out[3] = {cost_out, g_out, H_out};
     return linearize_call(ctx, "nlls_eval_gradhess", which, group, n, index, false, out);
+    NLLS_API_END(ctx)
+}
+// Matrix-free products with the linearisation (nlls_apply.hip).  These bodies validate, stage the caller's vectors in ApplyIndex::io, and synchronise; the launches are
+// enqueue_hess_apply and its siblings, on device pointers.  Read only: no event of nlls_state.hpp.
+int nlls_hess_apply(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* v, double* y_out) { NLLS_API_BEGIN
+    if (!ctx || !v || !y_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    if (!valid_set(which) || nvec < 1 || nvec > NLLS_APPLY_MAX_VEC || !std::isfinite(lambda)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_hess_apply: bad variable set, nvec or lambda");
+    TRY(apply_check(ctx, "nlls_hess_apply", -1, false));
+    const size_t nv = (size_t)nvec * (size_t)ctx->info.ndof;
+    if (nv == 0) return NLLS_OK;
+    double* io = nullptr; TRY(apply_io(ctx, 2 * nv, &io));
+    HIP_TRY(ctx, hipMemcpyAsync(io, v, sizeof(double) * nv, hipMemcpyHostToDevice, ctx->stream));
+    TRY(enqueue_hess_apply(ctx, which, lambda, nvec, io, io + nv));
+    HIP_TRY(ctx, hipMemcpyAsync(y_out, io + nv, sizeof(double) * nv, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+int nlls_jac_apply(nlls_ctx* ctx, int32_t which, int32_t group, int32_t nvec, const double* v, double* u_out) { NLLS_API_BEGIN
+    if (!ctx || !v || !u_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    if (!valid_set(which) || nvec < 1 || nvec > NLLS_APPLY_MAX_VEC || group < 0 || group >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_jac_apply: bad variable set, group or nvec");
+    TRY(apply_check(ctx, "nlls_jac_apply", group, true));
+    const Group& G = ctx->groups[(size_t)group];
+    const size_t nv = (size_t)nvec * (size_t)ctx->info.ndof, nu = (size_t)nvec * (size_t)G.ncost * (size_t)G.nres;
+    if (nv == 0 || nu == 0) return NLLS_OK;
+    double* io = nullptr; TRY(apply_io(ctx, nv + nu, &io));
+    HIP_TRY(ctx, hipMemcpyAsync(io, v, sizeof(double) * nv, hipMemcpyHostToDevice, ctx->stream));
+    TRY(enqueue_jac_apply(ctx, which, group, nvec, io, io + nv));
+    HIP_TRY(ctx, hipMemcpyAsync(u_out, io + nv, sizeof(double) * nu, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+int nlls_jact_apply(nlls_ctx* ctx, int32_t which, int32_t group, int32_t nvec, const double* u, double* y_out) { NLLS_API_BEGIN
+    if (!ctx || !u || !y_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    if (!valid_set(which) || nvec < 1 || nvec > NLLS_APPLY_MAX_VEC || group < 0 || group >= (int32_t)ctx->groups.size()) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_jact_apply: bad variable set, group or nvec");
+    TRY(apply_check(ctx, "nlls_jact_apply", group, true));
+    const Group& G = ctx->groups[(size_t)group];
+    const size_t nv = (size_t)nvec * (size_t)ctx->info.ndof, nu = (size_t)nvec * (size_t)G.ncost * (size_t)G.nres;
+    if (nv == 0) return NLLS_OK;
+    double* io = nullptr; TRY(apply_io(ctx, nv + nu, &io));
+    if (nu) HIP_TRY(ctx, hipMemcpyAsync(io, u, sizeof(double) * nu, hipMemcpyHostToDevice, ctx->stream));
+    TRY(enqueue_jact_apply(ctx, which, group, nvec, io, io + nu));
+    HIP_TRY(ctx, hipMemcpyAsync(y_out, io + nu, sizeof(double) * nv, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
+int nlls_hess_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d_out) { NLLS_API_BEGIN
+    if (!ctx || !d_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    if (!valid_set(which) || !std::isfinite(lambda)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_hess_block_diag: bad variable set or lambda");
+    TRY(apply_check(ctx, "nlls_hess_block_diag", -1, false));
+    const size_t nd = (size_t)apply_diag_len(ctx);
+    if (nd == 0) return NLLS_OK;
+    double* io = nullptr; TRY(apply_io(ctx, nd, &io));
+    TRY(enqueue_hess_block_diag(ctx, which, lambda, io));
+    HIP_TRY(ctx, hipMemcpyAsync(d_out, io, sizeof(double) * nd, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
     NLLS_API_END(ctx)
 }
 // optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)  src/robustadaptive.jl:48-73 on the device (nlls_eval.hip): one synchronisation
@@ -682,9 +752,11 @@ int nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
         if (hipEventSynchronize(ctx->phase_ev[9]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[8], ctx->phase_ev[9]) == hipSuccess) ctx->upd_ms = ms; else (void)hipGetLastError(); }
     if (take(ctx->lin_pending) && ctx->phase_ev.size() >= 12) { float ms = 0.f; (void)hipSetDevice(ctx->device);
         if (hipEventSynchronize(ctx->phase_ev[11]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[10], ctx->phase_ev[11]) == hipSuccess) ctx->lin_ms = ms; else (void)hipGetLastError(); }
-    const double v[12] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies,
-                          ctx->lin_ms, ctx->lin_bytes};
-    for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
+    if (take(ctx->app_pending) && ctx->phase_ev.size() >= 14) { float ms = 0.f; (void)hipSetDevice(ctx->device);
+        if (hipEventSynchronize(ctx->phase_ev[13]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[12], ctx->phase_ev[13]) == hipSuccess) ctx->app_ms = ms; else (void)hipGetLastError(); }
+    const double v[14] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies,
+                          ctx->lin_ms, ctx->lin_bytes, ctx->app_ms, ctx->app_bytes};
+    for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -695,9 +767,11 @@ int nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value) { NLLS_API_BEG
     case NLLS_OPT_LOOKAHEAD:   ctx->sw.spec_on = value != 0; return NLLS_OK;
     case NLLS_OPT_PHASE_EVENTS:
         ctx->phase_on = value != 0; (void)hipSetDevice(ctx->device);
-        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(12); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
+        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(14); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
         if (ctx->phase_on) { for (double& v : ctx->phase_ms) v = 0.0; ctx->phase_trials = ctx->phase_sweeps = 0; }
         return NLLS_OK;
+    case NLLS_OPT_APPLY_SCRATCH:  if (value < 0) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_option: NLLS_OPT_APPLY_SCRATCH takes bytes"); ctx->app_scratch_cap = value; return NLLS_OK;
+    case NLLS_OPT_APPLY_WAVE_MIN: ctx->app_wave_min = std::max<int64_t>(value, 1); return NLLS_OK;      // (the rows are classed again by the next product)
     }
     return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_option: unknown option");
     NLLS_API_END(ctx)
@@ -707,7 +781,7 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
     int32_t status[16] = {0};
     HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t vals[47] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
+    const int64_t vals[51] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
@@ -723,8 +797,10 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
                               // folded groups, groups whose last full sweep was one fused launch
                               ctx->n_tiles_light, ctx->n_tiles_image, ctx->n_tiles_direct, ctx->n_tiles_partial, ctx->n_fold_groups, ctx->sweep_fused_groups,
                               // [43..46] nlls_eval_jacobians / nlls_eval_gradhess: doubles of LDS a wavefront stages records in; lanes per staged sub-batch of the last call's J / g / H (0: stored directly)
-                              lin_wave_slab(), ctx->lin_batch[0], ctx->lin_batch[1], ctx->lin_batch[2]};
-    for (int i = 0; i < n && i < 47; ++i) out[i] = vals[i];
+                              lin_wave_slab(), ctx->lin_batch[0], ctx->lin_batch[1], ctx->lin_batch[2],
+                              // [47..50] the last matrix-free product (nlls_apply.hip): rows gathered one lane per unknown / a wavefront each, chunks of vectors, doubles of record scratch
+                              ctx->app_short, ctx->app_long, ctx->app_chunks, ctx->app_scratch};
+    for (int i = 0; i < n && i < 51; ++i) out[i] = vals[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

@@ -205,6 +205,29 @@ struct KnownZero { bool S = false, tiles = false, status = false, heavy_rows = f
 // Finishing work waiting for the look-ahead sweep's launch to carry it: the small dense system's finishing reduction `dense`, a matrix-free trial's finishing workgroup.
 struct Deferred { DenseFin dense{}; bool dense_pending = false, mf_pending = false; };
 
+// ---- matrix-free products with the linearisation (nlls_apply.hip): H v, J v, J' u, the diagonal blocks of H ------------------------------------------
+// The block launch leaves one record per cost block and vector (the block's product with its free slots' entries of v, or its slots' diagonal blocks of H); a gather
+// launch sums, per unfixed variable, the records of its (group, block, slot) incidences in that fixed order -- no atomics.  Built at the first call after an upload,
+// dropped by the next one; everything lies OUTSIDE the hot arena (compact_hot_set never sees it).
+constexpr uint32_t APP_SEGMENT = 4096;         // incidences a wavefront of the gather takes at most
+struct LongItem { uint32_t row, p0, p1, slot; };   // incidences [p0, p1) of block row `row`; slot: where the segment's sum goes in ApplyIndex::part (DEST_NONE: the row is whole, written directly)
+struct BigRow { uint32_t row, slot0, nslots; };    // a row cut into nslots segments, their sums at slot0 ..
+struct ApplyIndex {
+    bool ready = false;
+    std::vector<DevBuf<uint32_t>> boff;        // per cost group [ncost][ndeps]: dof offset of the slot's variable in b, DEST_NONE if it is fixed (empty: a dynamic-size group)
+    DevBuf<uint32_t> rowptr;                   // [nblocks + 1] incidences of every unfixed variable: CSR, ascending (group, block, slot)
+    DevBuf<uint32_t> off_vec, off_diag;        // per incidence: where the slot's entries start in a vector's records / in the diagonal-block records
+    DevBuf<uint32_t> erow_vec, erow_diag;      // per output element (an unknown; an entry of a diagonal block): its variable's block
+    DevBuf<uint32_t> start_vec, start_diag;    // per block: its first output element
+    DevBuf<LongItem> long_items;               // the blocks with at least wave_min_built incidences: a wavefront per item
+    DevBuf<BigRow>   big_rows;                 // ... those cut into several items
+    DevBuf<double>   rec, io, part;            // record scratch; the ABI bodies' staging of the caller's vectors; the cut rows' partial sums
+    std::vector<uint32_t> h_rowptr;
+    std::vector<int64_t> gbase_vec, gbase_diag;   // per group: first double of its records
+    int64_t rec_vec = 0, rec_diag = 0, nelem_diag = 0, nlong = 0, nitems = 0, nbig = 0; int64_t wave_min_built = -1;
+    uint32_t nslots = 0; int part_w_vec = 1, part_w_diag = 1;      // segments of all cut rows; widest cut row (unknowns; entries of its diagonal block)
+};
+
 }  // namespace nlls
 
 struct nlls_ctx {
@@ -385,4 +408,10 @@ struct nlls_ctx {
     // milliseconds and bytes written of the last launch); lin_batch: lanes per staged sub-batch of the last call's J / g / H (nlls_get_solve_stats [44..46]; 0: stored directly)
     nlls::DevBuf<double> lin_out; nlls::DevBuf<int64_t> lin_index;
     bool lin_pending = false; double lin_ms = 0.0, lin_bytes = 0.0; int lin_batch[3] = {0, 0, 0};
+    // nlls_hess_apply / nlls_jac_apply / nlls_jact_apply / nlls_hess_block_diag (nlls_apply.hip).  The two options outlive an upload (nlls_set_option); the counters are
+    // those of the last call (nlls_get_solve_stats [47..50]); under NLLS_OPT_PHASE_EVENTS a call's launches sit between phase_ev[12] and [13] (nlls_get_phase_times [12], [13])
+    nlls::ApplyIndex app;
+    int64_t app_scratch_cap = (int64_t)256 << 20, app_wave_min = 64;
+    int64_t app_short = 0, app_long = 0, app_chunks = 0, app_scratch = 0;
+    bool app_pending = false; double app_ms = 0.0, app_bytes = 0.0;
 };

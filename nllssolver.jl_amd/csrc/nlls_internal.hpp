@@ -66,6 +66,14 @@ struct LinSizes { int m, nj, p; int batch_r, batch_j, batch_g, batch_h; };   // 
 bool lin_sizes(int kind, LinSizes& s);         // false: unknown or dynamic-size kind
 int lin_wave_slab();                           // doubles of LDS a wavefront stages records in
 int enqueue_linearize(nlls_ctx* c, const Group& G, int which, int64_t n, const int64_t* d_index, double* d_r, double* d_J, double* d_cost, double* d_g, double* d_H);
+// matrix-free products with the linearisation at vars[which] (nlls_apply.hip): device pointers, on c->stream, no synchronisation.  Vector k of v / y starts at k * ndof, of a
+// group's u at k * ncost * M.  The caller has checked the arguments (apply_check); nvec is cut into chunks whose records fit nlls_ctx::app_scratch_cap.
+int apply_check(nlls_ctx* c, const char* name, int group /* -1: every group */, bool need_residual);     // NLLS_OK, or the status with nlls_last_error set
+int enqueue_hess_apply(nlls_ctx* c, int which, double lambda, int nvec, const double* d_v, double* d_y);
+int enqueue_jac_apply(nlls_ctx* c, int which, int group, int nvec, const double* d_v, double* d_u);
+int enqueue_jact_apply(nlls_ctx* c, int which, int group, int nvec, const double* d_u, double* d_y);
+int enqueue_hess_block_diag(nlls_ctx* c, int which, double lambda, double* d_out);
+int64_t apply_diag_len(const nlls_ctx* c);     // doubles of nlls_hess_block_diag's output
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);

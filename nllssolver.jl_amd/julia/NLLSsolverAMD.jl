@@ -163,6 +163,19 @@ function NLLSsolver.computecostgradhess(ls::MultiVariateLSgpu, which::Integer, g
     check(ls.ctx, ccall((:nlls_eval_gradhess, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, n, index === nothing ? C_NULL : index, cost, g, H))
     return cost, g, H
 end
+# Matrix-free products with the linearisation at device variable set `which` (0 = current), evaluated block by block and never stored: what the iterators take from
+# gethessgrad as hessian * x (src/linearsystem.jl:180-190, src/iterators.jl:47-115) and fast_bAb (src/utils.jl:71-106) as dot(v, y).  v, y: ndof, or ndof x nvec with
+# nvec <= 8 (NLLS_APPLY_MAX_VEC); u of a cost group: (nres * ncost) x nvec, block i of problem.costs.data[T] at rows (i - 1) * nres + 1 : i * nres.
+apply_nvec(a::AbstractVecOrMat{Float64}) = Int32(size(a, 2))
+function hessvec!(y::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, v::AbstractVecOrMat{Float64}, λ::Real=0.0, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_hess_apply, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, λ, apply_nvec(v), v, y)); return y
+end
+function jacvec!(u::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, group::Integer, v::AbstractVecOrMat{Float64}, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_jac_apply, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, apply_nvec(v), v, u)); return u
+end
+function jactvec!(y::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, group::Integer, u::AbstractVecOrMat{Float64}, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_jact_apply, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, apply_nvec(u), u, y)); return y
+end
 # optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
 # re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
 function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)

@@ -49,6 +49,22 @@ class MultiVariateLSgpu:
         """computecostgradhess of blocks of a cost group, every variable free (index 1-based, None: all; nlls_eval_gradhess)   src/residual.jl:57-111"""
         return self.ctx.eval_gradhess(group, which, index, want)
 
+    def hess_apply(self, v, lam=0.0, which=VARS_CURRENT):
+        """(hessian + lam I) * v without A.data (nlls_hess_apply)   src/linearsystem.jl:180-190, src/iterators.jl:47-115, src/utils.jl:71-106"""
+        return self.ctx.hess_apply(v, lam, which)
+
+    def jac_apply(self, group, v, which=VARS_CURRENT):
+        """J v per block of a cost group (nlls_jac_apply)"""
+        return self.ctx.jac_apply(group, v, which)
+
+    def jact_apply(self, group, u, which=VARS_CURRENT):
+        """J' u of a cost group's blocks (nlls_jact_apply)"""
+        return self.ctx.jact_apply(group, u, which)
+
+    def hess_block_diag(self, lam=0.0, which=VARS_CURRENT):
+        """the diagonal blocks of hessian + lam I (nlls_hess_block_diag)   src/BlockSparseMatrix.jl:83-99"""
+        return self.ctx.hess_block_diag(lam, which)
+
     def adaptive_em(self, kernel_var=1, which=VARS_NEXT, maxiters=10):
         """optimize(kernel::ContaminatedGaussian, squarederrors, maxiters)   src/robustadaptive.jl:48-73"""
         return self.ctx.adaptive_em(kernel_var, which, maxiters)

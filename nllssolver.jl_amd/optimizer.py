@@ -320,6 +320,31 @@ class Solver:
         self._start()
         return self.ls.eval_gradhess(int(group), VARS_CURRENT, _one_based(index))
 
+    def hessvec(self, v, lam=0.0):
+        """as N.hessvec, on the kept linear system"""
+        self._start()
+        return self.ls.hess_apply(v, lam, VARS_CURRENT)
+
+    def jacvec(self, group, v):
+        """as N.jacvec, on the kept linear system"""
+        self._start()
+        return self.ls.jac_apply(int(group), v, VARS_CURRENT)
+
+    def jactvec(self, group, u):
+        """as N.jactvec, on the kept linear system"""
+        self._start()
+        return self.ls.jact_apply(int(group), u, VARS_CURRENT)
+
+    def hessblockdiag(self, lam=0.0):
+        """the diagonal blocks of H + lam I at problem.variables: one (dof, dof) array per unfixed variable, in the order of the gradient"""
+        self._start()
+        return self.ls.hess_block_diag(lam, VARS_CURRENT)
+
+    def operator(self, lam=0.0):
+        """H + lam I at problem.variables (as they are NOW) as a linear operator: .shape, .matvec(v), .diag_blocks() -- what a Krylov method of the caller's needs"""
+        self._start()
+        return HessianOperator(self.ls, lam)
+
     def set_data(self, group, data, index=None):
         """New data (measurements) for blocks of cost group `group` (0-based, the order of problem.costs): `data` (n x ndata) for the blocks `index` (0-BASED here, as
         `group` is; distinct) or, index=None, for the first n.  Written to the device (nlls_set_cost_data) and to the problem's CostGroup: the two never disagree."""
@@ -347,6 +372,23 @@ class Solver:
             new = K.Robustifier(g.robust.kind, tuple(np.asarray(params_or_kernel, np.float64).ravel()[:4]))
         self.ls.set_robust_params(int(group), new.params)
         g.robust = new
+
+
+class HessianOperator:
+    """v -> (H + lam I) v of a linear system's CURRENT variables, evaluated on the device with every product (nlls_hess_apply): no matrix is held.  The members a
+    scipy LinearOperator has, without scipy: shape, dtype, matvec (1-D or (nvec, ndof)), and diag_blocks() for a block-Jacobi preconditioner."""
+
+    def __init__(self, ls, lam=0.0):
+        self.ls = ls; self.lam = float(lam); n = int(ls.info.ndof)
+        self.shape = (n, n); self.dtype = np.dtype(np.float64)
+
+    def matvec(self, v):
+        return self.ls.hess_apply(v, self.lam, VARS_CURRENT)
+
+    __call__ = matvec
+
+    def diag_blocks(self):
+        return self.ls.hess_block_diag(self.lam, VARS_CURRENT)
 
 
 SINGLES_MAX_DOF = 12          # NLLS_SINGLES_MAX_DOF (include/nlls_amd.h)
@@ -475,6 +517,37 @@ def computecostgradhess(problem, group=0, index=None, unfixed=None, device=0):
     ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
     try:
         return ls.eval_gradhess(int(group), VARS_CURRENT, _one_based(index))
+    finally:
+        ls.close()
+
+
+def hessvec(problem, v, lam=0.0, unfixed=None, device=0):
+    """(H + lam I) v at problem.variables, H the Hessian the linear system of `unfixed` would hold (robustified, second-order term, adaptive border included), formed
+    block by block on the device and never stored (nlls_hess_apply; src/linearsystem.jl:180-190, src/utils.jl:71-106).  v (ndof,) or (nvec, ndof), in the order of
+    the gradient.  A linear system is built and dropped per call: N.Solver keeps one."""
+    ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
+    try:
+        return ls.hess_apply(v, lam, VARS_CURRENT)
+    finally:
+        ls.close()
+
+
+def jacvec(problem, group, v, unfixed=None, device=0):
+    """J v per block of cost group `group` (0-based) at problem.variables: (ncost * M,), block i at [i * M, (i + 1) * M); J as N.computeresjac gives it, the columns
+    of fixed variables dropped (nlls_jac_apply)."""
+    ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
+    try:
+        return ls.jac_apply(int(group), v, VARS_CURRENT)
+    finally:
+        ls.close()
+
+
+def jactvec(problem, group, u, unfixed=None, device=0):
+    """J' u of cost group `group`'s blocks at problem.variables: (ndof,) in the order of the gradient (nlls_jact_apply); with u the residuals of an unrobustified
+    group, the group's share of the gradient."""
+    ls = makesymmvls(problem, convertunfixed(unfixed, problem), 0, device)
+    try:
+        return ls.jact_apply(int(group), u, VARS_CURRENT)
     finally:
         ls.close()
 
