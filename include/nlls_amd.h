@@ -445,7 +445,11 @@ int  nlls_solve(nlls_ctx* ctx, double* x_out);
  * launch (0 before the first sweep).  nlls_eval_jacobians / nlls_eval_gradhess: [43] doubles of LDS in which a wavefront stages its lanes' records before it
  * writes them out contiguously, [44], [45], [46] lanes of a wavefront staged at a time for the J / g / H of the last call that asked for them (64: all at once;
  * 0: stored directly, or not asked for yet).  The last matrix-free product (nlls_hess_apply, ...): [47] rows its gather summed one lane per unknown, [48] rows that
- * took a wavefront each, [49] chunks its vectors were cut into, [50] doubles of record scratch it used (nlls_jac_apply gathers nothing: 0, 0, 1, 0). */
+ * took a wavefront each, [49] chunks its vectors were cut into, [50] doubles of record scratch it used (nlls_jac_apply gathers nothing: 0, 0, 1, 0).
+ * The chain kernels (solve_mode 2 without block cyclic reduction: bands wider than 80, NLLS_FLAG_NO_BCR), as chosen where they are launched: [51] their form -- 0: the reduced
+ * solve is not theirs, 1: one persistent workgroup with the band window in registers, 2: the blocked factorisation from one end, 3: twisted (from both ends, NLLS_FLAG_NO_TWIST
+ * off, no border, a separator of at most 16 ceil(bw / 16) columns) -- and [52], for form 1, the window as 1000 SEG + 10 NSLOT + CH / 8 (segment length, segments per lane,
+ * columns per chunk of the HBM -> LDS ring); 0 otherwise. */
 int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
 /* Run-time switches of a context (A/B measurements, parity tests through both paths on ONE upload):
  *   NLLS_OPT_MATERIALIZE  value != 0: nlls_lm_trial eliminates from the materialised A.data (the round-5 path) although the structure qualifies for the

@@ -479,7 +479,7 @@ class Context:
         return dict(timegradient=out[0] * 1e-9, timecost=out[1] * 1e-9, timesolver=out[2] * 1e-9, trials=int(out[3]))
 
     def solve_stats(self):
-        out = np.zeros(51, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 51))
+        out = np.zeros(53, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 53))
         return dict(status=int(out[0]), band_factor_cycles=int(out[1]), band_backward_cycles=int(out[2]), solve_mode=int(out[3]),
                     elim_supernodes=int(out[4]), bandwidth=int(out[5]), bcr_mfma_issued=int(out[6]), bcr_launches=int(out[7]), bcr_levels=int(out[8]),
                     band_dof=int(out[9]), dropped_pivots=int(out[10]), reduced_row_sums=int(out[11]), lazy_trials=int(out[12]),
@@ -496,7 +496,9 @@ class Context:
                     # eval_jacobians / eval_gradhess: doubles of LDS a wavefront stages records in, lanes staged at a time for the last J / g / H asked for (0: stored directly)
                     linearize_slab=int(out[43]), linearize_batch_J=int(out[44]), linearize_batch_g=int(out[45]), linearize_batch_H=int(out[46]),
                     # the last matrix-free product: rows gathered one lane per unknown / a wavefront each, chunks its vectors were cut into, doubles of record scratch
-                    apply_short_rows=int(out[47]), apply_wave_rows=int(out[48]), apply_chunks=int(out[49]), apply_scratch=int(out[50]))
+                    apply_short_rows=int(out[47]), apply_wave_rows=int(out[48]), apply_chunks=int(out[49]), apply_scratch=int(out[50]),
+                    # the chain kernels' form of the band solve (0: not theirs; 1 register window, 2 blocked one-sided, 3 blocked twisted); form 1: 1000 SEG + 10 NSLOT + CH / 8
+                    chain_form=int(out[51]), chain_window=int(out[52]))
 
     def set_step(self, x):
         x = np.ascontiguousarray(x, np.float64); assert x.size == self.info.ndof

@@ -781,7 +781,8 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
     int32_t status[16] = {0};
     HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t vals[51] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
+    int64_t chain_form = 0, chain_window = 0; chain_form_stats(ctx, chain_form, chain_window);
+    const int64_t vals[53] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
@@ -799,8 +800,11 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
                               // [43..46] nlls_eval_jacobians / nlls_eval_gradhess: doubles of LDS a wavefront stages records in; lanes per staged sub-batch of the last call's J / g / H (0: stored directly)
                               lin_wave_slab(), ctx->lin_batch[0], ctx->lin_batch[1], ctx->lin_batch[2],
                               // [47..50] the last matrix-free product (nlls_apply.hip): rows gathered one lane per unknown / a wavefront each, chunks of vectors, doubles of record scratch
-                              ctx->app_short, ctx->app_long, ctx->app_chunks, ctx->app_scratch};
-    for (int i = 0; i < n && i < 51; ++i) out[i] = vals[i];
+                              ctx->app_short, ctx->app_long, ctx->app_chunks, ctx->app_scratch,
+                              // [51], [52] the band solver's form where the chain kernels solve the band (0: they do not; 1 register window, 2 blocked one-sided, 3 blocked twisted) and,
+                              // for form 1, the window 1000 SEG + 10 NSLOT + CH / 8
+                              chain_form, chain_window};
+    for (int i = 0; i < n && i < 53; ++i) out[i] = vals[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

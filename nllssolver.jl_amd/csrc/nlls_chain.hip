@@ -752,18 +752,33 @@ template <class F> static auto dispatch_band_window(int seg, int nseg, F&& f) {
     return f(Const<16>{}, Const<4>{});
 }
 
+// the form the chain kernels give a band: 1 the register window (band_ldlt_solve_kernel), 2 the blocked factorisation from one end, 3 twisted (two-sided):
+// two workgroups, one from each end of the band, meet at a separator of ws columns, bw <= ws <= 16 NBW, so that the sides do not touch each other
+struct ChainPlan { int form, kk, ws; };
+static ChainPlan chain_plan(const nlls_ctx* c, int n_band, int bw, int nbd, int H) {
+    if (!chain_blocked(c, bw, H)) return {1, 0, 0};
+    const int NBW = (bw + 15) / 16, kk = (n_band - bw) / 16, ws = n_band - 16 * kk;
+    const bool twisted = c->band_twisted && nbd == 0 && ws >= bw && ws <= 16 * NBW && kk >= 4 * (NBW + 2);
+    return {twisted ? 3 : 2, kk, ws};
+}
+void chain_form_stats(const nlls_ctx* c, int64_t& form, int64_t& window) {
+    form = window = 0;
+    if (c->solve_mode != SOLVE_BAND || c->bcr.ready) return;       // (not a chain solve)
+    form = chain_plan(c, (int)c->n_band, c->bw, c->nbd, c->band_H).form;
+    if (form == 1) window = dispatch_band_window(c->band_SEG, c->band_NSEG, [&](auto seg, auto nslot) { return (int64_t)(1000 * seg() + 10 * nslot() + c->band_CH / 8); });
+}
+
 // the solve of a band in band storage (c->S: [banded part | border rows | rhs row] per column, then the border corner); the solution lands in c->s_ptr()
 int enqueue_chain_solve(nlls_ctx* c, int n_band, int bw, int nbd, int H) {
     BandArgs a{}; a.Sb = c->S.p; a.Lb = c->Lwork.p; a.xr = c->s_ptr(); a.n_band = n_band; a.bw = bw; a.nbd = nbd; a.H = H; a.status = c->d_status.p;
     band_ldlt_args(c, bw, a);
     const int nbr = nbd + 1;
     const int NBW = (bw + 15) / 16;
-    if (chain_blocked(c, bw, H)) {
+    const ChainPlan plan = chain_plan(c, n_band, bw, nbd, H);
+    if (plan.form != 1) {
         const int nJb = (n_band + 15) / 16, fsz = blk_fsize(NBW, nbd);
-        // twisted (two-sided) factorisation: two workgroups, one from each end of the band, meet at a separator of
-        // ws columns, bw <= ws <= 16 NBW, so that the sides do not touch each other
-        const int kk = (n_band - bw) / 16, ws = n_band - 16 * kk;
-        const bool twisted = c->band_twisted && nbd == 0 && ws >= bw && ws <= 16 * NBW && kk >= 4 * (NBW + 2);
+        const int kk = plan.kk, ws = plan.ws;
+        const bool twisted = plan.form == 3;
         const int JA = twisted ? (kk + 1) / 2 : nJb, JB = twisted ? kk / 2 : 0, cA = 16 * JA;
         double* corner = c->Lwork.p + (size_t)nJb * fsz + 128;
         double* sepA = corner + 2 * nbr * nbr; double* sepB = sepA + (size_t)(16 * NBW) * (16 * NBW) + 16 * NBW;

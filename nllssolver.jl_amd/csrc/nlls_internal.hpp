@@ -142,6 +142,7 @@ int enqueue_solve_finish(nlls_ctx* c, const TrialArgs& t = {});
 int enqueue_tiny_dense_trial(nlls_ctx* c, int to, int from);
 int enqueue_tiny_trial_finish_pending(nlls_ctx* c);   // the finishing reduction no accumulate launch has carried   // nlls_ctx::tiny_dense: damped solve + step statistics + retraction in one launch, then the cost sweep
 int enqueue_chain_solve(nlls_ctx* c, int n_band, int bw, int nbd, int H);   // the banded reduced system by the chain kernels (nlls_chain.hip)
+void chain_form_stats(const nlls_ctx* c, int64_t& form, int64_t& window);   // which chain kernels enqueue_chain_solve launches for this structure (nlls_get_solve_stats [51], [52])
 int enqueue_reduced_solve(nlls_ctx* c, bool mf = false);   // the factorisation + backward pass of the assembled reduced system alone (timing)
 int enqueue_pack_reduce0(nlls_ctx* c);      // [cost | reduced rows | reduced b] -> redbuf
 int enqueue_unpack_reduce0(nlls_ctx* c, bool with_cost = true);

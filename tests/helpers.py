@@ -263,7 +263,7 @@ NAMED_ORDERS = dict(identity=order_identity, elim_first=order_elim_first, revers
 
 
 # ---- two-slot problems of a chosen elimination structure (the matrix-free LM trial's kernel shapes: tests/test_gpu_mf_shapes.py) -------------------
-def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3):
+def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3, border=0):
     """A problem of ONE cost group of a two-slot kind whose eliminated set and supernodes the caller chooses.  The `nred` reduced variables come first,
     the eliminated ones after them; runs = [(ncb, nmem), ...]: nmem eliminated variables in a row that share one window of ncb consecutive reduced
     variables (one cost block each), windows of neighbouring runs different -- so a run is a supernode (cut at 128 members).
@@ -271,12 +271,16 @@ def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3):
         perturbed as perturb_ba_problem does.
       kind RES_ROSENBROCK_B: b (x^2 - y), every variable one dof; ps = 1: the eliminated variable is y, ps = 0: it is x.  All blocks are of one size,
         so the greedy independent set (lowest degree first) must find every reduced variable of higher degree than every eliminated one: runs of
-        one-block members are appended to lift every reduced variable above the widest window.
+        one-block members are appended to lift every reduced variable above the widest window.  border (this kind only): the last `border` of the nred
+        reduced variables are no part of the band -- the windows are laid over the first nred - border -- and EVERY eliminated variable has one more
+        cost block on each of them: coupled to all eliminated blocks, they are what the upload orders behind the band as border rows (15 dof at most).
     Returns (problem, meta): meta["elim_blocks"] (bool per block), meta["supernodes"] (the count the grouping gives), meta["windows"] (per eliminated
     variable: its reduced neighbours, 0-based)."""
     from nllssolver_jl_amd import NLLSProblem, kinds as K
     rng = np.random.default_rng(seed)
-    windows, R = [], len(runs)
+    assert border == 0 or kind == K.RES_ROSENBROCK_B
+    windows, R, nred_all = [], len(runs), nred
+    nred = nred_all - border                # (the band's variables: what the windows are laid over)
     for r, (ncb, nmem) in enumerate(runs):
         assert 1 <= ncb <= nred
         span = nred - ncb + 1; start = int(round(r * (span - 1) / max(R - 1, 1)))          # (the windows spread over the reduced variables)
@@ -288,11 +292,13 @@ def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3):
         if cover[j] == 0:
             ncb = runs[0][0]; start = min(j, nred - ncb); windows.append(tuple(range(start, start + ncb))); cover[start:start + ncb] += 1
     if kind == K.RES_ROSENBROCK_B:
-        top = max(len(w) for w in windows)
+        top = max(len(w) for w in windows) + border
         for j in np.nonzero(cover <= top)[0]:
             windows += [(int(j),)] * int(top + 1 - cover[j])
+        windows = [w + tuple(range(nred, nred_all)) for w in windows]
     else:
         assert kind == K.RES_BA_AFFINE and ps == 1
+    nred = nred_all
     nelim = len(windows)
     assert nelim * 2 >= nred + nelim, "the eliminated variables must be at least half of all blocks"
     p = NLLSProblem()

@@ -186,6 +186,16 @@ def _upload_info(p, flags=0):
     return info, st
 
 
+def _chain_form(p, unfixed=None, flags=0):
+    """nlls_get_solve_stats [51] of this problem's upload: 1 where the register-window chain kernel (band_ldlt_solve_kernel) solves the band.  The seeds of the
+    randomized tests that reach it do so by luck of the draw (bands of 81 .. 126 that the cyclic reduction does not take): pinned, so that a change of the upload's
+    choice or of a generator that moves them elsewhere shows.  tests/test_gpu_chain_shapes.py aims at that kernel's shapes."""
+    ctx = _capi.Context()
+    ctx.upload(p.var_kind, p.var_dim, blockindices(p, unfixed), p.groups(), flags)
+    st = ctx.solve_stats(); ctx.close()
+    return st["chain_form"]
+
+
 @pytest.mark.parametrize("ncam,npts,prop,seed", [(40, 1500, 0.12, 31), (150, 6000, 0.04, 32), (300, 9000, 0.03, 33)])
 @pytest.mark.parametrize("reorder", [1, 0])
 def test_shuffled_camera_labels(ncam, npts, prop, seed, reorder):
@@ -508,6 +518,7 @@ def test_randomized_ba_against_oracle(seed):
     flags = [0, _capi.FLAG_NO_BCR, _capi.FLAG_FORCE_ATOMIC, _capi.FLAG_NO_BAND, _capi.FLAG_NO_BCR | _capi.FLAG_NO_TWIST, _capi.FLAG_FORCE_SPARSE][int(rng.integers(0, 6))]
     if seed % 3 == 0: flags |= _capi.FLAG_DETERMINISTIC
     check_problem(p, unfixed=unfixed, flags=flags, lam_scale=[1e-6, 1e-4, 1e-1, 1e-2][kind])
+    if seed in (118, 128): assert _chain_form(p, unfixed, flags) == 1      # (bw 101 and 89 with the 12 border unknowns of two end cameras)
 
 
 def test_reupload_on_one_context():
@@ -541,6 +552,7 @@ def test_randomized_so3_against_oracle(seed):
     if rng.random() < 0.3:
         unfixed = np.ones(p.nvariables, bool); unfixed[rng.choice(p.nvariables, size=max(1, p.nvariables // 25), replace=False)] = False
     check_problem(p, unfixed=unfixed, expect_sparse=1, lam_scale=1e-4 if robust is None or adaptive else 1e-1)
+    if seed in (305, 306, 311): assert _chain_form(p, unfixed) == 1        # (bw 101, 113, 89; borders of 12, 0, 12 unknowns)
 
 
 @pytest.mark.parametrize("seed", list(range(600, 616)))
