@@ -381,6 +381,33 @@ int  nlls_jact_apply(nlls_ctx* ctx, int32_t which, int32_t group, int32_t nvec, 
  *   the diagonal blocks of H + lambda I, a block-Jacobi preconditioner */
 int  nlls_hess_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d_out);
 
+/* ---- conjugate gradients on the device ------------------------------------------------------------------------------
+ * replaces: solve!(linsystem) + negate!(linsystem.x) of the iterators (src/linearsystem.jl:180-190, src/iterators.jl:149-157) by an ITERATIVE solve: no reduced
+ *           system, no factorisation, no read of A.data; with maxiters small, a truncated-Newton (inexact) step.
+ * nlls_solve_pcg stands where nlls_solve stands: it solves (H + lambda I) y = b by preconditioned conjugate gradients from y = 0 and leaves x = -y as the context's
+ * step.  lambda: the damping nlls_damp has accumulated; b: the gradient of the last sweep, as nlls_get_grad returns it; H: applied by the launches of nlls_hess_apply at
+ * NLLS_VARS_CURRENT, one vector per iteration, on device pointers (the caveat stated there holds: H is evaluated, and equals the sweep's A only while CURRENT holds what
+ * the sweep saw).  The preconditioner is the identity or the inverse of the diagonal blocks of H + lambda I (nlls_hess_block_diag, factored once per call).
+ * It stops when the residual of the recurrence satisfies ||r||_2 <= rtol ||b||_2 (status 0) or after maxiters iterations (status 1); both return NLLS_OK and set the
+ * step -- a truncated iterate from 0 is a descent direction.  ||b|| == 0: x = 0, status 0, 0 iterations.  Breakdown: status 2 -- p'(H + lambda I)p is not > 0, or a
+ * scalar of the recurrence is not finite -- and status 3 -- a diagonal block of the block-Jacobi preconditioner is not positive definite -- return NLLS_ERR_NOT_SPD
+ * (what the iterators answer with more damping) and leave the context's step, x_out and everything else byte for byte as before the call: only stats_out and the
+ * counters below are written.
+ * stats_out[8] (may be NULL): [0] iterations made (status 2: the iteration that broke down, counted from 1), [1] status, [2] ||b||_2 (status 3: 0, the start never
+ * ran), [3] ||r||_2 of the recurrence at exit, [4] stream synchronisations of the call (one per round of NLLS_OPT_PCG_ROUND iterations, one more for the step it
+ * sets), [5] launches it enqueued, [6], [7] 0.
+ * Every sum has a fixed order and nothing adds with atomics: two calls on the same sweep return identical bytes, and so do calls that differ only in
+ * NLLS_OPT_PCG_ROUND.  The host looks at the stop flag once per round; the iterations enqueued behind a stop change nothing but the product's scratch.
+ * NLLS_ERR_INVALID_ARG -- nothing enqueued -- for a null context, a precond other than the two, maxiters < 1, rtol not finite or < 0; NLLS_ERR_NOT_READY before an
+ * upload or without a sweep (as nlls_solve); NLLS_ERR_UNSUPPORTED where nlls_hess_apply is: a group of a dynamic-size kind, nlls_set_shard with nranks > 1.
+ * ndof == 0: NLLS_OK.  On success the step is the caller's as after nlls_set_step: nlls_retract, nlls_step_maxabs, nlls_step_norm, nlls_quadform and nlls_get_step
+ * see it.  Success or breakdown, A.data, b, the variable sets, the damping and the validity state of the linearisation are untouched; the solver works in buffers of
+ * its own (allocated at the first call after an upload).  nlls_get_solve_stats [53..55] and nlls_get_phase_times [14] report the last call; [47..50] there then
+ * describe its last product. */
+#define NLLS_PCG_PRECOND_NONE          0   /* M = I */
+#define NLLS_PCG_PRECOND_BLOCK_JACOBI  1   /* M = the diagonal blocks of H + lambda I (nlls_hess_block_diag) */
+int  nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out);
+
 /* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
  * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
  *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.
@@ -449,7 +476,8 @@ int  nlls_solve(nlls_ctx* ctx, double* x_out);
  * The chain kernels (solve_mode 2 without block cyclic reduction: bands wider than 80, NLLS_FLAG_NO_BCR), as chosen where they are launched: [51] their form -- 0: the reduced
  * solve is not theirs, 1: one persistent workgroup with the band window in registers, 2: the blocked factorisation from one end, 3: twisted (from both ends, NLLS_FLAG_NO_TWIST
  * off, no border, a separator of at most 16 ceil(bw / 16) columns) -- and [52], for form 1, the window as 1000 SEG + 10 NSLOT + CH / 8 (segment length, segments per lane,
- * columns per chunk of the HBM -> LDS ring); 0 otherwise. */
+ * columns per chunk of the HBM -> LDS ring); 0 otherwise.  The last nlls_solve_pcg: [53] iterations made, [54] its status (0 converged, 1 maxiters, 2 and 3
+ * breakdown), [55] stream synchronisations it took; [47..50] then describe the last product it enqueued. */
 int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
 /* Run-time switches of a context (A/B measurements, parity tests through both paths on ONE upload):
  *   NLLS_OPT_MATERIALIZE  value != 0: nlls_lm_trial eliminates from the materialised A.data (the round-5 path) although the structure qualifies for the
@@ -458,19 +486,26 @@ int  nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n);
  *   NLLS_OPT_PHASE_EVENTS see below.
  *   NLLS_OPT_APPLY_SCRATCH  bytes of record scratch the matrix-free products may hold (default 256 MiB): a call whose vectors need more is cut into chunks of
  *                         vectors (one vector's records are always held).  NLLS_OPT_APPLY_WAVE_MIN  incidences from which an unknown's row is summed by a
- *                         wavefront of its own (default 64; values below 1 count as 1).  Both outlive an upload. */
+ *                         wavefront of its own (default 64; values below 1 count as 1).  Both outlive an upload.
+ *   NLLS_OPT_PCG_ROUND    iterations nlls_solve_pcg enqueues between two looks at its stop flag (default 1, >= 1): a longer round saves synchronisations and spends
+ *                         up to round - 1 empty iterations behind the stop.  The result does not depend on it.  NLLS_OPT_PCG_GRID_MAX  most workgroups of its vector
+ *                         kernels (default 1024, >= 1): longer vectors are walked with a grid-stride loop; the partial sums group by it, so results agree to
+ *                         rounding, not to the bit, across values.  Both outlive an upload; values below 1: NLLS_ERR_INVALID_ARG. */
 /* Device-timed NLLSResult buckets since the upload, nanoseconds: out[0] gradient, [1] cost, [2] solver, [3] trials counted (single-GPU sparse trials; others leave them untouched). */
 int  nlls_get_time_buckets(nlls_ctx* ctx, int64_t* out, int32_t n);
 #define NLLS_OPT_MATERIALIZE 1
 #define NLLS_OPT_LOOKAHEAD   2
 #define NLLS_OPT_APPLY_SCRATCH  4
 #define NLLS_OPT_APPLY_WAVE_MIN 5
+#define NLLS_OPT_PCG_ROUND     6
+#define NLLS_OPT_PCG_GRID_MAX  7
 #define NLLS_OPT_PHASE_EVENTS 3   /* value != 0: the COLLECTIVE nlls_lm_trial records stream events at its phase boundaries (resets the sums); nlls_get_phase_times reads them */
 /* out[0..4]: milliseconds summed over the trials since NLLS_OPT_PHASE_EVENTS was set -- [0] this rank's assembly of [S | s] (elimination), [1] the all-reduce of [S | s] (wait included),
  * [2] the reduced solve (every rank), [3] back-substitution + retraction, [4] trial tail (statistics, cost sweep, the scalars' gather); [5] gradient sweeps (ms summed), [6] trials, [7] sweeps counted.
  * [8] milliseconds of the last nlls_set_cost_data's scatter launch alone (an event pair around it, while the option is set; waits for it), [9] the device copies of the payload the last such launch wrote.
  * [10] milliseconds of the last nlls_eval_jacobians / nlls_eval_gradhess launch alone (the same: an event pair, while the option is set), [11] the bytes of records that call's launch wrote.
- * [12] milliseconds of the last matrix-free product's launches (nlls_hess_apply, nlls_jac_apply, nlls_jact_apply, nlls_hess_block_diag: one event pair around all of them), [13] the bytes of records and output they wrote. */
+ * [12] milliseconds of the last matrix-free product's launches (nlls_hess_apply, nlls_jac_apply, nlls_jact_apply, nlls_hess_block_diag: one event pair around all of them), [13] the bytes of records and output they wrote.
+ * [14] milliseconds of the last nlls_solve_pcg's launches, products included (one event pair from its first launch to the launch that sets the step). */
 int  nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n);
 int  nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value);
 int  nlls_set_step(nlls_ctx* ctx, const double* x);               /* host-formed steps (dogleg, GD) */

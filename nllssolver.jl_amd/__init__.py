@@ -20,6 +20,8 @@ def __getattr__(name):
     if name in ("optimize", "optimizesingles", "NLLSOptions", "NLLSResult", "cost", "residuals", "squarederrors", "computeresjac", "computecostgradhess", "jacobian", "hessvec", "jacvec", "jactvec", "HessianOperator", "Solver", "NLLSIterator", "newton", "levenbergmarquardt", "dogleg",
                 "gradientdescent"):
         return getattr(importlib.import_module(__name__ + ".optimizer"), name)
+    if name == "PCG":                                # NLLSOptions(linearsolver=PCG(...)): conjugate gradients on the device in place of the direct solve
+        return importlib.import_module(__name__ + ".iterators").PCG
     if name in ("MultiVariateLSgpu", "makesymmvls"):
         return getattr(importlib.import_module(__name__ + ".linearsystem"), name)
     if name in ("nullcallback", "printoutcallback", "storecostscallback", "CostTrajectory", "emcallback"):

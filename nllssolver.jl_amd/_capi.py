@@ -22,6 +22,10 @@ FLAG_NO_PIVOT_FLOOR = 1024
 FLAG_MATERIALIZE = 2048
 OPT_MATERIALIZE, OPT_LOOKAHEAD, OPT_PHASE_EVENTS = 1, 2, 3
 OPT_APPLY_SCRATCH, OPT_APPLY_WAVE_MIN = 4, 5
+OPT_PCG_ROUND, OPT_PCG_GRID_MAX = 6, 7
+PCG_PRECOND_NONE, PCG_PRECOND_BLOCK_JACOBI = 0, 1
+PCG_PRECONDS = {"none": PCG_PRECOND_NONE, None: PCG_PRECOND_NONE, "blockjacobi": PCG_PRECOND_BLOCK_JACOBI}
+PCG_STATUS = {0: "converged", 1: "maxiters", 2: "breakdown", 3: "preconditioner not positive definite"}
 APPLY_MAX_VEC = 8
 VARS_CURRENT, VARS_NEXT, VARS_BEST = 0, 1, 2
 
@@ -36,7 +40,7 @@ nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_own
 nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
 nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
 nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim
-nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag""".split()
+nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -135,6 +139,7 @@ def lib():
         L.nlls_res_jac_cols.argtypes = [i32]; L.nlls_res_gh_dim.argtypes = [i32]
         L.nlls_hess_apply.argtypes = [vp, i32, dbl, i32, vp, vp]; L.nlls_jac_apply.argtypes = [vp, i32, i32, i32, vp, vp]
         L.nlls_jact_apply.argtypes = [vp, i32, i32, i32, vp, vp]; L.nlls_hess_block_diag.argtypes = [vp, i32, dbl, vp]
+        L.nlls_solve_pcg.argtypes = [vp, i32, i32, dbl, vp, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -384,6 +389,18 @@ class Context:
         self._chk(self.L.nlls_solve(self.h, _p(out)))
         return out
 
+    def solve_pcg(self, precond=PCG_PRECOND_BLOCK_JACOBI, maxiters=None, rtol=1e-8, want_x=False):
+        """nlls_solve_pcg: the step by conjugate gradients on the matrix-free operator, (H + lambda I) y = b from 0, x = -y, where solve() factors.  precond: 1 / "blockjacobi",
+        0 / "none"; maxiters: 4 ndof when None.  -> (x or None, stats) with stats = dict(iterations, status (0 converged, 1 maxiters), bnorm, rnorm, rounds, launches).
+        A breakdown (status 2, 3) raises NllsError with code ERR_NOT_SPD, as solve() does for a bad pivot, and leaves the step as it was; last_pcg holds its stats."""
+        pc = PCG_PRECONDS[precond] if isinstance(precond, str) or precond is None else int(precond)
+        mi = max(4 * int(self.info.ndof), 1) if maxiters is None else int(maxiters)
+        out = np.zeros(self.info.ndof) if want_x else None; st = np.zeros(8)
+        rc = self.L.nlls_solve_pcg(self.h, pc, mi, float(rtol), _p(out), _p(st))
+        self.last_pcg = dict(iterations=int(st[0]), status=int(st[1]), bnorm=float(st[2]), rnorm=float(st[3]), rounds=int(st[4]), launches=int(st[5]))
+        self._chk(rc)
+        return out, self.last_pcg
+
     def lm_trial(self, dlambda, to=VARS_NEXT, frm=VARS_CURRENT):
         """damp + solve + retract + cost sweep in one call / one synchronisation; returns the trial cost."""
         out = C.c_double()
@@ -461,17 +478,18 @@ class Context:
 
     def set_option(self, option, value):
         """nlls_set_option: OPT_MATERIALIZE (1: nlls_lm_trial eliminates from the materialised A.data, 0: matrix-free where it applies), OPT_LOOKAHEAD,
-        OPT_APPLY_SCRATCH (bytes of record scratch of the matrix-free products), OPT_APPLY_WAVE_MIN (incidences from which a row gets a wavefront)"""
+        OPT_APPLY_SCRATCH (bytes of record scratch of the matrix-free products), OPT_APPLY_WAVE_MIN (incidences from which a row gets a wavefront),
+        OPT_PCG_ROUND (iterations solve_pcg enqueues between two looks at its stop flag), OPT_PCG_GRID_MAX (most workgroups of its vector kernels)"""
         self._chk(self.L.nlls_set_option(self.h, int(option), int(value)))
 
     def phase_times(self):
         """nlls_get_phase_times: microseconds per collective trial by phase (stream events; NLLS_OPT_PHASE_EVENTS) and per gradient sweep"""
-        out = np.zeros(14); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 14)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
+        out = np.zeros(15); self._chk(self.L.nlls_get_phase_times(self.h, _p(out), 15)); nt, ns = max(out[6], 1.0), max(out[7], 1.0)
         return dict(trials=int(out[6]), sweeps=int(out[7]), elimination_us=1e3 * out[0] / nt, allreduce_S_us=1e3 * out[1] / nt, reduced_solve_us=1e3 * out[2] / nt,
                     backsub_retraction_us=1e3 * out[3] / nt, trial_tail_us=1e3 * out[4] / nt, gradient_sweep_us=1e3 * out[5] / ns,
                     update_scatter_us=1e3 * out[8], update_copies=int(out[9]),
                     linearize_us=1e3 * out[10], linearize_bytes=int(out[11]),
-                    apply_us=1e3 * out[12], apply_bytes=int(out[13]))
+                    apply_us=1e3 * out[12], apply_bytes=int(out[13]), pcg_us=1e3 * out[14])
 
     def time_buckets(self):
         """device-timed NLLSResult buckets since the upload: seconds (gradient, cost, solver) and the trials counted"""
@@ -479,7 +497,7 @@ class Context:
         return dict(timegradient=out[0] * 1e-9, timecost=out[1] * 1e-9, timesolver=out[2] * 1e-9, trials=int(out[3]))
 
     def solve_stats(self):
-        out = np.zeros(53, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 53))
+        out = np.zeros(56, np.int64); self._chk(self.L.nlls_get_solve_stats(self.h, _p(out), 56))
         return dict(status=int(out[0]), band_factor_cycles=int(out[1]), band_backward_cycles=int(out[2]), solve_mode=int(out[3]),
                     elim_supernodes=int(out[4]), bandwidth=int(out[5]), bcr_mfma_issued=int(out[6]), bcr_launches=int(out[7]), bcr_levels=int(out[8]),
                     band_dof=int(out[9]), dropped_pivots=int(out[10]), reduced_row_sums=int(out[11]), lazy_trials=int(out[12]),
@@ -498,7 +516,9 @@ class Context:
                     # the last matrix-free product: rows gathered one lane per unknown / a wavefront each, chunks its vectors were cut into, doubles of record scratch
                     apply_short_rows=int(out[47]), apply_wave_rows=int(out[48]), apply_chunks=int(out[49]), apply_scratch=int(out[50]),
                     # the chain kernels' form of the band solve (0: not theirs; 1 register window, 2 blocked one-sided, 3 blocked twisted); form 1: 1000 SEG + 10 NSLOT + CH / 8
-                    chain_form=int(out[51]), chain_window=int(out[52]))
+                    chain_form=int(out[51]), chain_window=int(out[52]),
+                    # the last solve_pcg: iterations made, status (0 converged, 1 maxiters, 2 / 3 breakdown), stream synchronisations
+                    pcg_iterations=int(out[53]), pcg_status=int(out[54]), pcg_rounds=int(out[55]))
 
     def set_step(self, x):
         x = np.ascontiguousarray(x, np.float64); assert x.size == self.info.ndof

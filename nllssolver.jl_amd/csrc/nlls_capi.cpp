@@ -523,6 +523,18 @@ int nlls_solve(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
+// The same solve by conjugate gradients on the matrix-free operator (nlls_pcg.hip): (H + lambda I) y = b from y = 0, x = -y.  Everything is refused here, before anything is
+// enqueued; the solver's rounds synchronise.  On success the transition nlls_set_step makes (step_replaced, inside pcg_solve); a breakdown leaves x as it was.
+int nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out) { NLLS_API_BEGIN
+    if (!ctx) return NLLS_ERR_INVALID_ARG;
+    if ((precond != NLLS_PCG_PRECOND_NONE && precond != NLLS_PCG_PRECOND_BLOCK_JACOBI) || maxiters < 1 || !std::isfinite(rtol) || rtol < 0) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg: bad preconditioner, maxiters or rtol");
+    NEED_GRAD_LAZY();
+    TRY(apply_check(ctx, "nlls_solve_pcg", -1, false));
+    if (ctx->info.ndof == 0) { ctx->pcg_iters = ctx->pcg_status = ctx->pcg_rounds = 0; if (stats_out) for (int k = 0; k < 8; ++k) stats_out[k] = 0.0; return NLLS_OK; }
+    TRY(ensure_grad(ctx, 2)); TRY(ensure_reduced_summed(ctx));      // (b as nlls_get_grad reads it)
+    return pcg_solve(ctx, precond, maxiters, rtol, x_out, stats_out);
+    NLLS_API_END(ctx)
+}
 // One Levenberg-Marquardt trial in one call and one synchronisation (src/iterators.jl:149-157): uniformscaling!(H, dlambda),
 // solve!, negate!, update!(to, from, x), cost(to).  Same kernels, same order as the separate entry points.
 int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, double* cost_out) { NLLS_API_BEGIN
@@ -754,9 +766,11 @@ int nlls_get_phase_times(nlls_ctx* ctx, double* out, int32_t n) { NLLS_API_BEGIN
         if (hipEventSynchronize(ctx->phase_ev[11]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[10], ctx->phase_ev[11]) == hipSuccess) ctx->lin_ms = ms; else (void)hipGetLastError(); }
     if (take(ctx->app_pending) && ctx->phase_ev.size() >= 14) { float ms = 0.f; (void)hipSetDevice(ctx->device);
         if (hipEventSynchronize(ctx->phase_ev[13]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[12], ctx->phase_ev[13]) == hipSuccess) ctx->app_ms = ms; else (void)hipGetLastError(); }
-    const double v[14] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies,
-                          ctx->lin_ms, ctx->lin_bytes, ctx->app_ms, ctx->app_bytes};
-    for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
+    if (take(ctx->pcg_pending) && ctx->phase_ev.size() >= 16) { float ms = 0.f; (void)hipSetDevice(ctx->device);
+        if (hipEventSynchronize(ctx->phase_ev[15]) == hipSuccess && hipEventElapsedTime(&ms, ctx->phase_ev[14], ctx->phase_ev[15]) == hipSuccess) ctx->pcg_ms = ms; else (void)hipGetLastError(); }
+    const double v[15] = {ctx->phase_ms[0], ctx->phase_ms[1], ctx->phase_ms[2], ctx->phase_ms[3], ctx->phase_ms[4], ctx->phase_ms[5], (double)ctx->phase_trials, (double)ctx->phase_sweeps, ctx->upd_ms, (double)ctx->upd_copies,
+                          ctx->lin_ms, ctx->lin_bytes, ctx->app_ms, ctx->app_bytes, ctx->pcg_ms};
+    for (int i = 0; i < n && i < 15; ++i) out[i] = v[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
@@ -767,11 +781,13 @@ int nlls_set_option(nlls_ctx* ctx, int32_t option, int64_t value) { NLLS_API_BEG
     case NLLS_OPT_LOOKAHEAD:   ctx->sw.spec_on = value != 0; return NLLS_OK;
     case NLLS_OPT_PHASE_EVENTS:
         ctx->phase_on = value != 0; (void)hipSetDevice(ctx->device);
-        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(14); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
+        if (ctx->phase_on && ctx->phase_ev.empty()) { ctx->phase_ev.resize(16); for (auto& e : ctx->phase_ev) if (hipEventCreate(&e) != hipSuccess) return NLLS_ERR_HIP; }
         if (ctx->phase_on) { for (double& v : ctx->phase_ms) v = 0.0; ctx->phase_trials = ctx->phase_sweeps = 0; }
         return NLLS_OK;
     case NLLS_OPT_APPLY_SCRATCH:  if (value < 0) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_option: NLLS_OPT_APPLY_SCRATCH takes bytes"); ctx->app_scratch_cap = value; return NLLS_OK;
     case NLLS_OPT_APPLY_WAVE_MIN: ctx->app_wave_min = std::max<int64_t>(value, 1); return NLLS_OK;      // (the rows are classed again by the next product)
+    case NLLS_OPT_PCG_ROUND:    if (value < 1) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_option: NLLS_OPT_PCG_ROUND takes iterations >= 1"); ctx->pcg_round = value; return NLLS_OK;
+    case NLLS_OPT_PCG_GRID_MAX: if (value < 1) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_option: NLLS_OPT_PCG_GRID_MAX takes workgroups >= 1"); ctx->pcg_grid_max = value; return NLLS_OK;
     }
     return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_set_option: unknown option");
     NLLS_API_END(ctx)
@@ -782,7 +798,7 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
     HIP_TRY(ctx, hipMemcpyAsync(status, ctx->d_status.p, sizeof(status), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     int64_t chain_form = 0, chain_window = 0; chain_form_stats(ctx, chain_form, chain_window);
-    const int64_t vals[53] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
+    const int64_t vals[56] = {status[0], (int64_t)status[2] << 10, (int64_t)status[3] << 10, ctx->solve_mode, ctx->nelim_groups, ctx->bw,
                               ctx->bcr.ready ? ctx->bcr.mfma_issued : 0, ctx->bcr.ready ? ctx->bcr.launches : 0, ctx->bcr.ready ? (int64_t)ctx->bcr.levels.size() : 0, ctx->n_band,
                               status[4] /* pivots the floor of the last undamped band solve dropped */, ctx->n_stage0, ctx->n_lazy_trials, ctx->red_reordered, ctx->bw_caller, ctx->dense_window ? 1 : 0,
                               ctx->tsp.ready ? ctx->tsp.nt : 0, ctx->tsp.ready ? (int64_t)ctx->tsp.levels.size() : 0, ctx->tsp.ready ? ctx->tsp.nslots : 0, ctx->tsp.ready ? ctx->tsp.launches : 0, ctx->tsp.ready ? ctx->tsp.products : 0,
@@ -803,8 +819,10 @@ int nlls_get_solve_stats(nlls_ctx* ctx, int64_t* out, int32_t n) { NLLS_API_BEGI
                               ctx->app_short, ctx->app_long, ctx->app_chunks, ctx->app_scratch,
                               // [51], [52] the band solver's form where the chain kernels solve the band (0: they do not; 1 register window, 2 blocked one-sided, 3 blocked twisted) and,
                               // for form 1, the window 1000 SEG + 10 NSLOT + CH / 8
-                              chain_form, chain_window};
-    for (int i = 0; i < n && i < 53; ++i) out[i] = vals[i];
+                              chain_form, chain_window,
+                              // [53..55] the last nlls_solve_pcg: iterations made, status, synchronisations
+                              ctx->pcg_iters, ctx->pcg_status, ctx->pcg_rounds};
+    for (int i = 0; i < n && i < 56; ++i) out[i] = vals[i];
     return NLLS_OK;
     NLLS_API_END(ctx)
 }

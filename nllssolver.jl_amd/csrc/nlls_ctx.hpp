@@ -228,6 +228,13 @@ struct ApplyIndex {
     uint32_t nslots = 0; int part_w_vec = 1, part_w_diag = 1;      // segments of all cut rows; widest cut row (unknowns; entries of its diagonal block)
 };
 
+// ---- block-Jacobi conjugate gradients on the device (nlls_pcg.hip): nlls_solve_pcg ---------------------------------------------------------------------------
+// Buffers of the solver's own, outside the hot arena: allocated at the first call after an upload, dropped by the next one.  vec: y, r0, r1, z, p, q (ndof each);
+// Minv: the inverses of the diagonal blocks of H + lambda I (sum of dof_b^2, the layout of nlls_hess_block_diag); part: three rows of per-workgroup partial sums
+// (p'q | r'z | r'r); scal: the scalar block PCG_* below.
+enum { PCG_RZ0 = 0, PCG_RZ1 = 1, PCG_PQ = 2, PCG_RR = 3, PCG_BB = 4, PCG_ITER = 5, PCG_STOP = 6, PCG_STATUS = 7, PCG_NSCAL = 8 };   // r'z by parity of the iteration, p'q, r'r, b'b, iterations, stop, status
+struct PcgState { DevBuf<double> vec, Minv, part, scal; int64_t ndof = 0, pw = 0; };      // pw: doubles of one row of part
+
 }  // namespace nlls
 
 struct nlls_ctx {
@@ -281,7 +288,7 @@ struct nlls_ctx {
     nlls::DevBuf<double> partials;           // per-workgroup cost partials
     int num_cus = 256;
     nlls::DevBuf<double> scalars;            // small device scratch for scalar results
-    double* h_scalars = nullptr;             // pinned host mirror
+    double* h_scalars = nullptr;             // pinned host mirror (64 doubles; [48, 56): nlls_solve_pcg's scalar block, once per round)
     int64_t trial_seq = 0;                   // sequence number the trial's finishing launch publishes in h_scalars[32], [33]
     double* h_scalars_dev = nullptr;         // ... as the device sees it (the trial's finishing launch writes the scalars there itself)
     int64_t npartials = 0;
@@ -414,4 +421,10 @@ struct nlls_ctx {
     int64_t app_scratch_cap = (int64_t)256 << 20, app_wave_min = 64;
     int64_t app_short = 0, app_long = 0, app_chunks = 0, app_scratch = 0;
     bool app_pending = false; double app_ms = 0.0, app_bytes = 0.0;
+    // nlls_solve_pcg (nlls_pcg.hip).  The two options outlive an upload (nlls_set_option); the counters are those of the last call (nlls_get_solve_stats [53..55]); under
+    // NLLS_OPT_PHASE_EVENTS a call's launches sit between phase_ev[14] and [15] (nlls_get_phase_times [14])
+    nlls::PcgState pcg;
+    int64_t pcg_round = 1, pcg_grid_max = 1024;      // (the round length with the smallest wall time on ba_1kx100k: notes/r18.md)
+    int64_t pcg_iters = 0, pcg_status = 0, pcg_rounds = 0;
+    bool pcg_pending = false; double pcg_ms = 0.0;
 };

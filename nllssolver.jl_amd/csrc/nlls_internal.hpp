@@ -74,6 +74,9 @@ int enqueue_jac_apply(nlls_ctx* c, int which, int group, int nvec, const double*
 int enqueue_jact_apply(nlls_ctx* c, int which, int group, int nvec, const double* d_u, double* d_y);
 int enqueue_hess_block_diag(nlls_ctx* c, int which, double lambda, double* d_out);
 int64_t apply_diag_len(const nlls_ctx* c);     // doubles of nlls_hess_block_diag's output
+// block-Jacobi conjugate gradients on (H + c->lambda I) y = b with the products above (nlls_pcg.hip): the caller has checked the arguments and holds b; synchronises once per
+// round of c->pcg_round iterations.  NLLS_OK: c->x = -y (and x_out, host, if not null); NLLS_ERR_NOT_SPD: a breakdown, c->x and x_out untouched.  stats: nlls_solve_pcg's (may be null)
+int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats);
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);

@@ -1,0 +1,247 @@
+// nlls_pcg.hip -- nlls_solve_pcg: preconditioned conjugate gradients on (H + lambda I) y = b, on the device (gfx950).
+//
+//   the linear solve of the iterators            src/linearsystem.jl:180-190, src/iterators.jl:149-157 (solve!, negate!)
+//
+// H is applied by enqueue_hess_apply (nlls_apply.hip) on device pointers -- evaluated at CURRENT, never read from A.data -- and the preconditioner is the inverse of the
+// diagonal blocks enqueue_hess_block_diag leaves (block Jacobi), or the identity.  The vector work is three launches per iteration behind the product's:
+//   pcg_dot   partials of p'q, one per workgroup
+//   pcg_step  alpha = r'z / p'q;  y += alpha p;  r_new = r_old - alpha q (into the OTHER r buffer);  z = Minv r_new;  partials of r'z and r'r
+//   pcg_dir   beta = r'z / (r'z of the iteration before);  p = z + beta p;  workgroup 0: the scalars, the iteration counter, the stop test
+// Every sum has a fixed order -- a lane's grid-stride terms in index order, block_sum's tree, the partials of all workgroups strided over the lanes of EVERY workgroup
+// and the same tree again, so that all workgroups hold the same scalar -- and nothing adds with atomics: two calls on the same b return identical bytes.
+// Stop: every kernel of this file returns at entry when PCG_STOP is set, so the iterations the host enqueued behind it (it looks once per round of nlls_ctx::pcg_round
+// iterations) cost their launches and the product, and change nothing: the result does not depend on the round length.  The flag is written where the writer's own
+// launch cannot be harmed by it: on a breakdown every workgroup takes the same decision and writes nothing; on convergence only p, which nobody reads again, may stay
+// partly updated.  Built like nlls_apply.o, WITHOUT -fno-honor-nans: a NaN in b or in a product reaches the breakdown tests below.
+#include <algorithm>
+#include <cmath>
+
+#include "nlls_wave.hpp"
+
+namespace nlls {
+
+struct PcgArgs {
+    const uint32_t* erow; const uint32_t* start; const uint32_t* dstart; const int32_t* bsz;      // ApplyIndex::erow_vec, start_vec, start_diag; nlls_ctx::d_blocksizes
+    int64_t ndof, nblocks; int precond, npart, parity;      // npart: workgroups of the vector kernels (= partials per row); parity: of the iteration (which r'z slot is the old one)
+    double rtol2;
+    const double* b; const double* Minv; double* y; const double* r_old; double* r_new; double* z; double* p; const double* q;
+    double* pa; double* pb; double* pc; double* scal;       // partials of p'q, r'z, r'r
+};
+
+// the stop flag as ONE value for the whole workgroup (a barrier follows in every kernel: lanes that read it at different times must not part ways)
+NLLS_DEV bool pcg_stopped(const double* scal, double* red) {
+    if (threadIdx.x == 0) red[8] = scal[PCG_STOP];
+    __syncthreads();
+    return red[8] != 0.0;
+}
+// the same sum of `n` partials in every workgroup: lane t takes t, t + TPB, ... in order, then block_sum's tree; broadcast through red[9]
+NLLS_DEV double pcg_total(const double* __restrict__ part, int n, double* red) {
+    double s = 0;
+    for (int i = (int)threadIdx.x; i < n; i += TPB) s += part[i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) red[9] = s;
+    __syncthreads();
+    s = red[9];
+    __syncthreads();
+    return s;
+}
+// z[e] = row of the block's inverse times the block's r, r formed by rk(k) for entry k of the block (precond 0: z = r)
+template <class RF>
+NLLS_DEV double pcg_prec(const PcgArgs& a, int64_t e, double re, RF&& rk) {
+    if (!a.precond) return re;
+    const uint32_t row = a.erow[e]; const int32_t d = a.bsz[row]; const int64_t s0 = a.start[row];
+    const double* __restrict__ m = a.Minv + a.dstart[row] + (int64_t)(e - s0) * d;      // column e - s0 of a symmetric block: contiguous
+    double s = 0;
+    for (int k = 0; k < d; ++k) s += m[k] * rk(s0 + k);
+    return s;
+}
+
+// One lane per diagonal block of H + lambda I (column-major dof x dof, as enqueue_hess_block_diag left it): Cholesky, the factor's inverse, the block's inverse, all in
+// place, run-time dof up to NLLS_MAX_BLOCK_SZ.  A pivot that is not > 0 (NaN included): status 3 and stop.  Once per solve.
+__global__ __launch_bounds__(TPB) void pcg_factor_kernel(PcgArgs a, double* __restrict__ Minv) {
+    const int64_t blk = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (blk >= a.nblocks) return;
+    const int d = a.bsz[blk]; double* __restrict__ M = Minv + a.dstart[blk];
+    bool bad = false;
+    for (int j = 0; j < d && !bad; ++j) {                   // M = L L', L in the lower triangle
+        double piv = M[j + j * d];
+        for (int k = 0; k < j; ++k) piv -= M[j + k * d] * M[j + k * d];
+        if (!(piv > 0.0)) { bad = true; break; }
+        piv = sqrt(piv); M[j + j * d] = piv;
+        for (int i = j + 1; i < d; ++i) { double s = M[i + j * d];
+            for (int k = 0; k < j; ++k) s -= M[i + k * d] * M[j + k * d];
+            M[i + j * d] = s / piv; }
+    }
+    if (bad) { a.scal[PCG_STATUS] = 3.0; a.scal[PCG_STOP] = 1.0; return; }      // (every lane that gets here stores the same two values)
+    for (int j = 0; j < d; ++j) {                           // L -> L^-1, column by column: rows below and columns right of j still hold L
+        M[j + j * d] = 1.0 / M[j + j * d];
+        for (int i = j + 1; i < d; ++i) { double s = 0;
+            for (int k = j; k < i; ++k) s += M[i + k * d] * M[k + j * d];
+            M[i + j * d] = -s / M[i + i * d]; }
+    }
+    for (int j = 0; j < d; ++j)                             // lower triangle of L^-T L^-1: entry (i, j) needs rows >= i of columns i and j, not yet overwritten
+        for (int i = j; i < d; ++i) { double s = 0;
+            for (int k = i; k < d; ++k) s += M[k + i * d] * M[k + j * d];
+            M[i + j * d] = s; }
+    for (int j = 0; j < d; ++j) for (int i = j + 1; i < d; ++i) M[j + i * d] = M[i + j * d];
+}
+
+// y = 0, r = b, z = Minv r, p = z; partials of r'z and b'b
+__global__ __launch_bounds__(TPB) void pcg_init_kernel(PcgArgs a) {
+    __shared__ double red[16];
+    if (pcg_stopped(a.scal, red)) return;
+    double srz = 0, sbb = 0;
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) {
+        const double re = a.b[e];
+        const double ze = pcg_prec(a, e, re, [&](int64_t k) { return a.b[k]; });
+        a.y[e] = 0.0; a.r_new[e] = re; a.z[e] = ze; a.p[e] = ze;
+        srz += re * ze; sbb += re * re;
+    }
+    srz = block_sum(srz, red); sbb = block_sum(sbb, red);
+    if (threadIdx.x == 0) { a.pb[blockIdx.x] = srz; a.pc[blockIdx.x] = sbb; }
+}
+// one workgroup: the scalars of the start -- r'z, r'r = b'b; b == 0 (or rtol >= 1) is converged before the first iteration
+__global__ __launch_bounds__(TPB) void pcg_start_kernel(PcgArgs a) {
+    __shared__ double red[16];
+    if (pcg_stopped(a.scal, red)) return;
+    const double rz = pcg_total(a.pb, a.npart, red), bb = pcg_total(a.pc, a.npart, red);
+    if (threadIdx.x == 0) { a.scal[PCG_RZ0] = rz; a.scal[PCG_RR] = bb; a.scal[PCG_BB] = bb; if (bb <= a.rtol2 * bb) a.scal[PCG_STOP] = 1.0; }
+}
+
+__global__ __launch_bounds__(TPB) void pcg_dot_kernel(PcgArgs a) {
+    __shared__ double red[16];
+    if (pcg_stopped(a.scal, red)) return;
+    double s = 0;
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) s += a.p[e] * a.q[e];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) a.pa[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(TPB) void pcg_step_kernel(PcgArgs a) {
+    __shared__ double red[16];
+    if (pcg_stopped(a.scal, red)) return;
+    const double pq = pcg_total(a.pa, a.npart, red), rz = a.scal[PCG_RZ0 + a.parity], alpha = rz / pq;
+    if (!(pq > 0.0) || !isfinite(alpha)) {                  // the same decision in every workgroup: nobody writes a vector
+        if (blockIdx.x == 0 && threadIdx.x == 0) { a.scal[PCG_PQ] = pq; a.scal[PCG_ITER] += 1.0; a.scal[PCG_STATUS] = 2.0; a.scal[PCG_STOP] = 1.0; }
+        return;
+    }
+    const double* __restrict__ ro = a.r_old; const double* __restrict__ q = a.q;
+    double srz = 0, srr = 0;
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) {
+        const double re = fma(-alpha, q[e], ro[e]);         // (the block's other entries of r_new are formed the same way below: r is never read while it is written)
+        const double ze = pcg_prec(a, e, re, [&](int64_t k) { return fma(-alpha, q[k], ro[k]); });
+        a.y[e] = fma(alpha, a.p[e], a.y[e]); a.r_new[e] = re; a.z[e] = ze;
+        srz += re * ze; srr += re * re;
+    }
+    srz = block_sum(srz, red); srr = block_sum(srr, red);
+    if (threadIdx.x == 0) { a.pb[blockIdx.x] = srz; a.pc[blockIdx.x] = srr; if (blockIdx.x == 0) a.scal[PCG_PQ] = pq; }
+}
+
+__global__ __launch_bounds__(TPB) void pcg_dir_kernel(PcgArgs a) {
+    __shared__ double red[16];
+    if (pcg_stopped(a.scal, red)) return;
+    const double rz = pcg_total(a.pb, a.npart, red), rr = pcg_total(a.pc, a.npart, red);
+    const double beta = rz / a.scal[PCG_RZ0 + a.parity], bb = a.scal[PCG_BB];
+    const bool done = rr <= a.rtol2 * bb, bad = !done && !(isfinite(beta) && isfinite(rr));
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        a.scal[PCG_RZ0 + (a.parity ^ 1)] = rz; a.scal[PCG_RR] = rr; a.scal[PCG_ITER] += 1.0;
+        if (done) a.scal[PCG_STOP] = 1.0;
+        if (bad) { a.scal[PCG_STATUS] = 2.0; a.scal[PCG_STOP] = 1.0; }
+    }
+    if (bad) return;
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) a.p[e] = fma(beta, a.p[e], a.z[e]);
+}
+
+// the step: x = -y (src/iterators.jl:151, negate!)
+__global__ __launch_bounds__(TPB) void pcg_finish_kernel(const double* __restrict__ y, double* __restrict__ x, int64_t n) {
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < n; e += (int64_t)gridDim.x * TPB) x[e] = -y[e];
+}
+
+// ================================================================================================
+// host side
+// ================================================================================================
+namespace {
+int pcg_buffers(nlls_ctx* c, bool jacobi) {
+    PcgState& S = c->pcg; const int64_t ndof = c->info.ndof;
+    auto need = [&](DevBuf<double>& buf, size_t n, const char* what) -> int {
+        if (buf.n >= n && buf.p) return NLLS_OK;
+        const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(c, e, what); }
+        return NLLS_OK; };
+    S.ndof = ndof; S.pw = (ndof + TPB - 1) / TPB;
+    int rc = need(S.vec, (size_t)(6 * ndof), "nlls_solve_pcg: the vectors"); if (rc != NLLS_OK) return rc;
+    rc = need(S.part, (size_t)(3 * S.pw), "nlls_solve_pcg: the partial sums"); if (rc != NLLS_OK) return rc;
+    rc = need(S.scal, (size_t)PCG_NSCAL, "nlls_solve_pcg: the scalars"); if (rc != NLLS_OK) return rc;
+    if (jacobi) rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "nlls_solve_pcg: the preconditioner's blocks");
+    return rc;
+}
+// launches of one enqueue_hess_apply of one vector (what it just enqueued: the block launches of the non-empty groups, the gather's)
+int64_t product_launches(const nlls_ctx* c) {
+    int64_t n = 0; for (const Group& G : c->groups) n += G.ncost > 0;
+    return n + (c->info.ndof > 0) + (c->app.nitems > 0) + (c->app.nbig > 0);
+}
+}  // namespace
+
+int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats) {
+    const int64_t ndof = c->info.ndof; const bool jacobi = precond == NLLS_PCG_PRECOND_BLOCK_JACOBI;
+    double st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    auto report = [&]() { c->pcg_iters = (int64_t)st[0]; c->pcg_status = (int64_t)st[1]; c->pcg_rounds = (int64_t)st[4]; if (stats) for (int k = 0; k < 8; ++k) stats[k] = st[k]; };
+    int rc = pcg_buffers(c, jacobi); if (rc != NLLS_OK) return rc;
+    PcgState& S = c->pcg; const double lambda = c->lambda;
+    double* const y = S.vec.p; double* const r[2] = {y + ndof, y + 2 * ndof}; double* const z = y + 3 * ndof; double* const p = y + 4 * ndof; double* const q = y + 5 * ndof;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(S.pw, std::max<int64_t>(c->pcg_grid_max, 1)));
+    const bool timed = c->phase_on && c->phase_ev.size() >= 16;
+    if (timed) (void)hipEventRecord(c->phase_ev[14], c->stream);
+    int64_t launches = 0;
+    HIPCHK(hipMemsetAsync(S.scal.p, 0, sizeof(double) * PCG_NSCAL, c->stream));
+    if (jacobi) { rc = enqueue_hess_block_diag(c, NLLS_VARS_CURRENT, lambda, S.Minv.p); if (rc != NLLS_OK) return rc; launches += product_launches(c); }
+    PcgArgs a{};
+    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = rtol * rtol;
+    a.b = c->b.p; a.Minv = S.Minv.p; a.y = y; a.r_old = r[1]; a.r_new = r[0]; a.z = z; a.p = p; a.q = q;
+    a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.scal = S.scal.p;
+    if (jacobi) {       // (the index of the products exists: enqueue_hess_block_diag built it)
+        a.erow = c->app.erow_vec.p; a.start = c->app.start_vec.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;
+        hipLaunchKernelGGL(pcg_factor_kernel, dim3((unsigned)((a.nblocks + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a, S.Minv.p); ++launches;
+    }
+    hipLaunchKernelGGL(pcg_init_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
+    hipLaunchKernelGGL(pcg_start_kernel, dim3(1), dim3(TPB), 0, c->stream, a); launches += 2;
+    HIPCHK(hipGetLastError());
+    const int64_t round = std::max<int64_t>(c->pcg_round, 1);
+    double* const h = c->h_scalars + 48;      // the pinned mirror's slots [48, 56): nothing else uses them (a copy into pageable memory is staged, and the round waits for it)
+    for (int k = 0; k < PCG_NSCAL; ++k) h[k] = 0.0;
+    int64_t it = 0, rounds = 0;
+    for (;;) {
+        const int64_t n = std::min<int64_t>(round, (int64_t)maxiters - it);
+        for (int64_t k = 0; k < n; ++k, ++it) {
+            a.parity = (int)(it & 1); a.r_old = r[it & 1]; a.r_new = r[(it + 1) & 1];
+            rc = enqueue_hess_apply(c, NLLS_VARS_CURRENT, lambda, 1, p, q); if (rc != NLLS_OK) return rc;
+            hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
+            hipLaunchKernelGGL(pcg_step_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
+            hipLaunchKernelGGL(pcg_dir_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
+            launches += product_launches(c) + 3;
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream)); ++rounds;
+        if (h[PCG_STOP] != 0.0 || it >= maxiters) break;
+    }
+    const int status = h[PCG_STOP] != 0.0 ? (int)h[PCG_STATUS] : 1;
+    st[0] = h[PCG_ITER]; st[1] = status; st[2] = std::sqrt(h[PCG_BB]); st[3] = std::sqrt(h[PCG_RR]); st[4] = (double)rounds; st[5] = (double)launches;
+    if (status >= 2) {
+        if (timed) { (void)hipEventRecord(c->phase_ev[15], c->stream); c->pcg_pending = true; }
+        report();
+        c->err = status == 3 ? "nlls_solve_pcg: a diagonal block of H + lambda I is not positive definite (status 3)"
+                             : "nlls_solve_pcg: p'(H + lambda I)p is not positive, or a scalar of the recurrence is not finite (status 2, iteration " + std::to_string((int64_t)h[PCG_ITER]) + ")";
+        return NLLS_ERR_NOT_SPD;
+    }
+    step_replaced(c);
+    hipLaunchKernelGGL(pcg_finish_kernel, dim3(grid), dim3(TPB), 0, c->stream, y, c->x.p, ndof); ++launches;
+    HIPCHK(hipGetLastError());
+    if (timed) { (void)hipEventRecord(c->phase_ev[15], c->stream); c->pcg_pending = true; }
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    st[4] = (double)(rounds + 1); st[5] = (double)launches;
+    report();
+    return NLLS_OK;
+}
+
+}  // namespace nlls

@@ -19,6 +19,24 @@ def _timed(data, field, fn):
     return out
 
 
+class PCG:
+    """NLLSOptions(linearsolver=PCG(...)): the iterators' linear solves by conjugate gradients on the device's matrix-free operator (nlls_solve_pcg) where they
+    factor by default -- no reduced system, and with `maxiters` small a truncated-Newton step.  precond: "blockjacobi" (the diagonal blocks of H + lambda I) or "none";
+    maxiters None: 4 ndof.  A breakdown (the system is not positive definite) is what a bad pivot is to the direct solve: Levenberg-Marquardt damps more."""
+
+    def __init__(self, rtol=1e-8, maxiters=None, precond="blockjacobi"):
+        assert precond in ("blockjacobi", "none") and rtol >= 0 and (maxiters is None or maxiters >= 1)
+        self.rtol, self.maxiters, self.precond = float(rtol), maxiters, precond
+
+
+def _solve(ls, options):
+    """solve!(linsystem): the direct solve, or options.linearsolver's"""
+    pcg = getattr(options, "linearsolver", None)
+    if pcg is None:
+        return ls.solve()
+    return ls.solve_pcg(pcg.precond, pcg.maxiters, pcg.rtol)
+
+
 class NewtonData:                                   # src/iterators.jl:11-13
     def reset(self):
         return self
@@ -29,7 +47,7 @@ class NewtonData:                                   # src/iterators.jl:11-13
 
 def iterate_newton(nd, data, problem, options):     # src/iterators.jl:15-27
     ls = data.linsystem
-    _timed(data, "timesolver", ls.solve)
+    _timed(data, "timesolver", lambda: _solve(ls, options))
     data.linearsolvers += 1
     ls.update(VARS_NEXT, VARS_CURRENT)
     cost_ = _timed(data, "timecost", lambda: ls.cost(VARS_NEXT))
@@ -60,7 +78,7 @@ def iterate_levmar(lmd, data, problem, options):    # src/iterators.jl:139-172
         # LDLFactorizations would throw here; this path counts it as a rejected trial -- more damping, solve again -- and records it in
         # data.singulartrials (NLLSResult.singulartrials), in both branches.  No cost was computed for such a trial.
         singular = None
-        if hasattr(ls, "lm_trial"):                   # :149-157 in one library call (same kernels, one synchronisation)
+        if hasattr(ls, "lm_trial") and getattr(options, "linearsolver", None) is None:   # :149-157 in one library call (same kernels, one synchronisation)
             try:
                 cost_ = _timed(data, "timesolver", lambda: ls.lm_trial(lmd.lambda_ - lastlambda))
                 data.costcomputations += 1
@@ -74,7 +92,7 @@ def iterate_levmar(lmd, data, problem, options):    # src/iterators.jl:139-172
             ls.uniformscaling(lmd.lambda_ - lastlambda)  # :149
             lastlambda = lmd.lambda_
             try:
-                _timed(data, "timesolver", ls.solve)     # :152
+                _timed(data, "timesolver", lambda: _solve(ls, options))     # :152 (options.linearsolver: conjugate gradients)
             except NllsError as e:
                 if e.code != ERR_NOT_SPD:
                     raise
@@ -136,7 +154,7 @@ def iterate_dogleg(dd, data, problem, options):     # src/iterators.jl:47-115
     beta = 0.0
     x = None
     if alpha < dd.trustradius:
-        ls.solve()
+        _solve(ls, options)
         x = np.array(ls.x)
         beta = float(np.linalg.norm(x))
         data.linearsolvers += 1

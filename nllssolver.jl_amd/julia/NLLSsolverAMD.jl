@@ -176,6 +176,14 @@ end
 function jactvec!(y::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, group::Integer, u::AbstractVecOrMat{Float64}, which::Integer=0)
     check(ls.ctx, ccall((:nlls_jact_apply, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, group, apply_nvec(u), u, y)); return y
 end
+# solve!(linsystem) + negate! (src/iterators.jl:149-157) by block-Jacobi conjugate gradients on those products, on the device: (H + λ I) y = b from 0 with the damping
+# uniformscaling! has accumulated, x = -y left as the system's step (ls.x).  precond 1: the diagonal blocks, 0: none.  Returns (iterations, status) -- status 0 converged,
+# 1 maxiters; a breakdown (the system or a diagonal block is not positive definite) errors like a bad pivot of solve! and leaves the step as it was.
+function solvepcg!(ls::MultiVariateLSgpu; precond::Integer=1, maxiters::Integer=4 * max(ls.ndof, 1), rtol::Real=1e-8)
+    stats = zeros(8)
+    check(ls.ctx, ccall((:nlls_solve_pcg, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}), ls.ctx, precond, maxiters, rtol, ls.x, stats))
+    return Int(stats[1]), Int(stats[2])
+end
 # optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
 # re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
 function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)

@@ -86,6 +86,11 @@ class MultiVariateLSgpu:
         self._x = None
         self.ctx.solve()
 
+    def solve_pcg(self, precond="blockjacobi", maxiters=None, rtol=1e-8, want_x=False):
+        """solve by conjugate gradients on the matrix-free operator, where solve() factors (nlls_solve_pcg) -> (x or None, stats); maxiters None: 4 ndof"""
+        self._x = None
+        return self.ctx.solve_pcg(precond, maxiters, rtol, want_x)
+
     def lm_trial(self, dlambda):
         """uniformscaling!(H, dlambda); solve!; update!(next, current); cost(next)   src/iterators.jl:149-157, fused
         into one call of the library (one synchronisation).  Returns the trial cost."""

@@ -24,11 +24,15 @@ newton, levenbergmarquardt, dogleg, gradientdescent = NLLSIterator
 
 class NLLSOptions:                                   # src/structs.jl:22-35
     def __init__(self, maxiters=100, reldcost=1e-15, absdcost=1e-15, dstep=1e-15, maxfails=3, maxtime=30.0,
-                 iterator=levenbergmarquardt, callback=None, iteratordata=None):
+                 iterator=levenbergmarquardt, callback=None, iteratordata=None, linearsolver=None):
         self.reldcost, self.absdcost, self.dstep = reldcost, absdcost, dstep
         self.maxfails, self.maxiters = maxfails, maxiters
         self.maxtime = int(round(maxtime * 1e9))     # nanoseconds
         self.iterator, self.callback, self.iteratordata = NLLSIterator(iterator), callback, iteratordata
+        # None: the direct solve of the linear system.  An iterators.PCG: conjugate gradients on the device's matrix-free operator (nlls_solve_pcg) in its place --
+        # Levenberg-Marquardt then runs its unfused trial (damp, solve, update, cost) in the Python loop
+        assert linearsolver is None or isinstance(linearsolver, It.PCG)
+        self.linearsolver = linearsolver
 
 
 class NLLSResult:                                    # src/structs.jl:37-79
@@ -113,7 +117,7 @@ class OuterLoop:
         ls = data.linsystem
         can = (iterate is It.iterate_levmar and callback is nullcallback and hasattr(ls, "ctx")
                and (not getattr(ls, "sharded", False) or getattr(ls, "native_collectives", False))     # (sharded: the collectives are inside the library)
-               and hasattr(ls.ctx, "lm_iterations"))
+               and hasattr(ls.ctx, "lm_iterations") and getattr(options, "linearsolver", None) is None)
         self.native = can if native is None else (bool(native) and can)
         self._state = None
 
@@ -339,6 +343,13 @@ class Solver:
         """the diagonal blocks of H + lam I at problem.variables: one (dof, dof) array per unfixed variable, in the order of the gradient"""
         self._start()
         return self.ls.hess_block_diag(lam, VARS_CURRENT)
+
+    def solve_pcg(self, lam=0.0, precond="blockjacobi", maxiters=None, rtol=1e-8):
+        """The step x = -(H + lam I)^-1 g at problem.variables by conjugate gradients on the device (nlls_solve_pcg): linearises, damps by lam, solves.
+        -> (x, stats) as MultiVariateLSgpu.solve_pcg; a breakdown raises NllsError (ERR_NOT_SPD)."""
+        self._start()
+        self.ls.costgradhess(want_cost=False); self.ls.uniformscaling(lam)
+        return self.ls.solve_pcg(precond, maxiters, rtol, want_x=True)
 
     def operator(self, lam=0.0):
         """H + lam I at problem.variables (as they are NOW) as a linear operator: .shape, .matvec(v), .diag_blocks() -- what a Krylov method of the caller's needs"""

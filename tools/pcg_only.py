@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""What nlls_solve_pcg costs: the damped system (H + lambda I) y = b of a bench.py workload, built as bench.py builds it, solved by conjugate gradients on the device.
+The median wall time of --repeats (at least 7) calls behind one untimed call, the iterations, the time per iteration, the time of the call's launches alone (the event
+pair of NLLS_OPT_PHASE_EVENTS, nlls_get_phase_times [14]) -- and beside it, measured in the same run on the same context: the host-composed block-Jacobi CG through
+Solver.operator at the same tolerance (tools/apply_only.py --cg; --no-host-cg skips it), the launches of one nlls_hess_apply at nvec 1, and nlls_solve.  One JSON line.
+
+  --workload   ba_100x10k | ba_1kx100k (default) | ba_so3_500x50k | ba_20x2k (with --no-schur: 6120 unknowns whose direct path is the dense LDL') |
+               ba_10x200_fixed (558 unknowns in two cost groups, 32 variables fixed: the problem the tests solve)
+  --lam        lambda as a fraction of max |diag H| (default 1e-3)      --rtol (default 1e-10)      --precond blockjacobi | none
+  --round      NLLS_OPT_PCG_ROUND; a comma list measures each value (the table of notes/r18.md)"""
+import argparse, json, os, sys, time
+import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import nllssolver_jl_amd as N
+from nllssolver_jl_amd import synthetic, _capi
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--workload", default="ba_1kx100k", choices=("ba_100x10k", "ba_1kx100k", "ba_so3_500x50k", "ba_20x2k", "ba_10x200_fixed"))
+ap.add_argument("--lam", type=float, default=1e-3); ap.add_argument("--rtol", type=float, default=1e-10); ap.add_argument("--precond", default="blockjacobi", choices=("blockjacobi", "none"))
+ap.add_argument("--round", default=""); ap.add_argument("--repeats", type=int, default=7); ap.add_argument("--maxiters", type=int, default=0)
+ap.add_argument("--no-schur", action="store_true"); ap.add_argument("--no-host-cg", action="store_true"); ap.add_argument("--host-cg-maxiter", type=int, default=2000)
+a = ap.parse_args()
+a.repeats = max(a.repeats, 7); unfixed = None
+if a.workload == "ba_10x200_fixed":
+    from nllssolver_jl_amd import kinds as K
+    p = synthetic.perturb_ba_problem(synthetic.create_ba_problem(10, 200, 0.3, seed=3, robust=N.HuberKernel(0.002)), 1e-3, 1e-3)
+    (g,) = p.costs.values(); vi, da = g.arrays(); rng = np.random.default_rng(4); pick = rng.choice(vi.shape[0], 150, replace=False)
+    p.addcosts(K.RES_BA_AFFINE, vi[pick], da[pick] + 0.01 * rng.standard_normal((150, 2)), N.GemanMcclureKernel(0.01))
+    unfixed = np.ones(p.nvariables, bool); unfixed[[0, 1]] = False; unfixed[10:40] = False
+elif a.workload == "ba_so3_500x50k":
+    p = synthetic.perturb_ba_problem(synthetic.create_so3_ba_problem(500, 50000, 0.02, seed=1, adaptive=True), 1e-3, 1e-3)
+else:
+    ncam, npts, prop = {"ba_100x10k": (100, 10000, 0.1), "ba_1kx100k": (1000, 100000, 0.01), "ba_20x2k": (20, 2000, 0.3)}[a.workload]
+    p = synthetic.perturb_ba_problem(synthetic.create_ba_problem(ncam, npts, prop, seed=1, robust=N.HuberKernel(0.01), outlier_frac=0.05, outlier_sigma=0.05), 1e-3, 1e-3)
+
+with N.Solver(p, unfixed, flags=_capi.FLAG_NO_SCHUR if a.no_schur else 0) as s:
+    op = s.operator(0.0); ctx = s.ls.ctx; ndof = int(ctx.info.ndof)
+    ctx.sweep_gradhess(); lam = a.lam * ctx.max_abs_diag(); ctx.damp(lam); maxiters = a.maxiters or None
+    out = {"workload": a.workload, "no_schur": a.no_schur, "ndof": ndof, "blocks": int(ctx.info.ncost), "solve_mode": int(ctx.info.solve_mode), "lambda": lam, "rtol": a.rtol,
+           "precond": a.precond, "repeats": a.repeats}
+
+    def measure():
+        ms, dev = [], []
+        for _ in range(a.repeats + 1):                # (the wall time without the event pairs: each is two marker packets on the queue per product)
+            t0 = time.perf_counter(); _, st = ctx.solve_pcg(a.precond, maxiters, a.rtol); ms.append(1e3 * (time.perf_counter() - t0))
+        ctx.set_option(_capi.OPT_PHASE_EVENTS, 1)
+        for _ in range(a.repeats + 1):
+            ctx.solve_pcg(a.precond, maxiters, a.rtol); dev.append(ctx.phase_times()["pcg_us"])
+        ctx.set_option(_capi.OPT_PHASE_EVENTS, 0)
+        wall = float(np.median(ms[1:]))
+        return {"iterations": st["iterations"], "status": st["status"], "rounds": st["rounds"], "launches": st["launches"], "relative_residual": st["rnorm"] / max(st["bnorm"], 1e-300),
+                "wall_ms": wall, "wall_ms_all": [round(m, 3) for m in ms[1:]], "launches_ms": 1e-3 * float(np.median(dev[1:])), "us_per_iteration": 1e3 * wall / max(st["iterations"], 1)}
+
+    if a.round:
+        out["rounds"] = {}
+        for r in (int(v) for v in a.round.split(",")):
+            ctx.set_option(_capi.OPT_PCG_ROUND, r); out["rounds"][str(r)] = measure()
+    else:
+        out["pcg"] = measure()
+        xp = ctx.solve_pcg(a.precond, maxiters, a.rtol, want_x=True)[0]
+        ts = []
+        for _ in range(a.repeats + 1):
+            t0 = time.perf_counter(); xs = ctx.solve(want_x=True); ts.append(1e3 * (time.perf_counter() - t0))
+        out["nlls_solve_ms"] = float(np.median(ts[1:])); out["distance_to_nlls_solve"] = float(np.max(np.abs(xp - xs)) / np.max(np.abs(xs)))
+        v = np.random.default_rng(1).standard_normal(ndof); us = []; ctx.set_option(_capi.OPT_PHASE_EVENTS, 1)
+        for _ in range(a.repeats + 1):
+            ctx.hess_apply(v, lam); us.append(ctx.phase_times()["apply_us"])
+        ctx.set_option(_capi.OPT_PHASE_EVENTS, 0)
+        out["hess_apply_launches_us"] = float(np.median(us[1:]))
+        if not a.no_host_cg and a.precond == "blockjacobi":      # the composition of tools/apply_only.py --cg: one synchronous product per iteration, the vector work in numpy
+            b = ctx.get_grad(); op.lam = lam
+            bs = ctx.block_sizes(); bo = np.concatenate(([0], np.cumsum(bs)))[:-1]; D = op.diag_blocks()
+            inv = {int(d): (np.nonzero(bs == d)[0], np.linalg.inv(np.stack([D[k] for k in np.nonzero(bs == d)[0]]))) for d in np.unique(bs)}
+            def prec(r):
+                z = np.empty_like(r)
+                for d, (idx, m) in inv.items():
+                    pos = bo[idx][:, None] + np.arange(d)[None, :]; z[pos] = np.einsum("nij,nj->ni", m, r[pos])
+                return z
+            walls = []
+            for _ in range(3):
+                x = np.zeros(ndof); r = b.copy(); z = prec(r); d = z.copy(); rz = r @ z; nb = np.linalg.norm(b); it = 0; t0 = time.perf_counter()
+                while it < a.host_cg_maxiter and np.linalg.norm(r) > a.rtol * nb:
+                    q = op.matvec(d); alpha = rz / (d @ q); x += alpha * d; r -= alpha * q; z = prec(r); rz, old = r @ z, rz; d = z + (rz / old) * d; it += 1
+                walls.append(time.perf_counter() - t0)
+            out["host_cg"] = {"iterations": it, "seconds": float(np.median(walls)), "seconds_all": [round(w, 5) for w in walls], "distance_to_nlls_solve": float(np.max(np.abs(-x - xs)) / np.max(np.abs(xs)))}
+            out["pcg_over_host_cg"] = 1e-3 * out["pcg"]["wall_ms"] / out["host_cg"]["seconds"]
+print(json.dumps(out))
