@@ -408,6 +408,43 @@ int  nlls_hess_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d
 #define NLLS_PCG_PRECOND_BLOCK_JACOBI  1   /* M = the diagonal blocks of H + lambda I (nlls_hess_block_diag) */
 int  nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out);
 
+/* ---- conjugate gradients on the caller's right-hand sides; marginal covariance blocks ----------------------------------
+ * replaces: solve!(linsystem) for a right-hand side other than the gradient (src/linearsolver.jl:20-32: the reference solves with whatever the linear system's b
+ *           holds, and a caller who wants another right-hand side overwrites it), as a call that takes the right-hand sides and leaves the linear system alone.
+ * For every k < nrhs: (H + lambda I) x_k = b_k by the iteration of nlls_solve_pcg from x_k = 0.  Column k is at B + k * ndof and at X_out + k * ndof, host pointers, in
+ * the order of b and x.  H is that of nlls_hess_apply, evaluated at variable set `which` at the time of the call; lambda is the ARGUMENT, not the damping nlls_damp has
+ * accumulated.  No sign flip: X solves the system as written (with B = nlls_get_grad's vector, `which` = CURRENT, lambda = the context's damping and nrhs = 1, X_out is
+ * -x of nlls_solve_pcg byte for byte, and the column's four statistics are equal).  Needs an upload and no sweep; read only, like the products: the context's step,
+ * A.data, b, the variable sets, the damping, the validity state, a pending look-ahead sweep and the counters of the last nlls_solve_pcg are untouched.  Synchronous.
+ * Status per column, as nlls_solve_pcg: 0 ||r_k|| <= rtol ||b_k|| (a zero column: status 0, 0 iterations, x_k = 0); 1 maxiters reached; 2 p'(H + lambda I)p not > 0
+ * or a scalar not finite (a NaN in b_k ends here); 3 a diagonal block of the preconditioner has no Cholesky factor -- call-wide: every column reports 3 and 0
+ * iterations.  A column that stops leaves the others running.  NLLS_OK when every column ended 0 or 1; NLLS_ERR_NOT_SPD when any ended 2 or 3: then no byte of X_out
+ * is written and stats_out tells which column.
+ * stats_out[4 * nrhs + 4] (may be NULL): per column k at [4 k ..]: iterations, status, ||b_k||_2, ||r_k||_2 of the recurrence at exit; then, for the call: stream
+ * synchronisations, launches, product vectors (the sum over its products of the vectors each carried), batches.
+ * At most NLLS_APPLY_MAX_VEC columns iterate together, each iteration ONE product over the columns still iterating; a call with more columns runs them in batches of
+ * eight, in order.  The preconditioner is set up once per call.  The host looks at all columns' stop flags once per round of NLLS_OPT_PCG_ROUND iterations; a column
+ * found stopped pays for no further product.  Column k's bytes and its four statistics do not depend on which other columns the call carries, on their order, on
+ * nrhs, on where a batch ends or on NLLS_OPT_PCG_ROUND; two calls return identical bytes; different NLLS_OPT_PCG_GRID_MAX agree to rounding.
+ * Memory: 6 * min(nrhs, 8) * ndof doubles of vectors and nrhs * ndof for the columns, outside the hot arena, allocated on demand.
+ * NLLS_ERR_INVALID_ARG -- nothing enqueued, no output byte written -- for a null context, B or X_out, `which` outside 0 .. 2, nrhs < 1, a precond other than the two,
+ * maxiters < 1, rtol not finite or < 0, lambda not finite; NLLS_ERR_NOT_READY before an upload; NLLS_ERR_UNSUPPORTED where nlls_hess_apply is (a dynamic-size group,
+ * nlls_set_shard with nranks > 1); ndof == 0: NLLS_OK, X_out untouched, stats_out zeros. */
+int  nlls_solve_pcg_rhs(nlls_ctx* ctx, int32_t which, double lambda, int32_t precond, int32_t maxiters, double rtol, int32_t nrhs, const double* B, double* X_out, double* stats_out);
+/* replaces: nothing -- the reference has NO covariance routine.  The nearest thing in it is the vestigial `formarginalization` flag of makesymmvls
+ *           (src/linearsystem.jl:91-118), which only orders the variables for a marginalisation it never performs; Ceres, g2o and GTSAM answer "how certain is this
+ *           variable" with marginal covariance blocks, and this is that call.
+ * The joint covariance block of the listed variables: with m = the sum of their dof, cov_out is m x m, column-major -- the rows and columns of (H + lambda I)^-1 that
+ * belong to the listed variables, in the listed order, in the tangent space of their update() as x is.  varindices: nsel 1-based variable indices of the upload (as
+ * nlls_optimize_singles takes them), in any order.  The entry is the inverse of H: scaling by a noise level is the caller's.  Column j is the solve for unit vector j
+ * -- written on the device, nothing of length ndof crosses the bus, and only the m selected rows of a finished column are kept -- through the batched solver of
+ * nlls_solve_pcg_rhs: eight columns at a time, the preconditioner once; so symmetry holds to the solve's accuracy and is not enforced, and every byte rule above holds.
+ * A singular H at lambda = 0 (a problem whose gauge is free) shows as status 1, 2 or 3: fix the gauge with fixed variables, or pass a lambda > 0.
+ * stats_out[4 * m + 4] (may be NULL) as above, a column per unknown.  NLLS_OK when every column ended 0 or 1 (check the statuses: a column that ended on maxiters is
+ * not a covariance); NLLS_ERR_NOT_SPD on any 2 or 3, cov_out untouched.  Refusals as above, and NLLS_ERR_INVALID_ARG for nsel < 1, a null varindices, an index outside
+ * 1 .. nvar, an index listed twice, a listed variable that is fixed (it has no row in H). */
+int  nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel, const int64_t* varindices, int32_t precond, int32_t maxiters, double rtol, double* cov_out, double* stats_out);
+
 /* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
  * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
  *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.

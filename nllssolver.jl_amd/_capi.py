@@ -40,7 +40,7 @@ nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_own
 nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
 nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
 nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim
-nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg""".split()
+nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg nlls_solve_pcg_rhs nlls_marginal_cov""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -140,6 +140,7 @@ def lib():
         L.nlls_hess_apply.argtypes = [vp, i32, dbl, i32, vp, vp]; L.nlls_jac_apply.argtypes = [vp, i32, i32, i32, vp, vp]
         L.nlls_jact_apply.argtypes = [vp, i32, i32, i32, vp, vp]; L.nlls_hess_block_diag.argtypes = [vp, i32, dbl, vp]
         L.nlls_solve_pcg.argtypes = [vp, i32, i32, dbl, vp, vp]
+        L.nlls_solve_pcg_rhs.argtypes = [vp, i32, dbl, i32, i32, dbl, i32, vp, vp, vp]; L.nlls_marginal_cov.argtypes = [vp, i32, dbl, i64, vp, i32, i32, dbl, vp, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -203,6 +204,7 @@ class Context:
             for k in range(4):
                 arr[i].robust_params[k] = float(rp[k])
             arr[i].ncost = vi.shape[0]; arr[i].varind = vi.ctypes.data; arr[i].data = da.ctypes.data
+        self._var_kind, self._var_dim = vk, vd                   # (marginal_cov: the dof of the listed variables)
         self._kinds = [int(g["res_kind"]) for g in groups]      # (eval_jacobians / eval_gradhess: the record sizes of a group's kind)
         self._groups = []; self._ndata = [int(da.size // max(vi.shape[0], 1)) for vi, da in zip(keep[3::2], keep[4::2])]     # doubles of payload per block, per group (set_cost_data)
         self._chk(self.L.nlls_upload_structure(self.h, len(vk), _p(vk), _p(vd), _p(bi), len(groups), arr, flags))
@@ -400,6 +402,45 @@ class Context:
         self.last_pcg = dict(iterations=int(st[0]), status=int(st[1]), bnorm=float(st[2]), rnorm=float(st[3]), rounds=int(st[4]), launches=int(st[5]))
         self._chk(rc)
         return out, self.last_pcg
+
+    @staticmethod
+    def _pcg_rhs_stats(st, n):
+        cols = st[:4 * n].reshape(n, 4)
+        return dict(iterations=cols[:, 0].astype(np.int64), status=cols[:, 1].astype(np.int64), bnorm=cols[:, 2].copy(), rnorm=cols[:, 3].copy(),
+                    synchronisations=int(st[4 * n]), launches=int(st[4 * n + 1]), product_vectors=int(st[4 * n + 2]), batches=int(st[4 * n + 3]))
+
+    def solve_pcg_rhs(self, B, lam=0.0, which=VARS_CURRENT, precond=PCG_PRECOND_BLOCK_JACOBI, maxiters=None, rtol=1e-8):
+        """nlls_solve_pcg_rhs: (H + lam I) x_k = b_k by conjugate gradients on the device for right-hand sides of the caller's, H evaluated at variable set `which`; no
+        sign flip, nothing of the context changes.  B (ndof,) -> X (ndof,); (nrhs, ndof) -> (nrhs, ndof): eight columns iterate together, the preconditioner is set up
+        once.  maxiters: 4 ndof when None.  -> (X, stats) with stats = dict of arrays iterations, status (0 converged, 1 maxiters), bnorm, rnorm -- one entry per
+        column -- and the call's synchronisations, launches, product_vectors, batches.  A breakdown of any column (status 2, 3) raises NllsError with code ERR_NOT_SPD;
+        last_pcg_rhs holds the stats."""
+        pc = PCG_PRECONDS[precond] if isinstance(precond, str) or precond is None else int(precond)
+        mi = max(4 * int(self.info.ndof), 1) if maxiters is None else int(maxiters)
+        a = np.ascontiguousarray(B, np.float64); one = a.ndim == 1
+        a = a.reshape(1, -1) if one else a
+        assert a.ndim == 2 and a.shape[1] == self.info.ndof, f"expected right-hand sides of length {self.info.ndof}"
+        n = a.shape[0]; out = np.zeros_like(a); st = np.zeros(4 * n + 4)
+        rc = self.L.nlls_solve_pcg_rhs(self.h, int(which), float(lam), pc, mi, float(rtol), n, _p(a), _p(out), _p(st))
+        self.last_pcg_rhs = self._pcg_rhs_stats(st, n)
+        self._chk(rc)
+        return (out[0] if one else out), self.last_pcg_rhs
+
+    def marginal_cov(self, varindices, lam=0.0, which=VARS_CURRENT, precond=PCG_PRECOND_BLOCK_JACOBI, maxiters=None, rtol=1e-8):
+        """nlls_marginal_cov: the rows and columns of (H + lam I)^-1 that belong to the listed variables (1-BASED indices of the upload, any order, unfixed, distinct), in
+        the listed order: (m, m) with m the sum of their dof, in the tangent space of their update().  Column j is the solve for unit vector j through solve_pcg_rhs's
+        solver; symmetry is not enforced.  -> (cov, stats) with stats as solve_pcg_rhs, a column per unknown; a breakdown raises NllsError (ERR_NOT_SPD), last_pcg_rhs
+        holds the stats.  A column with status 1 has NOT converged: check stats["status"]."""
+        pc = PCG_PRECONDS[precond] if isinstance(precond, str) or precond is None else int(precond)
+        mi = max(4 * int(self.info.ndof), 1) if maxiters is None else int(maxiters)
+        vi = np.ascontiguousarray(varindices, np.int64).ravel()
+        vk, vd = getattr(self, "_var_kind", ()), getattr(self, "_var_dim", ())
+        m = int(sum(max(self.L.nlls_var_dof(int(vk[v - 1]), int(vd[v - 1])), 0) for v in vi[(vi >= 1) & (vi <= len(vd))]))      # (a list the library refuses: it says why)
+        cov = np.zeros((m, m)); st = np.zeros(4 * m + 4)
+        rc = self.L.nlls_marginal_cov(self.h, int(which), float(lam), int(vi.size), _p(vi), pc, mi, float(rtol), _p(cov), _p(st))
+        self.last_pcg_rhs = self._pcg_rhs_stats(st, m)
+        self._chk(rc)
+        return np.ascontiguousarray(cov.T), self.last_pcg_rhs
 
     def lm_trial(self, dlambda, to=VARS_NEXT, frm=VARS_CURRENT):
         """damp + solve + retract + cost sweep in one call / one synchronisation; returns the trial cost."""

@@ -535,6 +535,42 @@ int nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol
     return pcg_solve(ctx, precond, maxiters, rtol, x_out, stats_out);
     NLLS_API_END(ctx)
 }
+// Conjugate gradients on right-hand sides of the caller's, and on unit columns for a block of the inverse (nlls_pcg.hip, pcg_solve_cols).  Read only, like the products:
+// no event of nlls_state.hpp, nothing of the last nlls_solve_pcg's counters.  Everything is refused here, before anything is enqueued or written.
+static int pcg_cols_check(nlls_ctx* ctx, const char* name, int32_t which, double lambda, int32_t precond, int32_t maxiters, double rtol) {
+    if (!valid_set(which) || !std::isfinite(lambda) || (precond != NLLS_PCG_PRECOND_NONE && precond != NLLS_PCG_PRECOND_BLOCK_JACOBI) || maxiters < 1 || !std::isfinite(rtol) || rtol < 0)
+        return fail(ctx, NLLS_ERR_INVALID_ARG, std::string(name) + ": bad variable set, lambda, preconditioner, maxiters or rtol");
+    return NLLS_OK;
+}
+int nlls_solve_pcg_rhs(nlls_ctx* ctx, int32_t which, double lambda, int32_t precond, int32_t maxiters, double rtol, int32_t nrhs, const double* B, double* X_out, double* stats_out) { NLLS_API_BEGIN
+    if (!ctx || !B || !X_out) return NLLS_ERR_INVALID_ARG;
+    if (nrhs < 1) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg_rhs: nrhs < 1");
+    TRY(pcg_cols_check(ctx, "nlls_solve_pcg_rhs", which, lambda, precond, maxiters, rtol));
+    NEED_READY();
+    TRY(apply_check(ctx, "nlls_solve_pcg_rhs", -1, false));
+    if (ctx->info.ndof == 0) { if (stats_out) for (int64_t k = 0; k < 4 * (int64_t)nrhs + 4; ++k) stats_out[k] = 0.0; return NLLS_OK; }
+    return pcg_solve_cols(ctx, "nlls_solve_pcg_rhs", which, lambda, precond, maxiters, rtol, nrhs, B, nullptr, X_out, stats_out);
+    NLLS_API_END(ctx)
+}
+int nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel, const int64_t* varindices, int32_t precond, int32_t maxiters, double rtol, double* cov_out, double* stats_out) { NLLS_API_BEGIN
+    if (!ctx || !varindices || !cov_out) return NLLS_ERR_INVALID_ARG;
+    if (nsel < 1) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_marginal_cov: nsel < 1");
+    TRY(pcg_cols_check(ctx, "nlls_marginal_cov", which, lambda, precond, maxiters, rtol));
+    NEED_READY();
+    TRY(apply_check(ctx, "nlls_marginal_cov", -1, false));
+    std::vector<int64_t> rows; std::vector<uint8_t> seen((size_t)ctx->info.nvar, 0);      // the unknowns of the listed variables, in the listed order
+    for (int64_t i = 0; i < nsel; ++i) { const int64_t v = varindices[i] - 1;
+        if (v < 0 || v >= ctx->info.nvar) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_marginal_cov: a variable index outside 1 .. nvar");
+        if (seen[(size_t)v]) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_marginal_cov: a variable is listed twice");
+        seen[(size_t)v] = 1;
+        const uint64_t blk = ctx->blockindices[(size_t)v];
+        if (blk == 0) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_marginal_cov: a listed variable is fixed: it has no row in H");
+        for (int32_t k = 0; k < ctx->blocksizes[(size_t)(blk - 1)]; ++k) rows.push_back(ctx->boffsets[(size_t)(blk - 1)] + k); }
+    const int64_t m = (int64_t)rows.size();
+    if (m == 0) { if (stats_out) for (int k = 0; k < 4; ++k) stats_out[k] = 0.0; return NLLS_OK; }
+    return pcg_solve_cols(ctx, "nlls_marginal_cov", which, lambda, precond, maxiters, rtol, m, nullptr, rows.data(), cov_out, stats_out);
+    NLLS_API_END(ctx)
+}
 // One Levenberg-Marquardt trial in one call and one synchronisation (src/iterators.jl:149-157): uniformscaling!(H, dlambda),
 // solve!, negate!, update!(to, from, x), cost(to).  Same kernels, same order as the separate entry points.
 int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, double* cost_out) { NLLS_API_BEGIN

@@ -233,7 +233,23 @@ struct ApplyIndex {
 // Minv: the inverses of the diagonal blocks of H + lambda I (sum of dof_b^2, the layout of nlls_hess_block_diag); part: three rows of per-workgroup partial sums
 // (p'q | r'z | r'r); scal: the scalar block PCG_* below.
 enum { PCG_RZ0 = 0, PCG_RZ1 = 1, PCG_PQ = 2, PCG_RR = 3, PCG_BB = 4, PCG_ITER = 5, PCG_STOP = 6, PCG_STATUS = 7, PCG_NSCAL = 8 };   // r'z by parity of the iteration, p'q, r'r, b'b, iterations, stop, status
-struct PcgState { DevBuf<double> vec, Minv, part, scal; int64_t ndof = 0, pw = 0; };      // pw: doubles of one row of part
+// nlls_solve_pcg_rhs / nlls_marginal_cov: up to NLLS_APPLY_MAX_VEC columns iterate together.  vec: y | r0 | r1 | z | p | q, each `cap` columns of ndof (the columns
+// of p and of q are contiguous: one enqueue_hess_apply takes them all); part: three rows of partials per column; scal: a scalar block per column and one more, the
+// factorisation's, that every column's block starts from; io: the caller's B, overwritten column by column with the results (nlls_marginal_cov: one batch of unit
+// columns); rows, cov: the selected unknowns and the m x m block of nlls_marginal_cov.  h_scal: the pinned mirror of the batch's scalar blocks, one copy per round.
+struct PinnedBuf {
+    double* p = nullptr; size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    PinnedBuf(PinnedBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    ~PinnedBuf() { release(); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+    hipError_t alloc(size_t count) { release(); n = count; return hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(double), hipHostMallocDefault); }
+};
+struct PcgRhsState { DevBuf<double> vec, Minv, part, scal, io, cov; DevBuf<int64_t> rows; PinnedBuf h_scal; int64_t pw = 0; };
+struct PcgState { DevBuf<double> vec, Minv, part, scal; int64_t ndof = 0, pw = 0; PcgRhsState rhs; };      // pw: doubles of one row of part
 
 }  // namespace nlls
 

@@ -77,6 +77,11 @@ int64_t apply_diag_len(const nlls_ctx* c);     // doubles of nlls_hess_block_dia
 // block-Jacobi conjugate gradients on (H + c->lambda I) y = b with the products above (nlls_pcg.hip): the caller has checked the arguments and holds b; synchronises once per
 // round of c->pcg_round iterations.  NLLS_OK: c->x = -y (and x_out, host, if not null); NLLS_ERR_NOT_SPD: a breakdown, c->x and x_out untouched.  stats: nlls_solve_pcg's (may be null)
 int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats);
+// the same iteration on ncols right-hand sides of the caller's, NLLS_APPLY_MAX_VEC at a time, H at set `which`, lambda the argument; reads only.  B: ncols columns of ndof
+// (host), out the solutions; B null: column j is the unit vector of unknown h_rows[j] (0-based, host), out the ncols x ncols block of the inverse (nlls_marginal_cov).
+// NLLS_ERR_NOT_SPD: a column broke down, out untouched.  stats: 4 * ncols + 4 doubles (may be null).  `name`: the entry point, for the error text
+int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int precond, int maxiters, double rtol, int64_t ncols, const double* B, const int64_t* h_rows,
+                   double* out, double* stats);
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);

@@ -13,6 +13,10 @@
 // iterations) cost their launches and the product, and change nothing: the result does not depend on the round length.  The flag is written where the writer's own
 // launch cannot be harmed by it: on a breakdown every workgroup takes the same decision and writes nothing; on convergence only p, which nobody reads again, may stay
 // partly updated.  Built like nlls_apply.o, WITHOUT -fno-honor-nans: a NaN in b or in a product reaches the breakdown tests below.
+// Columns (nlls_solve_pcg_rhs, nlls_marginal_cov): the vector kernels take a column per blockIdx.y -- its own vectors (slot blockIdx.y of each of the six arrays), its
+// own scalar block and rows of partials (those of the column PcgArgs::cols names for the slot: a column keeps them when its vectors move to another slot).
+// pcg_column() turns the launch's arguments into the column's and the bodies below are those of one column: nlls_solve_pcg launches them with one.  A workgroup
+// belongs to one column, so the stop flag is one value per workgroup and a stopped column's workgroups leave at entry while the others iterate.
 #include <algorithm>
 #include <cmath>
 
@@ -26,7 +30,15 @@ struct PcgArgs {
     double rtol2;
     const double* b; const double* Minv; double* y; const double* r_old; double* r_new; double* z; double* p; const double* q;
     double* pa; double* pb; double* pc; double* scal;       // partials of p'q, r'z, r'r
+    int64_t pstride; uint32_t cols;                         // doubles between two columns' rows of partials; four bits per slot: the column (of the batch) whose scalars and partials it uses
 };
+// the arguments of this workgroup's column (everything here is uniform over the workgroup)
+NLLS_DEV PcgArgs pcg_column(PcgArgs a) {
+    const int64_t v = (int64_t)blockIdx.y * a.ndof, cb = (a.cols >> (4 * blockIdx.y)) & 15u;
+    a.b += v; a.y += v; a.r_old += v; a.r_new += v; a.z += v; a.p += v; a.q += v;
+    a.pa += cb * a.pstride; a.pb += cb * a.pstride; a.pc += cb * a.pstride; a.scal += cb * PCG_NSCAL;
+    return a;
+}
 
 // the stop flag as ONE value for the whole workgroup (a barrier follows in every kernel: lanes that read it at different times must not part ways)
 NLLS_DEV bool pcg_stopped(const double* scal, double* red) {
@@ -87,8 +99,9 @@ __global__ __launch_bounds__(TPB) void pcg_factor_kernel(PcgArgs a, double* __re
 }
 
 // y = 0, r = b, z = Minv r, p = z; partials of r'z and b'b
-__global__ __launch_bounds__(TPB) void pcg_init_kernel(PcgArgs a) {
+__global__ __launch_bounds__(TPB) void pcg_init_kernel(PcgArgs a0) {
     __shared__ double red[16];
+    const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     double srz = 0, sbb = 0;
     for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) {
@@ -101,15 +114,17 @@ __global__ __launch_bounds__(TPB) void pcg_init_kernel(PcgArgs a) {
     if (threadIdx.x == 0) { a.pb[blockIdx.x] = srz; a.pc[blockIdx.x] = sbb; }
 }
 // one workgroup: the scalars of the start -- r'z, r'r = b'b; b == 0 (or rtol >= 1) is converged before the first iteration
-__global__ __launch_bounds__(TPB) void pcg_start_kernel(PcgArgs a) {
+__global__ __launch_bounds__(TPB) void pcg_start_kernel(PcgArgs a0) {
     __shared__ double red[16];
+    const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     const double rz = pcg_total(a.pb, a.npart, red), bb = pcg_total(a.pc, a.npart, red);
     if (threadIdx.x == 0) { a.scal[PCG_RZ0] = rz; a.scal[PCG_RR] = bb; a.scal[PCG_BB] = bb; if (bb <= a.rtol2 * bb) a.scal[PCG_STOP] = 1.0; }
 }
 
-__global__ __launch_bounds__(TPB) void pcg_dot_kernel(PcgArgs a) {
+__global__ __launch_bounds__(TPB) void pcg_dot_kernel(PcgArgs a0) {
     __shared__ double red[16];
+    const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     double s = 0;
     for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) s += a.p[e] * a.q[e];
@@ -117,8 +132,9 @@ __global__ __launch_bounds__(TPB) void pcg_dot_kernel(PcgArgs a) {
     if (threadIdx.x == 0) a.pa[blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(TPB) void pcg_step_kernel(PcgArgs a) {
+__global__ __launch_bounds__(TPB) void pcg_step_kernel(PcgArgs a0) {
     __shared__ double red[16];
+    const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     const double pq = pcg_total(a.pa, a.npart, red), rz = a.scal[PCG_RZ0 + a.parity], alpha = rz / pq;
     if (!(pq > 0.0) || !isfinite(alpha)) {                  // the same decision in every workgroup: nobody writes a vector
@@ -137,8 +153,9 @@ __global__ __launch_bounds__(TPB) void pcg_step_kernel(PcgArgs a) {
     if (threadIdx.x == 0) { a.pb[blockIdx.x] = srz; a.pc[blockIdx.x] = srr; if (blockIdx.x == 0) a.scal[PCG_PQ] = pq; }
 }
 
-__global__ __launch_bounds__(TPB) void pcg_dir_kernel(PcgArgs a) {
+__global__ __launch_bounds__(TPB) void pcg_dir_kernel(PcgArgs a0) {
     __shared__ double red[16];
+    const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     const double rz = pcg_total(a.pb, a.npart, red), rr = pcg_total(a.pc, a.npart, red);
     const double beta = rz / a.scal[PCG_RZ0 + a.parity], bb = a.scal[PCG_BB];
@@ -155,6 +172,24 @@ __global__ __launch_bounds__(TPB) void pcg_dir_kernel(PcgArgs a) {
 // the step: x = -y (src/iterators.jl:151, negate!)
 __global__ __launch_bounds__(TPB) void pcg_finish_kernel(const double* __restrict__ y, double* __restrict__ x, int64_t n) {
     for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < n; e += (int64_t)gridDim.x * TPB) x[e] = -y[e];
+}
+
+// ---- columns: what nlls_solve_pcg_rhs and nlls_marginal_cov add around the kernels above ------------------------------------------------------------------------
+// every column's scalar block starts as the factorisation's: zeros, or status 3 and the stop flag -- a block without a factor stops every column of the call
+__global__ __launch_bounds__(TPB) void pcg_cols_begin_kernel(const double* __restrict__ fscal, double* __restrict__ scal, int ncol) {
+    if ((int)threadIdx.x < ncol * PCG_NSCAL) scal[threadIdx.x] = fscal[threadIdx.x % PCG_NSCAL];
+}
+// unit right-hand sides written where they are used: column blockIdx.y is e_(rows[blockIdx.y])
+__global__ __launch_bounds__(TPB) void pcg_unit_kernel(double* __restrict__ io, int64_t ndof, const int64_t* __restrict__ rows) {
+    double* __restrict__ colp = io + (int64_t)blockIdx.y * ndof; const int64_t one = rows[blockIdx.y];
+    for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < ndof; e += (int64_t)gridDim.x * TPB) colp[e] = e == one ? 1.0 : 0.0;
+}
+// the selected rows of the batch's finished columns, one lane per (row, column): cov points at the batch's first column of the m x m block
+__global__ __launch_bounds__(TPB) void pcg_pick_kernel(const double* __restrict__ io, int64_t ndof, const int64_t* __restrict__ rows, int64_t m, int ncol, double* __restrict__ cov) {
+    const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (t >= m * ncol) return;
+    const int64_t s = t / m, i = t - s * m;
+    cov[s * m + i] = io[s * ndof + rows[i]];
 }
 
 // ================================================================================================
@@ -241,6 +276,116 @@ int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out
     HIPCHK(hipStreamSynchronize(c->stream));
     st[4] = (double)(rounds + 1); st[5] = (double)launches;
     report();
+    return NLLS_OK;
+}
+
+// nlls_solve_pcg_rhs (B: ncols columns of ndof, host) and nlls_marginal_cov (B null: column j is the unit vector of unknown h_rows[j], ncols = m, out is m x m).
+// The caller has checked the arguments.  stats: 4 * ncols + 4 doubles (may be null)
+int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int precond, int maxiters, double rtol, int64_t ncols, const double* B, const int64_t* h_rows,
+                   double* out, double* stats) {
+    constexpr int MAXC = NLLS_APPLY_MAX_VEC;
+    const int64_t ndof = c->info.ndof; const bool jacobi = precond == NLLS_PCG_PRECOND_BLOCK_JACOBI; const std::string nm(name);
+    PcgRhsState& S = c->pcg.rhs; const int cap = (int)std::min<int64_t>(ncols, MAXC);
+    auto need = [&](auto& buf, size_t n, const char* what) -> int {
+        if (buf.n >= n && buf.p) return NLLS_OK;
+        const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(c, e, (nm + ": " + what).c_str()); }
+        return NLLS_OK; };
+    S.pw = (ndof + TPB - 1) / TPB;
+    int rc = need(S.vec, (size_t)(6 * cap * ndof), "the vectors"); if (rc != NLLS_OK) return rc;
+    rc = need(S.part, (size_t)(3 * S.pw * cap), "the partial sums"); if (rc != NLLS_OK) return rc;
+    rc = need(S.scal, (size_t)((MAXC + 1) * PCG_NSCAL), "the scalars"); if (rc != NLLS_OK) return rc;
+    rc = need(S.h_scal, (size_t)(MAXC * PCG_NSCAL), "the pinned mirror of the scalars"); if (rc != NLLS_OK) return rc;
+    rc = need(S.io, (size_t)((B ? ncols : (int64_t)cap) * ndof), "the columns"); if (rc != NLLS_OK) return rc;
+    if (jacobi) { rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "the preconditioner's blocks"); if (rc != NLLS_OK) return rc; }
+    if (!B) { rc = need(S.rows, (size_t)ncols, "the selected unknowns"); if (rc != NLLS_OK) return rc;
+              rc = need(S.cov, (size_t)(ncols * ncols), "the covariance block"); if (rc != NLLS_OK) return rc; }
+    const int64_t vs = (int64_t)cap * ndof;      // doubles of one of the six arrays
+    double* const y = S.vec.p; double* const r[2] = {y + vs, y + 2 * vs}; double* const z = y + 3 * vs; double* const p = y + 4 * vs; double* const q = y + 5 * vs;
+    double* const fscal = S.scal.p + MAXC * PCG_NSCAL; double* const h = S.h_scal.p;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(S.pw, std::max<int64_t>(c->pcg_grid_max, 1)));
+    std::vector<double> st((size_t)(4 * ncols + 4), 0.0);
+    int64_t launches = 0, syncs = 0, products = 0, batches = 0; bool bad = false; int64_t bad_col = -1; int bad_status = 0;
+    if (!B) HIPCHK(hipMemcpyAsync(S.rows.p, h_rows, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(fscal, 0, sizeof(double) * PCG_NSCAL, c->stream));
+    PcgArgs a{};
+    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = rtol * rtol;
+    a.Minv = S.Minv.p; a.y = y; a.r_old = r[1]; a.r_new = r[0]; a.z = z; a.p = p; a.q = q;
+    a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.pstride = 3 * S.pw; a.scal = S.scal.p; a.b = S.io.p;
+    if (jacobi) {       // the preconditioner: once per call, whatever the number of batches
+        rc = enqueue_hess_block_diag(c, which, lambda, S.Minv.p); if (rc != NLLS_OK) return rc; launches += product_launches(c);
+        a.erow = c->app.erow_vec.p; a.start = c->app.start_vec.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;
+        PcgArgs f = a; f.scal = fscal;
+        hipLaunchKernelGGL(pcg_factor_kernel, dim3((unsigned)((a.nblocks + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, f, S.Minv.p); ++launches;
+    }
+    const int64_t round = std::max<int64_t>(c->pcg_round, 1);
+    for (int64_t j0 = 0; j0 < ncols && bad_status != 3; j0 += MAXC, ++batches) {
+        const int nb = (int)std::min<int64_t>(MAXC, ncols - j0);
+        double* const bio = B ? S.io.p + j0 * ndof : S.io.p;      // the batch's right-hand sides, then its results
+        if (B) HIPCHK(hipMemcpyAsync(bio, B + j0 * ndof, sizeof(double) * (size_t)(nb * ndof), hipMemcpyHostToDevice, c->stream));
+        else { hipLaunchKernelGGL(pcg_unit_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p + j0); ++launches; }
+        hipLaunchKernelGGL(pcg_cols_begin_kernel, dim3(1), dim3(TPB), 0, c->stream, fscal, S.scal.p, nb);
+        a.b = bio; a.cols = 0x76543210u; a.parity = 0; a.r_old = r[1]; a.r_new = r[0];
+        hipLaunchKernelGGL(pcg_init_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, a);
+        hipLaunchKernelGGL(pcg_start_kernel, dim3(1, nb), dim3(TPB), 0, c->stream, a); launches += 3;
+        HIPCHK(hipGetLastError());
+        int slot_col[MAXC]; for (int s = 0; s < MAXC; ++s) slot_col[s] = s;
+        int active = nb; int64_t it = 0;
+        auto stopped = [&](int s) { return h[slot_col[s] * PCG_NSCAL + PCG_STOP] != 0.0; };
+        auto finalize = [&](int s) -> hipError_t {          // the column's four statistics; its y to its place among the results
+            const int col = slot_col[s]; const double* hc = h + col * PCG_NSCAL; double* sc = st.data() + 4 * (j0 + col);
+            const int status = hc[PCG_STOP] != 0.0 ? (int)hc[PCG_STATUS] : 1;
+            sc[0] = hc[PCG_ITER]; sc[1] = status; sc[2] = std::sqrt(hc[PCG_BB]); sc[3] = std::sqrt(hc[PCG_RR]);
+            if (status >= 2) { if (!bad) { bad = true; bad_col = j0 + col; bad_status = status; } if (status == 3) bad_status = 3; return hipSuccess; }
+            return hipMemcpyAsync(bio + (int64_t)col * ndof, y + (int64_t)s * ndof, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToDevice, c->stream); };
+        for (;;) {      // a look, then a round: the first look finds the columns that need no iteration (b == 0; no factor), so that they pay for no product either
+            HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * (size_t)(nb * PCG_NSCAL), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream)); ++syncs;       // one look per round for all columns
+            if (it >= maxiters) { for (int s = 0; s < active; ++s) HIPCHK(finalize(s)); active = 0; break; }
+            // a stopped column pays for no further product: the columns still iterating stay contiguous -- the last one's y, current r and p move into the freed slot
+            // (z, q and the other r are written before they are read in the next iteration)
+            int s = 0;
+            while (s < active) {
+                if (!stopped(s)) { ++s; continue; }
+                HIPCHK(finalize(s)); int last = --active;
+                while (last > s && stopped(last)) { HIPCHK(finalize(last)); last = --active; }
+                if (last > s) {
+                    double* const mv[3] = {y, r[it & 1], p};
+                    for (double* v : mv) HIPCHK(hipMemcpyAsync(v + (int64_t)s * ndof, v + (int64_t)last * ndof, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToDevice, c->stream));
+                    slot_col[s] = slot_col[last]; ++s;
+                }
+            }
+            if (active == 0) break;
+            const int64_t n = std::min<int64_t>(round, (int64_t)maxiters - it);
+            a.cols = 0; for (int s = 0; s < active; ++s) a.cols |= (uint32_t)slot_col[s] << (4 * s);
+            for (int64_t k = 0; k < n; ++k, ++it) {
+                a.parity = (int)(it & 1); a.r_old = r[it & 1]; a.r_new = r[(it + 1) & 1];
+                rc = enqueue_hess_apply(c, which, lambda, active, p, q); if (rc != NLLS_OK) return rc;
+                hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
+                hipLaunchKernelGGL(pcg_step_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
+                hipLaunchKernelGGL(pcg_dir_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
+                launches += product_launches(c) + 3; products += active;
+            }
+            HIPCHK(hipGetLastError());
+        }
+        if (!B && !bad) { hipLaunchKernelGGL(pcg_pick_kernel, dim3((unsigned)((ncols * nb + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p, ncols, nb, S.cov.p + j0 * ncols); ++launches;
+                          HIPCHK(hipGetLastError()); }
+    }
+    if (bad_status == 3) for (int64_t k = 0; k < ncols; ++k) { st[4 * k] = 0.0; st[4 * k + 1] = 3.0; st[4 * k + 2] = 0.0; st[4 * k + 3] = 0.0; }   // call-wide: no column started
+    if (!bad) {
+        // (a batch at a time, as the right-hand sides came: one copy of 16 columns of ba_1kx100k into pageable memory took longer than two of 8, notes/r19.md)
+        if (B) { for (int64_t j0 = 0; j0 < ncols; j0 += MAXC) { const int64_t nb = std::min<int64_t>(MAXC, ncols - j0);
+                     HIPCHK(hipMemcpyAsync(out + j0 * ndof, S.io.p + j0 * ndof, sizeof(double) * (size_t)(nb * ndof), hipMemcpyDeviceToHost, c->stream)); } }
+        else HIPCHK(hipMemcpyAsync(out, S.cov.p, sizeof(double) * (size_t)(ncols * ncols), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream)); ++syncs;
+    }
+    double* const tail = st.data() + 4 * ncols;
+    tail[0] = (double)syncs; tail[1] = (double)launches; tail[2] = (double)products; tail[3] = (double)batches;
+    if (stats) std::copy(st.begin(), st.end(), stats);
+    if (bad) {
+        c->err = bad_status == 3 ? nm + ": a diagonal block of H + lambda I is not positive definite (status 3)"
+                                 : nm + ": p'(H + lambda I)p is not positive, or a scalar of the recurrence is not finite (status 2, column " + std::to_string(bad_col) + ")";
+        return NLLS_ERR_NOT_SPD;
+    }
     return NLLS_OK;
 }
 

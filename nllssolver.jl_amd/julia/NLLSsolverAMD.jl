@@ -184,6 +184,24 @@ function solvepcg!(ls::MultiVariateLSgpu; precond::Integer=1, maxiters::Integer=
     check(ls.ctx, ccall((:nlls_solve_pcg, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}), ls.ctx, precond, maxiters, rtol, ls.x, stats))
     return Int(stats[1]), Int(stats[2])
 end
+# solve!(linsystem) for right-hand sides other than the gradient (src/linearsolver.jl:20-32), without touching the linear system: (H + λ I) X[:, k] = B[:, k] by the same
+# iteration, eight columns at a time, H evaluated at device variable set `which`; no sign flip.  B, X: ndof, or ndof x nrhs.  Returns (iterations, status) per column.
+function solvepcgrhs!(X::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, B::AbstractVecOrMat{Float64}; λ::Real=0.0, which::Integer=0, precond::Integer=1,
+                      maxiters::Integer=4 * max(ls.ndof, 1), rtol::Real=1e-8)
+    nrhs = size(B, 2); stats = zeros(4 * nrhs + 4)
+    check(ls.ctx, ccall((:nlls_solve_pcg_rhs, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                        ls.ctx, which, λ, precond, maxiters, rtol, nrhs, B, X, stats))
+    return Int.(stats[1:4:4 * nrhs]), Int.(stats[2:4:4 * nrhs])
+end
+# The joint marginal covariance block of the variables `varindices` (1-based, unfixed, distinct): their rows and columns of (H + λ I)^-1, m x m with m = sum(dofs), the
+# dof of each listed variable -- the reference has no covariance routine (the formarginalization flag of makesymmvls, src/linearsystem.jl:91-118, only orders variables).
+function marginalcov(ls::MultiVariateLSgpu, varindices::Vector{Int64}, dofs::Vector{<:Integer}; λ::Real=0.0, which::Integer=0, precond::Integer=1,
+                     maxiters::Integer=4 * max(ls.ndof, 1), rtol::Real=1e-10)
+    m = sum(dofs); cov = zeros(m, m); stats = zeros(4 * m + 4)
+    check(ls.ctx, ccall((:nlls_marginal_cov, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int64, Ptr{Int64}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}),
+                        ls.ctx, which, λ, length(varindices), varindices, precond, maxiters, rtol, cov, stats))
+    return cov, Int.(stats[2:4:4 * m])
+end
 # optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
 # re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
 function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)

@@ -91,6 +91,15 @@ class MultiVariateLSgpu:
         self._x = None
         return self.ctx.solve_pcg(precond, maxiters, rtol, want_x)
 
+    def solve_pcg_rhs(self, B, lam=0.0, which=VARS_CURRENT, precond="blockjacobi", maxiters=None, rtol=1e-8):
+        """(hessian + lam I) x_k = b_k for right-hand sides of the caller's, eight at a time on the device (nlls_solve_pcg_rhs) -> (X, stats); the linear system is
+        left as it is   src/linearsolver.jl:20-32"""
+        return self.ctx.solve_pcg_rhs(B, lam, which, precond, maxiters, rtol)
+
+    def marginal_cov(self, varindices, lam=0.0, which=VARS_CURRENT, precond="blockjacobi", maxiters=None, rtol=1e-8):
+        """the block of (hessian + lam I)^-1 of the listed variables (1-based, unfixed; nlls_marginal_cov) -> (cov, stats); the reference has no such routine"""
+        return self.ctx.marginal_cov(varindices, lam, which, precond, maxiters, rtol)
+
     def lm_trial(self, dlambda):
         """uniformscaling!(H, dlambda); solve!; update!(next, current); cost(next)   src/iterators.jl:149-157, fused
         into one call of the library (one synchronisation).  Returns the trial cost."""

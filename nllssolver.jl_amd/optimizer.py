@@ -351,6 +351,26 @@ class Solver:
         self.ls.costgradhess(want_cost=False); self.ls.uniformscaling(lam)
         return self.ls.solve_pcg(precond, maxiters, rtol, want_x=True)
 
+    def solve_rhs(self, B, lam=0.0, precond="blockjacobi", maxiters=None, rtol=1e-8):
+        """(H + lam I) x_k = b_k at problem.variables for right-hand sides of the caller's -- B (ndof,) or (nrhs, ndof), in the order of the gradient -- by conjugate
+        gradients on the device, eight columns at a time (nlls_solve_pcg_rhs).  No linearisation is needed and none is changed.  -> (X, stats) as
+        Context.solve_pcg_rhs; a breakdown raises NllsError (ERR_NOT_SPD)."""
+        self._start()
+        return self.ls.solve_pcg_rhs(B, lam, VARS_CURRENT, precond, maxiters, rtol)
+
+    def covariance(self, variables, lam=0.0, precond="blockjacobi", maxiters=None, rtol=1e-10, strict=True):
+        """The joint marginal covariance block of `variables` (the indices addvariable returned: 1-based, unfixed, distinct, any order) at problem.variables: the rows
+        and columns of (H + lam I)^-1 that belong to them, in the listed order, in the tangent space of their update() (nlls_marginal_cov).  It is the inverse of H:
+        scaling by a noise level is the caller's.  A problem whose gauge is free has a singular H: fix variables, or pass a lam.  strict: a column that ended on
+        maxiters raises ValueError -- a covariance from an unconverged solve is silently wrong; strict=False returns it, stats["status"] tells.  -> (cov, stats)"""
+        self._start()
+        cov, st = self.ls.marginal_cov(np.asarray(variables, np.int64).ravel(), lam, VARS_CURRENT, precond, maxiters, rtol)
+        if strict and np.any(np.asarray(st["status"]) != 0):
+            bad = np.flatnonzero(np.asarray(st["status"]) != 0)
+            raise ValueError(f"covariance: {bad.size} of {len(st['status'])} columns did not converge to rtol {rtol} within maxiters (first: column {int(bad[0])}, "
+                             f"||r|| / ||b|| = {float(st['rnorm'][bad[0]]) / max(float(st['bnorm'][bad[0]]), 1e-300):.3e}): raise maxiters, pass a lam, or strict=False")
+        return cov, st
+
     def operator(self, lam=0.0):
         """H + lam I at problem.variables (as they are NOW) as a linear operator: .shape, .matvec(v), .diag_blocks() -- what a Krylov method of the caller's needs"""
         self._start()
@@ -400,6 +420,10 @@ class HessianOperator:
 
     def diag_blocks(self):
         return self.ls.hess_block_diag(self.lam, VARS_CURRENT)
+
+    def solve(self, B, precond="blockjacobi", maxiters=None, rtol=1e-8):
+        """(H + lam I)^-1 B by conjugate gradients on the device (nlls_solve_pcg_rhs): B (ndof,) or (nrhs, ndof) -> (X, stats)"""
+        return self.ls.solve_pcg_rhs(B, self.lam, VARS_CURRENT, precond, maxiters, rtol)
 
 
 SINGLES_MAX_DOF = 12          # NLLS_SINGLES_MAX_DOF (include/nlls_amd.h)
@@ -541,6 +565,14 @@ def hessvec(problem, v, lam=0.0, unfixed=None, device=0):
         return ls.hess_apply(v, lam, VARS_CURRENT)
     finally:
         ls.close()
+
+
+def marginalcovariance(problem, variables, lam=0.0, unfixed=None, device=0, precond="blockjacobi", maxiters=None, rtol=1e-10, strict=True):
+    """The joint marginal covariance block of `variables` at problem.variables: the rows and columns of (H + lam I)^-1 of the linear system of `unfixed` that belong
+    to them, as Solver.covariance returns it (nlls_marginal_cov; the reference has no covariance routine).  -> (cov, stats).  A linear system is built and dropped
+    per call: N.Solver keeps one."""
+    with Solver(problem, unfixed, 0, device) as s:
+        return s.covariance(variables, lam, precond, maxiters, rtol, strict)
 
 
 def jacvec(problem, group, v, unfixed=None, device=0):

@@ -7,7 +7,10 @@ Solver.operator at the same tolerance (tools/apply_only.py --cg; --no-host-cg sk
   --workload   ba_100x10k | ba_1kx100k (default) | ba_so3_500x50k | ba_20x2k (with --no-schur: 6120 unknowns whose direct path is the dense LDL') |
                ba_10x200_fixed (558 unknowns in two cost groups, 32 variables fixed: the problem the tests solve)
   --lam        lambda as a fraction of max |diag H| (default 1e-3)      --rtol (default 1e-10)      --precond blockjacobi | none
-  --round      NLLS_OPT_PCG_ROUND; a comma list measures each value (the table of notes/r18.md)"""
+  --round      NLLS_OPT_PCG_ROUND; a comma list measures each value (the table of notes/r18.md)
+  --rhs K      nlls_solve_pcg_rhs instead: the first K unit columns (K = 6: those of the first unfixed camera) in ONE call, against K single-column calls and against K
+               host-composed solves, same context, same run: wall time, product vectors, synchronisations
+  --cov N      nlls_marginal_cov instead: the joint covariance block of the first N unfixed cameras, against the same columns through --rhs's one call"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--workload", default="ba_1kx100k", choices=("ba_100x10k", "ba_1kx100k", "ba_so3_500x50k", "ba_20x2k", "ba_10x200_fixed"))
 ap.add_argument("--lam", type=float, default=1e-3); ap.add_argument("--rtol", type=float, default=1e-10); ap.add_argument("--precond", default="blockjacobi", choices=("blockjacobi", "none"))
 ap.add_argument("--round", default=""); ap.add_argument("--repeats", type=int, default=7); ap.add_argument("--maxiters", type=int, default=0)
+ap.add_argument("--rhs", type=int, default=0); ap.add_argument("--cov", type=int, default=0)
 ap.add_argument("--no-schur", action="store_true"); ap.add_argument("--no-host-cg", action="store_true"); ap.add_argument("--host-cg-maxiter", type=int, default=2000)
 a = ap.parse_args()
 a.repeats = max(a.repeats, 7); unfixed = None
@@ -51,7 +55,59 @@ with N.Solver(p, unfixed, flags=_capi.FLAG_NO_SCHUR if a.no_schur else 0) as s:
         return {"iterations": st["iterations"], "status": st["status"], "rounds": st["rounds"], "launches": st["launches"], "relative_residual": st["rnorm"] / max(st["bnorm"], 1e-300),
                 "wall_ms": wall, "wall_ms_all": [round(m, 3) for m in ms[1:]], "launches_ms": 1e-3 * float(np.median(dev[1:])), "us_per_iteration": 1e3 * wall / max(st["iterations"], 1)}
 
-    if a.round:
+    def host_cg_solver():
+        """the composition of tools/apply_only.py --cg: one synchronous product per iteration, the vector work in numpy -> solve(b) = (x, iterations)"""
+        op.lam = lam
+        bs = ctx.block_sizes(); bo = np.concatenate(([0], np.cumsum(bs)))[:-1]; D = op.diag_blocks()
+        inv = {int(d): (np.nonzero(bs == d)[0], np.linalg.inv(np.stack([D[k] for k in np.nonzero(bs == d)[0]]))) for d in np.unique(bs)}
+        def prec(r):
+            z = np.empty_like(r)
+            for d, (idx, m) in inv.items():
+                pos = bo[idx][:, None] + np.arange(d)[None, :]; z[pos] = np.einsum("nij,nj->ni", m, r[pos])
+            return z
+        def solve(b):
+            x = np.zeros(ndof); r = b.copy(); z = prec(r); d = z.copy(); rz = r @ z; nb = np.linalg.norm(b); it = 0
+            while it < a.host_cg_maxiter and np.linalg.norm(r) > a.rtol * nb:
+                q = op.matvec(d); alpha = rz / (d @ q); x += alpha * d; r -= alpha * q; z = prec(r); rz, old = r @ z, rz; d = z + (rz / old) * d; it += 1
+            return x, it
+        return solve
+
+    def median_ms(f):
+        ms = []
+        for _ in range(a.repeats + 1):
+            t0 = time.perf_counter(); res = f(); ms.append(1e3 * (time.perf_counter() - t0))
+        return float(np.median(ms[1:])), [round(m, 3) for m in ms[1:]], res
+
+    def call_stats(st):
+        return {"iterations": st["iterations"].tolist(), "status": st["status"].tolist(), "synchronisations": st["synchronisations"], "launches": st["launches"],
+                "product_vectors": st["product_vectors"], "batches": st["batches"]}
+
+    if a.rhs:
+        B = np.zeros((a.rhs, ndof)); B[np.arange(a.rhs), np.arange(a.rhs)] = 1.0
+        one, one_all, (X, st) = median_ms(lambda: ctx.solve_pcg_rhs(B, lam, _capi.VARS_CURRENT, a.precond, maxiters, a.rtol))
+        def singles():
+            sts = [ctx.solve_pcg_rhs(B[k], lam, _capi.VARS_CURRENT, a.precond, maxiters, a.rtol) for k in range(a.rhs)]
+            return np.stack([x for x, _ in sts]), [t for _, t in sts]
+        sep, sep_all, (Xs, sts) = median_ms(singles)
+        out["rhs"] = {"columns": a.rhs, "one_call": dict(call_stats(st), wall_ms=one, wall_ms_all=one_all),
+                      "single_column_calls": {"wall_ms": sep, "wall_ms_all": sep_all, "synchronisations": sum(t["synchronisations"] for t in sts), "launches": sum(t["launches"] for t in sts),
+                                              "product_vectors": sum(t["product_vectors"] for t in sts)},
+                      "same_bytes": bool(X.tobytes() == Xs.tobytes()), "one_call_over_single_column_calls": one / sep}
+        if not a.no_host_cg and a.precond == "blockjacobi":
+            solve = host_cg_solver(); walls = []
+            for _ in range(3):
+                t0 = time.perf_counter(); hs = [solve(B[k]) for k in range(a.rhs)]; walls.append(time.perf_counter() - t0)
+            out["rhs"]["host_cg"] = {"iterations": [it for _, it in hs], "seconds": float(np.median(walls)), "seconds_all": [round(w, 5) for w in walls],
+                                     "distance": float(max(np.max(np.abs(hs[k][0] - X[k])) / np.max(np.abs(X[k])) for k in range(a.rhs)))}
+            out["rhs"]["one_call_over_host_cg"] = 1e-3 * one / out["rhs"]["host_cg"]["seconds"]
+    elif a.cov:
+        cams = (np.flatnonzero(np.asarray(s.ls.blockindices) > 0)[:a.cov] + 1).astype(np.int64)          # (the cameras are the first variables of these workloads)
+        wall, wall_all, (cov, st) = median_ms(lambda: ctx.marginal_cov(cams, lam, _capi.VARS_CURRENT, a.precond, maxiters, a.rtol))
+        m = cov.shape[0]; E = np.zeros((m, ndof)); E[np.arange(m), np.arange(m)] = 1.0
+        rhs, rhs_all, (X, sx) = median_ms(lambda: ctx.solve_pcg_rhs(E, lam, _capi.VARS_CURRENT, a.precond, maxiters, a.rtol))
+        out["cov"] = dict(call_stats(st), variables=cams.tolist(), m=m, wall_ms=wall, wall_ms_all=wall_all, asymmetry=float(np.max(np.abs(cov - cov.T)) / np.max(np.abs(cov))),
+                          min_diagonal=float(np.min(np.diag(cov))), same_columns_through_rhs_ms=rhs, same_bytes=bool(cov.tobytes() == np.ascontiguousarray(X[:, :m].T).tobytes()))
+    elif a.round:
         out["rounds"] = {}
         for r in (int(v) for v in a.round.split(",")):
             ctx.set_option(_capi.OPT_PCG_ROUND, r); out["rounds"][str(r)] = measure()
@@ -67,21 +123,10 @@ with N.Solver(p, unfixed, flags=_capi.FLAG_NO_SCHUR if a.no_schur else 0) as s:
             ctx.hess_apply(v, lam); us.append(ctx.phase_times()["apply_us"])
         ctx.set_option(_capi.OPT_PHASE_EVENTS, 0)
         out["hess_apply_launches_us"] = float(np.median(us[1:]))
-        if not a.no_host_cg and a.precond == "blockjacobi":      # the composition of tools/apply_only.py --cg: one synchronous product per iteration, the vector work in numpy
-            b = ctx.get_grad(); op.lam = lam
-            bs = ctx.block_sizes(); bo = np.concatenate(([0], np.cumsum(bs)))[:-1]; D = op.diag_blocks()
-            inv = {int(d): (np.nonzero(bs == d)[0], np.linalg.inv(np.stack([D[k] for k in np.nonzero(bs == d)[0]]))) for d in np.unique(bs)}
-            def prec(r):
-                z = np.empty_like(r)
-                for d, (idx, m) in inv.items():
-                    pos = bo[idx][:, None] + np.arange(d)[None, :]; z[pos] = np.einsum("nij,nj->ni", m, r[pos])
-                return z
-            walls = []
+        if not a.no_host_cg and a.precond == "blockjacobi":
+            b = ctx.get_grad(); solve = host_cg_solver(); walls = []
             for _ in range(3):
-                x = np.zeros(ndof); r = b.copy(); z = prec(r); d = z.copy(); rz = r @ z; nb = np.linalg.norm(b); it = 0; t0 = time.perf_counter()
-                while it < a.host_cg_maxiter and np.linalg.norm(r) > a.rtol * nb:
-                    q = op.matvec(d); alpha = rz / (d @ q); x += alpha * d; r -= alpha * q; z = prec(r); rz, old = r @ z, rz; d = z + (rz / old) * d; it += 1
-                walls.append(time.perf_counter() - t0)
+                t0 = time.perf_counter(); x, it = solve(b); walls.append(time.perf_counter() - t0)
             out["host_cg"] = {"iterations": it, "seconds": float(np.median(walls)), "seconds_all": [round(w, 5) for w in walls], "distance_to_nlls_solve": float(np.max(np.abs(-x - xs)) / np.max(np.abs(xs)))}
             out["pcg_over_host_cg"] = 1e-3 * out["pcg"]["wall_ms"] / out["host_cg"]["seconds"]
 print(json.dumps(out))
