@@ -244,7 +244,7 @@ def test_random_visibility_has_no_band(ncam, npts, k, seed):
 
 @pytest.mark.parametrize("gw,gh,shuffle", [(16, 12, None), (24, 24, 5)])
 def test_grid_camera_graph_windowed_dense_solve(gw, gh, shuffle):
-    """A 2-D grid of cameras (every landmark seen by a 3 x 3 block): the reduced camera system is a WIDE band -- too wide for the band kernels (> 80 columns),
+    """A 2-D grid of cameras (every landmark seen by a 3 x 3 block): the reduced camera system is a WIDE band -- too wide for the band kernels (which take half bandwidths up to 126),
     far narrower than the system.  With the tile-sparse solver switched off (NLLS_FLAG_NO_TILE_SPARSE) the dense blocked LDL' works only inside the band of the
     re-ordered system and the border strip (`dense_window`); with shuffled camera labels the reverse Cuthill-McKee ordering of the upload has to find the band
     first.  Sweep, solve, retraction and LM against the oracle, whose sparse LDL' takes any structure (as the reference's does: src/linearsolver.jl:28-32)."""

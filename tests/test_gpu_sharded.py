@@ -46,8 +46,10 @@ def test_sharded_matches_unsharded(world, backend, seed):
                     q.kill()
             out, _ = p.communicate()
         outs.append(out)
+    # (a rank that dies takes its peers down inside their next collective: the message carries every failed rank's output, the one that died first among them)
+    failed = "".join(f"\n---- rank {r}: exit code {p.returncode}\n{out[-3000:]}" for r, (p, out) in enumerate(zip(procs, outs)) if p.returncode != 0)
     for r, (p, out) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, f"rank {r} failed:\n{out[-3000:]}"
+        assert p.returncode == 0, f"rank {r} failed:{failed}"
         if seeds[0] < 0: assert "singular block raised on every rank" in out
         else: assert out.count("sharded == unsharded") == len(seeds), out[-3000:]
 
