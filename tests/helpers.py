@@ -263,7 +263,7 @@ NAMED_ORDERS = dict(identity=order_identity, elim_first=order_elim_first, revers
 
 
 # ---- two-slot problems of a chosen elimination structure (the matrix-free LM trial's kernel shapes: tests/test_gpu_mf_shapes.py) -------------------
-def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3, border=0):
+def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3, border=0, windows=None):
     """A problem of ONE cost group of a two-slot kind whose eliminated set and supernodes the caller chooses.  The `nred` reduced variables come first,
     the eliminated ones after them; runs = [(ncb, nmem), ...]: nmem eliminated variables in a row that share one window of ncb consecutive reduced
     variables (one cost block each), windows of neighbouring runs different -- so a run is a supernode (cut at 128 members).
@@ -274,14 +274,22 @@ def structured_problem(kind, runs, nred, ps=1, seed=0, noise=1e-3, border=0):
         one-block members are appended to lift every reduced variable above the widest window.  border (this kind only): the last `border` of the nred
         reduced variables are no part of the band -- the windows are laid over the first nred - border -- and EVERY eliminated variable has one more
         cost block on each of them: coupled to all eliminated blocks, they are what the upload orders behind the band as border rows (15 dof at most).
+      windows (optional; `runs` is then not read): one tuple of 0-based reduced variables (of the first nred - border) per eliminated variable, in place of the
+        windows laid out from runs -- any reduced graph (a tree, an expander, several components: tests/test_gpu_tsp_shapes.py); every reduced variable must lie
+        in one.  What follows the layout -- the degree lifting, the border, meta, the perturbation -- is the same.
     Returns (problem, meta): meta["elim_blocks"] (bool per block), meta["supernodes"] (the count the grouping gives), meta["windows"] (per eliminated
     variable: its reduced neighbours, 0-based)."""
     from nllssolver_jl_amd import NLLSProblem, kinds as K
     rng = np.random.default_rng(seed)
     assert border == 0 or kind == K.RES_ROSENBROCK_B
-    windows, R, nred_all = [], len(runs), nred
+    given, nred_all = windows, nred
+    windows, R = [], (0 if given is not None else len(runs))
     nred = nred_all - border                # (the band's variables: what the windows are laid over)
-    for r, (ncb, nmem) in enumerate(runs):
+    if given is not None:
+        windows = [tuple(int(j) for j in w) for w in given]
+        assert all(len(w) >= 1 and len(set(w)) == len(w) and 0 <= min(w) and max(w) < nred for w in windows), "a window outside the reduced variables, or one listed twice"
+        assert np.unique(np.concatenate([np.asarray(w) for w in windows])).size == nred, "a reduced variable in no window"
+    for r, (ncb, nmem) in enumerate(runs if given is None else []):
         assert 1 <= ncb <= nred
         span = nred - ncb + 1; start = int(round(r * (span - 1) / max(R - 1, 1)))          # (the windows spread over the reduced variables)
         if windows and windows[-1][0] == start and len(windows[-1]) == ncb: start = (start + 1) % span

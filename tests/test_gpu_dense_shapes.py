@@ -19,7 +19,8 @@ damped solve against the oracle at RTOL_X, the long-double backward error at ETA
 and a SECOND solve on the same context at 100 lambda against the oracle's second solve (the factored diagonal slots, inv(L_JJ)' and the zero-fill flags carry over).
 
 The tile-sparse solver is offered every Schur complement of n >= 512 without NLLS_FLAG_NO_BAND; whether it takes one is a cost model's decision over a nested
-dissection, not a formula a test can restate.  The windowed cases switch it off (NLLS_FLAG_NO_TILE_SPARSE); rb_130_1023 and rb_256_1024 are uploaded at default flags
+dissection -- a formula over counts that the host-only nlls_nd_tiles gives on the CPU, restated and held to the upload in tests/test_gpu_tsp_shapes.py (`_expected`),
+not here.  The windowed cases switch it off (NLLS_FLAG_NO_TILE_SPARSE); rb_130_1023 and rb_256_1024 are uploaded at default flags
 and assert that it declines them (solve_mode 1).
 
 Where the border comes from: the generators' own border variables (rb, so3), and on ba_43_180 the upload's rule that a reduced block coupled to more than a quarter of
