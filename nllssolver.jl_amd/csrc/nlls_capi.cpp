@@ -523,11 +523,15 @@ int nlls_solve(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     return NLLS_OK;
     NLLS_API_END(ctx)
 }
+// The iteration's own arguments: the one condition of nlls_solve_pcg, nlls_solve_pcg_rhs and nlls_marginal_cov
+static bool pcg_iteration_args_ok(int32_t precond, int32_t maxiters, double rtol) {
+    return (precond == NLLS_PCG_PRECOND_NONE || precond == NLLS_PCG_PRECOND_BLOCK_JACOBI) && maxiters >= 1 && std::isfinite(rtol) && rtol >= 0;
+}
 // The same solve by conjugate gradients on the matrix-free operator (nlls_pcg.hip): (H + lambda I) y = b from y = 0, x = -y.  Everything is refused here, before anything is
 // enqueued; the solver's rounds synchronise.  On success the transition nlls_set_step makes (step_replaced, inside pcg_solve); a breakdown leaves x as it was.
 int nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out) { NLLS_API_BEGIN
     if (!ctx) return NLLS_ERR_INVALID_ARG;
-    if ((precond != NLLS_PCG_PRECOND_NONE && precond != NLLS_PCG_PRECOND_BLOCK_JACOBI) || maxiters < 1 || !std::isfinite(rtol) || rtol < 0) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg: bad preconditioner, maxiters or rtol");
+    if (!pcg_iteration_args_ok(precond, maxiters, rtol)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg: bad preconditioner, maxiters or rtol");
     NEED_GRAD_LAZY();
     TRY(apply_check(ctx, "nlls_solve_pcg", -1, false));
     if (ctx->info.ndof == 0) { ctx->pcg_iters = ctx->pcg_status = ctx->pcg_rounds = 0; if (stats_out) for (int k = 0; k < 8; ++k) stats_out[k] = 0.0; return NLLS_OK; }
@@ -538,7 +542,7 @@ int nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol
 // Conjugate gradients on right-hand sides of the caller's, and on unit columns for a block of the inverse (nlls_pcg.hip, pcg_solve_cols).  Read only, like the products:
 // no event of nlls_state.hpp, nothing of the last nlls_solve_pcg's counters.  Everything is refused here, before anything is enqueued or written.
 static int pcg_cols_check(nlls_ctx* ctx, const char* name, int32_t which, double lambda, int32_t precond, int32_t maxiters, double rtol) {
-    if (!valid_set(which) || !std::isfinite(lambda) || (precond != NLLS_PCG_PRECOND_NONE && precond != NLLS_PCG_PRECOND_BLOCK_JACOBI) || maxiters < 1 || !std::isfinite(rtol) || rtol < 0)
+    if (!valid_set(which) || !std::isfinite(lambda) || !pcg_iteration_args_ok(precond, maxiters, rtol))
         return fail(ctx, NLLS_ERR_INVALID_ARG, std::string(name) + ": bad variable set, lambda, preconditioner, maxiters or rtol");
     return NLLS_OK;
 }
@@ -549,7 +553,7 @@ int nlls_solve_pcg_rhs(nlls_ctx* ctx, int32_t which, double lambda, int32_t prec
     NEED_READY();
     TRY(apply_check(ctx, "nlls_solve_pcg_rhs", -1, false));
     if (ctx->info.ndof == 0) { if (stats_out) for (int64_t k = 0; k < 4 * (int64_t)nrhs + 4; ++k) stats_out[k] = 0.0; return NLLS_OK; }
-    return pcg_solve_cols(ctx, "nlls_solve_pcg_rhs", which, lambda, precond, maxiters, rtol, nrhs, B, nullptr, X_out, stats_out);
+    return pcg_solve_cols(ctx, PcgCall{.name = "nlls_solve_pcg_rhs", .which = which, .lambda = lambda, .precond = precond, .maxiters = maxiters, .rtol = rtol, .ncols = nrhs, .B = B, .out = X_out}, stats_out);
     NLLS_API_END(ctx)
 }
 int nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel, const int64_t* varindices, int32_t precond, int32_t maxiters, double rtol, double* cov_out, double* stats_out) { NLLS_API_BEGIN
@@ -568,7 +572,7 @@ int nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel,
         for (int32_t k = 0; k < ctx->blocksizes[(size_t)(blk - 1)]; ++k) rows.push_back(ctx->boffsets[(size_t)(blk - 1)] + k); }
     const int64_t m = (int64_t)rows.size();
     if (m == 0) { if (stats_out) for (int k = 0; k < 4; ++k) stats_out[k] = 0.0; return NLLS_OK; }
-    return pcg_solve_cols(ctx, "nlls_marginal_cov", which, lambda, precond, maxiters, rtol, m, nullptr, rows.data(), cov_out, stats_out);
+    return pcg_solve_cols(ctx, PcgCall{.name = "nlls_marginal_cov", .which = which, .lambda = lambda, .precond = precond, .maxiters = maxiters, .rtol = rtol, .ncols = m, .rows = rows.data(), .out = cov_out}, stats_out);
     NLLS_API_END(ctx)
 }
 // One Levenberg-Marquardt trial in one call and one synchronisation (src/iterators.jl:149-157): uniformscaling!(H, dlambda),

@@ -228,15 +228,15 @@ struct ApplyIndex {
     uint32_t nslots = 0; int part_w_vec = 1, part_w_diag = 1;      // segments of all cut rows; widest cut row (unknowns; entries of its diagonal block)
 };
 
-// ---- block-Jacobi conjugate gradients on the device (nlls_pcg.hip): nlls_solve_pcg ---------------------------------------------------------------------------
-// Buffers of the solver's own, outside the hot arena: allocated at the first call after an upload, dropped by the next one.  vec: y, r0, r1, z, p, q (ndof each);
-// Minv: the inverses of the diagonal blocks of H + lambda I (sum of dof_b^2, the layout of nlls_hess_block_diag); part: three rows of per-workgroup partial sums
-// (p'q | r'z | r'r); scal: the scalar block PCG_* below.
+// ---- block-Jacobi conjugate gradients on the device (nlls_pcg.hip): nlls_solve_pcg, nlls_solve_pcg_rhs, nlls_marginal_cov ------------------------------------
+// ONE set of buffers of the solver's own for the three of them, outside the hot arena: grown on demand by the driver (pcg_solve_cols), dropped by the next upload.  Up to
+// NLLS_APPLY_MAX_VEC columns iterate together; a call lays the buffers out by its own cap = min(columns, NLLS_APPLY_MAX_VEC), nlls_solve_pcg's is 1.
+// vec: y | r0 | r1 | z | p | q, each `cap` columns of ndof (the columns of p and of q are contiguous: one enqueue_hess_apply takes them all); Minv: the inverses of the
+// diagonal blocks of H + lambda I at the CALL's lambda (sum of dof_b^2, the layout of nlls_hess_block_diag); part: three rows of per-workgroup partial sums per column
+// (p'q | r'z | r'r); scal: a scalar block PCG_* per column and one more, the factorisation's, that every column's block starts from; io: the caller's B, overwritten
+// column by column with the results (nlls_marginal_cov: one batch of unit columns; nlls_solve_pcg: unused); rows, cov: the selected unknowns and the m x m block of
+// nlls_marginal_cov.  h_scal: the pinned mirror of the batch's scalar blocks, one copy per round.
 enum { PCG_RZ0 = 0, PCG_RZ1 = 1, PCG_PQ = 2, PCG_RR = 3, PCG_BB = 4, PCG_ITER = 5, PCG_STOP = 6, PCG_STATUS = 7, PCG_NSCAL = 8 };   // r'z by parity of the iteration, p'q, r'r, b'b, iterations, stop, status
-// nlls_solve_pcg_rhs / nlls_marginal_cov: up to NLLS_APPLY_MAX_VEC columns iterate together.  vec: y | r0 | r1 | z | p | q, each `cap` columns of ndof (the columns
-// of p and of q are contiguous: one enqueue_hess_apply takes them all); part: three rows of partials per column; scal: a scalar block per column and one more, the
-// factorisation's, that every column's block starts from; io: the caller's B, overwritten column by column with the results (nlls_marginal_cov: one batch of unit
-// columns); rows, cov: the selected unknowns and the m x m block of nlls_marginal_cov.  h_scal: the pinned mirror of the batch's scalar blocks, one copy per round.
 struct PinnedBuf {
     double* p = nullptr; size_t n = 0;
     PinnedBuf() = default;
@@ -248,8 +248,7 @@ struct PinnedBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
     hipError_t alloc(size_t count) { release(); n = count; return hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(double), hipHostMallocDefault); }
 };
-struct PcgRhsState { DevBuf<double> vec, Minv, part, scal, io, cov; DevBuf<int64_t> rows; PinnedBuf h_scal; int64_t pw = 0; };
-struct PcgState { DevBuf<double> vec, Minv, part, scal; int64_t ndof = 0, pw = 0; PcgRhsState rhs; };      // pw: doubles of one row of part
+struct PcgState { DevBuf<double> vec, Minv, part, scal, io, cov; DevBuf<int64_t> rows; PinnedBuf h_scal; int64_t pw = 0; };      // pw: doubles of one row of part
 
 }  // namespace nlls
 
@@ -304,7 +303,7 @@ struct nlls_ctx {
     nlls::DevBuf<double> partials;           // per-workgroup cost partials
     int num_cus = 256;
     nlls::DevBuf<double> scalars;            // small device scratch for scalar results
-    double* h_scalars = nullptr;             // pinned host mirror (64 doubles; [48, 56): nlls_solve_pcg's scalar block, once per round)
+    double* h_scalars = nullptr;             // pinned host mirror (64 doubles; the conjugate gradients mirror their scalars in PcgState::h_scal, not here)
     int64_t trial_seq = 0;                   // sequence number the trial's finishing launch publishes in h_scalars[32], [33]
     double* h_scalars_dev = nullptr;         // ... as the device sees it (the trial's finishing launch writes the scalars there itself)
     int64_t npartials = 0;

@@ -77,11 +77,22 @@ int64_t apply_diag_len(const nlls_ctx* c);     // doubles of nlls_hess_block_dia
 // block-Jacobi conjugate gradients on (H + c->lambda I) y = b with the products above (nlls_pcg.hip): the caller has checked the arguments and holds b; synchronises once per
 // round of c->pcg_round iterations.  NLLS_OK: c->x = -y (and x_out, host, if not null); NLLS_ERR_NOT_SPD: a breakdown, c->x and x_out untouched.  stats: nlls_solve_pcg's (may be null)
 int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats);
-// the same iteration on ncols right-hand sides of the caller's, NLLS_APPLY_MAX_VEC at a time, H at set `which`, lambda the argument; reads only.  B: ncols columns of ndof
-// (host), out the solutions; B null: column j is the unit vector of unknown h_rows[j] (0-based, host), out the ncols x ncols block of the inverse (nlls_marginal_cov).
-// NLLS_ERR_NOT_SPD: a column broke down, out untouched.  stats: 4 * ncols + 4 doubles (may be null).  `name`: the entry point, for the error text
-int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int precond, int maxiters, double rtol, int64_t ncols, const double* B, const int64_t* h_rows,
-                   double* out, double* stats);
+// the iteration itself, on ncols right-hand sides, NLLS_APPLY_MAX_VEC at a time: what pcg_solve is one column of, and nlls_solve_pcg_rhs / nlls_marginal_cov call as it is.
+// What differs between the three is the call's description.  Exactly one of d_b, B, rows is set:
+//   d_b   ONE right-hand side on the device, never written (the step: c->b); the solution leaves as x = -y in c->x, nothing goes to the host, the caller synchronises
+//   B     ncols columns of ndof on the host, copied in a batch at a time; `out` (host): the solutions
+//   rows  column j is the unit vector of unknown rows[j] (0-based, host), written on the device; `out` (host): rows `rows` of the solutions, ncols x ncols (nlls_marginal_cov)
+// Nothing leaves the solver's own buffers -- c->x and `out` stay byte for byte -- before every column of the call has ended well.
+struct PcgCall {
+    const char* name;                      // the entry point, for the error texts
+    int which; double lambda;              // H at this variable set, this damping
+    int precond, maxiters; double rtol;
+    int64_t ncols;
+    const double* d_b = nullptr; const double* B = nullptr; const int64_t* rows = nullptr; double* out = nullptr;
+    bool look_first = true;                // the first look at the stop flags before the first product (a zero column, a missing factor pay for none) or behind the first round (one synchronisation less)
+};
+// NLLS_ERR_NOT_SPD: a column broke down (the error text names the first one).  stats: 4 * ncols + 4 doubles (may be null)
+int pcg_solve_cols(nlls_ctx* c, const PcgCall& call, double* stats);
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);

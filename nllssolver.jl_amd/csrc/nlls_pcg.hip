@@ -17,6 +17,10 @@
 // own scalar block and rows of partials (those of the column PcgArgs::cols names for the slot: a column keeps them when its vectors move to another slot).
 // pcg_column() turns the launch's arguments into the column's and the bodies below are those of one column: nlls_solve_pcg launches them with one.  A workgroup
 // belongs to one column, so the stop flag is one value per workgroup and a stopped column's workgroups leave at entry while the others iterate.
+// Host: ONE driver, pcg_solve_cols, allocates (nlls_ctx::pcg, one set of buffers), fills PcgArgs, launches and loops for the three entry points; a PcgCall
+// (nlls_internal.hpp) says where the right-hand sides come from, where a finished column goes and when the first look at the stop flags is due.  pcg_solve is that
+// driver on one column -- H at CURRENT, the context's damping, b the gradient where it lies -- plus what is the step's alone: the phase events, step_replaced, the
+// counters of nlls_get_solve_stats, the copy to x_out, its eight statistics and its error texts.
 #include <algorithm>
 #include <cmath>
 
@@ -196,19 +200,6 @@ __global__ __launch_bounds__(TPB) void pcg_pick_kernel(const double* __restrict_
 // host side
 // ================================================================================================
 namespace {
-int pcg_buffers(nlls_ctx* c, bool jacobi) {
-    PcgState& S = c->pcg; const int64_t ndof = c->info.ndof;
-    auto need = [&](DevBuf<double>& buf, size_t n, const char* what) -> int {
-        if (buf.n >= n && buf.p) return NLLS_OK;
-        const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(c, e, what); }
-        return NLLS_OK; };
-    S.ndof = ndof; S.pw = (ndof + TPB - 1) / TPB;
-    int rc = need(S.vec, (size_t)(6 * ndof), "nlls_solve_pcg: the vectors"); if (rc != NLLS_OK) return rc;
-    rc = need(S.part, (size_t)(3 * S.pw), "nlls_solve_pcg: the partial sums"); if (rc != NLLS_OK) return rc;
-    rc = need(S.scal, (size_t)PCG_NSCAL, "nlls_solve_pcg: the scalars"); if (rc != NLLS_OK) return rc;
-    if (jacobi) rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "nlls_solve_pcg: the preconditioner's blocks");
-    return rc;
-}
 // launches of one enqueue_hess_apply of one vector (what it just enqueued: the block launches of the non-empty groups, the gather's)
 int64_t product_launches(const nlls_ctx* c) {
     int64_t n = 0; for (const Group& G : c->groups) n += G.ncost > 0;
@@ -216,76 +207,12 @@ int64_t product_launches(const nlls_ctx* c) {
 }
 }  // namespace
 
-int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats) {
-    const int64_t ndof = c->info.ndof; const bool jacobi = precond == NLLS_PCG_PRECOND_BLOCK_JACOBI;
-    double st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto report = [&]() { c->pcg_iters = (int64_t)st[0]; c->pcg_status = (int64_t)st[1]; c->pcg_rounds = (int64_t)st[4]; if (stats) for (int k = 0; k < 8; ++k) stats[k] = st[k]; };
-    int rc = pcg_buffers(c, jacobi); if (rc != NLLS_OK) return rc;
-    PcgState& S = c->pcg; const double lambda = c->lambda;
-    double* const y = S.vec.p; double* const r[2] = {y + ndof, y + 2 * ndof}; double* const z = y + 3 * ndof; double* const p = y + 4 * ndof; double* const q = y + 5 * ndof;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(S.pw, std::max<int64_t>(c->pcg_grid_max, 1)));
-    const bool timed = c->phase_on && c->phase_ev.size() >= 16;
-    if (timed) (void)hipEventRecord(c->phase_ev[14], c->stream);
-    int64_t launches = 0;
-    HIPCHK(hipMemsetAsync(S.scal.p, 0, sizeof(double) * PCG_NSCAL, c->stream));
-    if (jacobi) { rc = enqueue_hess_block_diag(c, NLLS_VARS_CURRENT, lambda, S.Minv.p); if (rc != NLLS_OK) return rc; launches += product_launches(c); }
-    PcgArgs a{};
-    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = rtol * rtol;
-    a.b = c->b.p; a.Minv = S.Minv.p; a.y = y; a.r_old = r[1]; a.r_new = r[0]; a.z = z; a.p = p; a.q = q;
-    a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.scal = S.scal.p;
-    if (jacobi) {       // (the index of the products exists: enqueue_hess_block_diag built it)
-        a.erow = c->app.erow_vec.p; a.start = c->app.start_vec.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;
-        hipLaunchKernelGGL(pcg_factor_kernel, dim3((unsigned)((a.nblocks + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a, S.Minv.p); ++launches;
-    }
-    hipLaunchKernelGGL(pcg_init_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
-    hipLaunchKernelGGL(pcg_start_kernel, dim3(1), dim3(TPB), 0, c->stream, a); launches += 2;
-    HIPCHK(hipGetLastError());
-    const int64_t round = std::max<int64_t>(c->pcg_round, 1);
-    double* const h = c->h_scalars + 48;      // the pinned mirror's slots [48, 56): nothing else uses them (a copy into pageable memory is staged, and the round waits for it)
-    for (int k = 0; k < PCG_NSCAL; ++k) h[k] = 0.0;
-    int64_t it = 0, rounds = 0;
-    for (;;) {
-        const int64_t n = std::min<int64_t>(round, (int64_t)maxiters - it);
-        for (int64_t k = 0; k < n; ++k, ++it) {
-            a.parity = (int)(it & 1); a.r_old = r[it & 1]; a.r_new = r[(it + 1) & 1];
-            rc = enqueue_hess_apply(c, NLLS_VARS_CURRENT, lambda, 1, p, q); if (rc != NLLS_OK) return rc;
-            hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
-            hipLaunchKernelGGL(pcg_step_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
-            hipLaunchKernelGGL(pcg_dir_kernel, dim3(grid), dim3(TPB), 0, c->stream, a);
-            launches += product_launches(c) + 3;
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream)); ++rounds;
-        if (h[PCG_STOP] != 0.0 || it >= maxiters) break;
-    }
-    const int status = h[PCG_STOP] != 0.0 ? (int)h[PCG_STATUS] : 1;
-    st[0] = h[PCG_ITER]; st[1] = status; st[2] = std::sqrt(h[PCG_BB]); st[3] = std::sqrt(h[PCG_RR]); st[4] = (double)rounds; st[5] = (double)launches;
-    if (status >= 2) {
-        if (timed) { (void)hipEventRecord(c->phase_ev[15], c->stream); c->pcg_pending = true; }
-        report();
-        c->err = status == 3 ? "nlls_solve_pcg: a diagonal block of H + lambda I is not positive definite (status 3)"
-                             : "nlls_solve_pcg: p'(H + lambda I)p is not positive, or a scalar of the recurrence is not finite (status 2, iteration " + std::to_string((int64_t)h[PCG_ITER]) + ")";
-        return NLLS_ERR_NOT_SPD;
-    }
-    step_replaced(c);
-    hipLaunchKernelGGL(pcg_finish_kernel, dim3(grid), dim3(TPB), 0, c->stream, y, c->x.p, ndof); ++launches;
-    HIPCHK(hipGetLastError());
-    if (timed) { (void)hipEventRecord(c->phase_ev[15], c->stream); c->pcg_pending = true; }
-    if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    st[4] = (double)(rounds + 1); st[5] = (double)launches;
-    report();
-    return NLLS_OK;
-}
-
-// nlls_solve_pcg_rhs (B: ncols columns of ndof, host) and nlls_marginal_cov (B null: column j is the unit vector of unknown h_rows[j], ncols = m, out is m x m).
-// The caller has checked the arguments.  stats: 4 * ncols + 4 doubles (may be null)
-int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int precond, int maxiters, double rtol, int64_t ncols, const double* B, const int64_t* h_rows,
-                   double* out, double* stats) {
+// The driver of the three entry points: the only place that allocates, launches and loops.  The caller has checked the arguments.  stats: 4 * ncols + 4 doubles (may be null)
+int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     constexpr int MAXC = NLLS_APPLY_MAX_VEC;
-    const int64_t ndof = c->info.ndof; const bool jacobi = precond == NLLS_PCG_PRECOND_BLOCK_JACOBI; const std::string nm(name);
-    PcgRhsState& S = c->pcg.rhs; const int cap = (int)std::min<int64_t>(ncols, MAXC);
+    const int64_t ndof = c->info.ndof, ncols = k.ncols; const int maxiters = k.maxiters; const bool jacobi = k.precond == NLLS_PCG_PRECOND_BLOCK_JACOBI; const std::string nm(k.name);
+    const double* const B = k.B; const bool step = k.d_b != nullptr, units = k.rows != nullptr;
+    PcgState& S = c->pcg; const int cap = (int)std::min<int64_t>(ncols, MAXC);
     auto need = [&](auto& buf, size_t n, const char* what) -> int {
         if (buf.n >= n && buf.p) return NLLS_OK;
         const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(c, e, (nm + ": " + what).c_str()); }
@@ -295,71 +222,76 @@ int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int 
     rc = need(S.part, (size_t)(3 * S.pw * cap), "the partial sums"); if (rc != NLLS_OK) return rc;
     rc = need(S.scal, (size_t)((MAXC + 1) * PCG_NSCAL), "the scalars"); if (rc != NLLS_OK) return rc;
     rc = need(S.h_scal, (size_t)(MAXC * PCG_NSCAL), "the pinned mirror of the scalars"); if (rc != NLLS_OK) return rc;
-    rc = need(S.io, (size_t)((B ? ncols : (int64_t)cap) * ndof), "the columns"); if (rc != NLLS_OK) return rc;
+    if (!step) { rc = need(S.io, (size_t)((B ? ncols : (int64_t)cap) * ndof), "the columns"); if (rc != NLLS_OK) return rc; }
     if (jacobi) { rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "the preconditioner's blocks"); if (rc != NLLS_OK) return rc; }
-    if (!B) { rc = need(S.rows, (size_t)ncols, "the selected unknowns"); if (rc != NLLS_OK) return rc;
-              rc = need(S.cov, (size_t)(ncols * ncols), "the covariance block"); if (rc != NLLS_OK) return rc; }
-    const int64_t vs = (int64_t)cap * ndof;      // doubles of one of the six arrays
+    if (units) { rc = need(S.rows, (size_t)ncols, "the selected unknowns"); if (rc != NLLS_OK) return rc;
+                 rc = need(S.cov, (size_t)(ncols * ncols), "the covariance block"); if (rc != NLLS_OK) return rc; }
+    const int64_t vs = (int64_t)cap * ndof;      // doubles of one of the six arrays: the layout is this call's, whatever an earlier call left in the buffers
     double* const y = S.vec.p; double* const r[2] = {y + vs, y + 2 * vs}; double* const z = y + 3 * vs; double* const p = y + 4 * vs; double* const q = y + 5 * vs;
     double* const fscal = S.scal.p + MAXC * PCG_NSCAL; double* const h = S.h_scal.p;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(S.pw, std::max<int64_t>(c->pcg_grid_max, 1)));
     std::vector<double> st((size_t)(4 * ncols + 4), 0.0);
     int64_t launches = 0, syncs = 0, products = 0, batches = 0; bool bad = false; int64_t bad_col = -1; int bad_status = 0;
-    if (!B) HIPCHK(hipMemcpyAsync(S.rows.p, h_rows, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, c->stream));
+    if (units) HIPCHK(hipMemcpyAsync(S.rows.p, k.rows, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(fscal, 0, sizeof(double) * PCG_NSCAL, c->stream));
     PcgArgs a{};
-    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = rtol * rtol;
+    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = k.rtol * k.rtol;
     a.Minv = S.Minv.p; a.y = y; a.r_old = r[1]; a.r_new = r[0]; a.z = z; a.p = p; a.q = q;
-    a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.pstride = 3 * S.pw; a.scal = S.scal.p; a.b = S.io.p;
-    if (jacobi) {       // the preconditioner: once per call, whatever the number of batches
-        rc = enqueue_hess_block_diag(c, which, lambda, S.Minv.p); if (rc != NLLS_OK) return rc; launches += product_launches(c);
-        a.erow = c->app.erow_vec.p; a.start = c->app.start_vec.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;
+    a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.pstride = 3 * S.pw; a.scal = S.scal.p;
+    if (jacobi) {       // the preconditioner: once per call, whatever the number of batches (Minv is this call's: an earlier one left it at its own lambda)
+        rc = enqueue_hess_block_diag(c, k.which, k.lambda, S.Minv.p); if (rc != NLLS_OK) return rc; launches += product_launches(c);
+        a.erow = c->app.erow_vec.p; a.start = c->app.start_vec.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;       // (the index of the products exists: enqueue_hess_block_diag built it)
         PcgArgs f = a; f.scal = fscal;
         hipLaunchKernelGGL(pcg_factor_kernel, dim3((unsigned)((a.nblocks + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, f, S.Minv.p); ++launches;
     }
     const int64_t round = std::max<int64_t>(c->pcg_round, 1);
     for (int64_t j0 = 0; j0 < ncols && bad_status != 3; j0 += MAXC, ++batches) {
         const int nb = (int)std::min<int64_t>(MAXC, ncols - j0);
-        double* const bio = B ? S.io.p + j0 * ndof : S.io.p;      // the batch's right-hand sides, then its results
+        double* const bio = B ? S.io.p + j0 * ndof : S.io.p;      // the batch's right-hand sides, then its results (the step has neither here: d_b is read, c->x written at the end)
         if (B) HIPCHK(hipMemcpyAsync(bio, B + j0 * ndof, sizeof(double) * (size_t)(nb * ndof), hipMemcpyHostToDevice, c->stream));
-        else { hipLaunchKernelGGL(pcg_unit_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p + j0); ++launches; }
+        if (units) { hipLaunchKernelGGL(pcg_unit_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p + j0); ++launches; }
         hipLaunchKernelGGL(pcg_cols_begin_kernel, dim3(1), dim3(TPB), 0, c->stream, fscal, S.scal.p, nb);
-        a.b = bio; a.cols = 0x76543210u; a.parity = 0; a.r_old = r[1]; a.r_new = r[0];
+        a.b = step ? k.d_b : bio; a.cols = 0x76543210u; a.parity = 0; a.r_old = r[1]; a.r_new = r[0];
         hipLaunchKernelGGL(pcg_init_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, a);
         hipLaunchKernelGGL(pcg_start_kernel, dim3(1, nb), dim3(TPB), 0, c->stream, a); launches += 3;
         HIPCHK(hipGetLastError());
         int slot_col[MAXC]; for (int s = 0; s < MAXC; ++s) slot_col[s] = s;
         int active = nb; int64_t it = 0;
         auto stopped = [&](int s) { return h[slot_col[s] * PCG_NSCAL + PCG_STOP] != 0.0; };
-        auto finalize = [&](int s) -> hipError_t {          // the column's four statistics; its y to its place among the results
+        auto finalize = [&](int s) -> hipError_t {          // the column's four statistics; its y to its place among the results (the step's one column stays in slot 0)
             const int col = slot_col[s]; const double* hc = h + col * PCG_NSCAL; double* sc = st.data() + 4 * (j0 + col);
             const int status = hc[PCG_STOP] != 0.0 ? (int)hc[PCG_STATUS] : 1;
             sc[0] = hc[PCG_ITER]; sc[1] = status; sc[2] = std::sqrt(hc[PCG_BB]); sc[3] = std::sqrt(hc[PCG_RR]);
             if (status >= 2) { if (!bad) { bad = true; bad_col = j0 + col; bad_status = status; } if (status == 3) bad_status = 3; return hipSuccess; }
+            if (step) return hipSuccess;
             return hipMemcpyAsync(bio + (int64_t)col * ndof, y + (int64_t)s * ndof, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToDevice, c->stream); };
-        for (;;) {      // a look, then a round: the first look finds the columns that need no iteration (b == 0; no factor), so that they pay for no product either
-            HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * (size_t)(nb * PCG_NSCAL), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream)); ++syncs;       // one look per round for all columns
-            if (it >= maxiters) { for (int s = 0; s < active; ++s) HIPCHK(finalize(s)); active = 0; break; }
-            // a stopped column pays for no further product: the columns still iterating stay contiguous -- the last one's y, current r and p move into the freed slot
-            // (z, q and the other r are written before they are read in the next iteration)
-            int s = 0;
-            while (s < active) {
-                if (!stopped(s)) { ++s; continue; }
-                HIPCHK(finalize(s)); int last = --active;
-                while (last > s && stopped(last)) { HIPCHK(finalize(last)); last = --active; }
-                if (last > s) {
-                    double* const mv[3] = {y, r[it & 1], p};
-                    for (double* v : mv) HIPCHK(hipMemcpyAsync(v + (int64_t)s * ndof, v + (int64_t)last * ndof, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToDevice, c->stream));
-                    slot_col[s] = slot_col[last]; ++s;
+        // a look, then a round.  look_first: the first look finds the columns that need no iteration (b == 0; no factor), so that they pay for no product either; without
+        // it the first look comes behind the first round, and the call synchronises once per round and no more
+        for (;;) {
+            if (it > 0 || k.look_first) {
+                HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * (size_t)(nb * PCG_NSCAL), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream)); ++syncs;       // one look per round for all columns
+                if (it >= maxiters) { for (int s = 0; s < active; ++s) HIPCHK(finalize(s)); active = 0; break; }
+                // a stopped column pays for no further product: the columns still iterating stay contiguous -- the last one's y, current r and p move into the freed slot
+                // (z, q and the other r are written before they are read in the next iteration)
+                int s = 0;
+                while (s < active) {
+                    if (!stopped(s)) { ++s; continue; }
+                    HIPCHK(finalize(s)); int last = --active;
+                    while (last > s && stopped(last)) { HIPCHK(finalize(last)); last = --active; }
+                    if (last > s) {
+                        double* const mv[3] = {y, r[it & 1], p};
+                        for (double* v : mv) HIPCHK(hipMemcpyAsync(v + (int64_t)s * ndof, v + (int64_t)last * ndof, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToDevice, c->stream));
+                        slot_col[s] = slot_col[last]; ++s;
+                    }
                 }
+                if (active == 0) break;
             }
-            if (active == 0) break;
             const int64_t n = std::min<int64_t>(round, (int64_t)maxiters - it);
             a.cols = 0; for (int s = 0; s < active; ++s) a.cols |= (uint32_t)slot_col[s] << (4 * s);
-            for (int64_t k = 0; k < n; ++k, ++it) {
+            for (int64_t i = 0; i < n; ++i, ++it) {
                 a.parity = (int)(it & 1); a.r_old = r[it & 1]; a.r_new = r[(it + 1) & 1];
-                rc = enqueue_hess_apply(c, which, lambda, active, p, q); if (rc != NLLS_OK) return rc;
+                rc = enqueue_hess_apply(c, k.which, k.lambda, active, p, q); if (rc != NLLS_OK) return rc;
                 hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
                 hipLaunchKernelGGL(pcg_step_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
                 hipLaunchKernelGGL(pcg_dir_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
@@ -367,16 +299,19 @@ int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int 
             }
             HIPCHK(hipGetLastError());
         }
-        if (!B && !bad) { hipLaunchKernelGGL(pcg_pick_kernel, dim3((unsigned)((ncols * nb + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p, ncols, nb, S.cov.p + j0 * ncols); ++launches;
-                          HIPCHK(hipGetLastError()); }
+        if (units && !bad) { hipLaunchKernelGGL(pcg_pick_kernel, dim3((unsigned)((ncols * nb + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p, ncols, nb, S.cov.p + j0 * ncols); ++launches;
+                             HIPCHK(hipGetLastError()); }
     }
-    if (bad_status == 3) for (int64_t k = 0; k < ncols; ++k) { st[4 * k] = 0.0; st[4 * k + 1] = 3.0; st[4 * k + 2] = 0.0; st[4 * k + 3] = 0.0; }   // call-wide: no column started
-    if (!bad) {
-        // (a batch at a time, as the right-hand sides came: one copy of 16 columns of ba_1kx100k into pageable memory took longer than two of 8, notes/r19.md)
-        if (B) { for (int64_t j0 = 0; j0 < ncols; j0 += MAXC) { const int64_t nb = std::min<int64_t>(MAXC, ncols - j0);
-                     HIPCHK(hipMemcpyAsync(out + j0 * ndof, S.io.p + j0 * ndof, sizeof(double) * (size_t)(nb * ndof), hipMemcpyDeviceToHost, c->stream)); } }
-        else HIPCHK(hipMemcpyAsync(out, S.cov.p, sizeof(double) * (size_t)(ncols * ncols), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream)); ++syncs;
+    if (bad_status == 3) for (int64_t j = 0; j < ncols; ++j) { st[4 * j] = 0.0; st[4 * j + 1] = 3.0; st[4 * j + 2] = 0.0; st[4 * j + 3] = 0.0; }   // call-wide: no column started
+    if (!bad) {         // every column of the call has ended well: only now does a result leave the solver's own buffers
+        if (step) { hipLaunchKernelGGL(pcg_finish_kernel, dim3(grid), dim3(TPB), 0, c->stream, y, c->x.p, ndof); ++launches; HIPCHK(hipGetLastError()); }      // (pcg_solve waits for it)
+        else {
+            // (a batch at a time, as the right-hand sides came: one copy of 16 columns of ba_1kx100k into pageable memory took longer than two of 8, notes/r19.md)
+            if (B) { for (int64_t j0 = 0; j0 < ncols; j0 += MAXC) { const int64_t nb = std::min<int64_t>(MAXC, ncols - j0);
+                         HIPCHK(hipMemcpyAsync(k.out + j0 * ndof, S.io.p + j0 * ndof, sizeof(double) * (size_t)(nb * ndof), hipMemcpyDeviceToHost, c->stream)); } }
+            else HIPCHK(hipMemcpyAsync(k.out, S.cov.p, sizeof(double) * (size_t)(ncols * ncols), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream)); ++syncs;
+        }
     }
     double* const tail = st.data() + 4 * ncols;
     tail[0] = (double)syncs; tail[1] = (double)launches; tail[2] = (double)products; tail[3] = (double)batches;
@@ -389,4 +324,30 @@ int pcg_solve_cols(nlls_ctx* c, const char* name, int which, double lambda, int 
     return NLLS_OK;
 }
 
+// nlls_solve_pcg: the driver on ONE column, the gradient where the sweep left it, H at CURRENT under the context's damping -- and what is the step's alone
+int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats) {
+    double st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cs[8];         // cs: the column's four statistics, then synchronisations, launches, product vectors, batches
+    auto report = [&]() { c->pcg_iters = (int64_t)st[0]; c->pcg_status = (int64_t)st[1]; c->pcg_rounds = (int64_t)st[4]; if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i]; };
+    const bool timed = c->phase_on && c->phase_ev.size() >= 16;
+    if (timed) (void)hipEventRecord(c->phase_ev[14], c->stream);
+    const int rc = pcg_solve_cols(c, PcgCall{.name = "nlls_solve_pcg", .which = NLLS_VARS_CURRENT, .lambda = c->lambda, .precond = precond, .maxiters = maxiters, .rtol = rtol,
+                                             .ncols = 1, .d_b = c->b.p, .look_first = false}, cs);
+    if (rc != NLLS_OK && rc != NLLS_ERR_NOT_SPD) return rc;
+    for (int i = 0; i < 6; ++i) st[i] = cs[i];
+    if (timed) { (void)hipEventRecord(c->phase_ev[15], c->stream); c->pcg_pending = true; }
+    if (rc == NLLS_ERR_NOT_SPD) {
+        report();
+        c->err = (int)st[1] == 3 ? "nlls_solve_pcg: a diagonal block of H + lambda I is not positive definite (status 3)"
+                                 : "nlls_solve_pcg: p'(H + lambda I)p is not positive, or a scalar of the recurrence is not finite (status 2, iteration " + std::to_string((int64_t)st[0]) + ")";
+        return rc;
+    }
+    step_replaced(c);
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)c->info.ndof, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    st[4] += 1.0;
+    report();
+    return NLLS_OK;
+}
+
 }  // namespace nlls
+

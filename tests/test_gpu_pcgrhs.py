@@ -97,6 +97,54 @@ def test_equal_to_solve_pcg(pc):
     ctx.close()
 
 
+def test_interleaved_calls_share_buffers():
+    """The three entry points share one driver and one set of buffers, regrown between calls, laid out by each call's own cap = min(columns, 8), with Minv left behind at
+    another call's lambda.  558 unknowns: three workgroups of 256 per column, blocks of two sizes.  Every call of the sequence on ONE context returns, byte for byte and in
+    every statistic, what the FIRST call on a fresh context of the same problem returns.
+
+    For nlls_solve_pcg_rhs and nlls_marginal_cov the fresh context makes the same call.  nlls_solve_pcg reads the gradient of the context's own sweep, and two sweeps
+    of this problem (two cost groups share rows: the accumulate sweep adds them with atomics) differ in the last bits -- on the MI355X the first solve_pcg of two fresh
+    contexts differed in x from byte 8 on.  Its reference is therefore the call that takes that gradient as an ARGUMENT, nlls_solve_pcg_rhs(b, lambda = the damping,
+    CURRENT, one column) as the first call of a fresh context: -X and the four statistics, byte for byte (the rule of test_equal_to_solve_pcg), the synchronisations
+    ceil(k / round) + 1; and the second solve_pcg of the sequence, behind the two column calls, equals the first one of the same context in every byte and statistic."""
+    p, unfixed = affine_two_groups(); ctx, A, b, bo, bs = swept(p, unfixed); ndof = b.size
+    lam = 1e-2 * np.max(np.abs(np.diag(A))); lam2 = 0.5 * lam
+    B9 = np.random.default_rng(29).standard_normal((9, ndof)); sel = [57, 4]                  # a point and a camera: m = 9, two batches of unit columns
+    assert ndof == 558 and sorted(set(bs.tolist())) == [3, 6]
+    (k,) = mirror_converges(A, lam, bo, bs, [b]); assert k > 4                                  # (maxiters = 4 below ends on the cap)
+    mirror_converges(A, lam2, bo, bs, B9[:2])
+    ctx.damp(lam); g = ctx.get_grad()
+    step = lambda mi: ((lambda c: c.solve_pcg(JACOBI, mi, 1e-10, want_x=True)), (lambda c: c.solve_pcg_rhs(g, lam, CUR, JACOBI, mi, 1e-10)))
+    cols = lambda f: (f, f)
+    calls = [("solve_pcg", *step(None)),                                                        # (on the one context, as the first call of a fresh one)
+             ("solve_pcg_rhs, 9 columns at another lambda", *cols(lambda c: c.solve_pcg_rhs(B9, lam2, CUR, JACOBI, None, 1e-10))),
+             ("marginal_cov of two variables", *cols(lambda c: c.marginal_cov(sel, lam, CUR, JACOBI, None, 1e-10))),
+             ("solve_pcg again", *step(None)),
+             ("solve_pcg_rhs, one column", *cols(lambda c: c.solve_pcg_rhs(B9[3], lam2, CUR, JACOBI, None, 1e-10))),
+             ("solve_pcg, maxiters 4", *step(4))]
+
+    def same(u, v):
+        return type(u) is type(v) and (u.tobytes() == v.tobytes() if isinstance(u, np.ndarray) else u == v)
+
+    seen = {}
+    for what, call, first in calls:
+        got, gs = call(ctx)
+        fresh = swept(p, unfixed)[0]; fresh.damp(lam); ref, rs = first(fresh); fresh.close()
+        print(f"PCGRHS interleaved, {what}: iterations {np.asarray(gs['iterations']).tolist()} status {np.asarray(gs['status']).tolist()} launches {gs['launches']}")
+        assert np.all(rs["status"] == (1 if "maxiters" in what else 0)), (what, rs)
+        if call is first:
+            assert got.shape == ref.shape and got.tobytes() == ref.tobytes(), what
+            assert gs.keys() == rs.keys() and all(same(gs[key], rs[key]) for key in rs), (what, gs, rs)
+            continue
+        assert got.shape == ref.shape == (ndof,) and got.tobytes() == (-ref).tobytes() and ctx.get_step().tobytes() == got.tobytes(), what
+        assert (gs["iterations"], gs["status"], gs["bnorm"], gs["rnorm"]) == colstats(rs, 0), (what, gs, rs)
+        assert gs["rounds"] == gs["iterations"] + 1, (what, gs)                               # (round length 1)
+        seen[what] = (got.tobytes(), dict(gs))
+    assert seen["solve_pcg again"] == seen["solve_pcg"] and seen["solve_pcg, maxiters 4"][1]["iterations"] == 4
+    assert ctx.get_grad().tobytes() == g.tobytes()
+    ctx.close()
+
+
 # ---- 3. column independence ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("pc", [JACOBI, NONE], ids=["blockjacobi", "none"])
 def test_column_independence(pc):

@@ -39,7 +39,11 @@ def test_entry_point_sits_between_the_guard_pair_and_reads_no_environment():
     assert "NLLS_API_BEGIN" in heads["nlls_solve_pcg"]
     hip = open(os.path.join(CSRC, "nlls_pcg.hip")).read()
     assert "getenv" not in hip and "hipFuncSetAttribute" not in hip and "#define HIPCHK" not in hip and "atomicAdd" not in hip and "__hip_atomic" not in hip
-    assert "block_sum" in hip and "enqueue_hess_apply(c, NLLS_VARS_CURRENT, lambda, 1, p, q)" in hip and "enqueue_hess_block_diag" in hip
+    assert "block_sum" in hip and "enqueue_hess_block_diag" in hip
+    # the product is the driver's ONE call, and nlls_solve_pcg is that driver on one column: H at CURRENT, the context's damping, b where the sweep left it
+    assert hip.count("enqueue_hess_apply(c,") == 1 and "enqueue_hess_apply(c, k.which, k.lambda, active, p, q)" in hip
+    assert ".which = NLLS_VARS_CURRENT, .lambda = c->lambda" in hip and ".ncols = 1, .d_b = c->b.p" in hip
+    assert hip.count("for (;;)") == 1 and hip.count("PcgArgs a{}") == 1 and hip.count("hipLaunchKernelGGL(pcg_step_kernel") == 1
 
 
 def test_makefile_builds_it_like_the_products_and_into_the_user_libraries():
