@@ -445,6 +445,36 @@ int  nlls_solve_pcg_rhs(nlls_ctx* ctx, int32_t which, double lambda, int32_t pre
  * 1 .. nvar, an index listed twice, a listed variable that is fixed (it has no row in H). */
 int  nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel, const int64_t* varindices, int32_t precond, int32_t maxiters, double rtol, double* cov_out, double* stats_out);
 
+/* ---- the reduced system, matrix-free: products with the Schur complement and conjugate gradients on it -----------------------
+ * replaces: the reduced system the reference's direct solvers form and factor (src/linearsolver.jl:20-32) -- here it is applied, never formed: what Ceres calls
+ *           ITERATIVE_SCHUR, and the only Schur path for a reduced system too large to store.
+ * The upload picks an independent set of blocks to eliminate (nlls_info::nschur_blocks of them).  Two sets of unknowns:
+ *   e   the eliminated blocks
+ *   r   the other unfixed blocks, in ascending block order; nred is their dof, and a REDUCED vector has nred entries in that order
+ * With H + lambda I = [[B, E], [E', C]] over (r, e), C is block diagonal, and S(lambda) = B + lambda I - E (C + lambda I)^-1 E'.
+ * nlls_schur_info: nred, the number of eliminated blocks, and (is_elim_out not NULL) one byte per unfixed block, 1 where it is eliminated.  Needs an upload; no device work.
+ * The three products follow the rules of nlls_hess_apply: H is evaluated at set `which` at the time of the call, never read from A.data; lambda is the argument; host
+ * pointers, synchronous; they need an upload and no sweep, and change nothing -- no validity state, step, A.data, b, variable set, damping or pending look-ahead sweep;
+ * nvec is 1 .. NLLS_APPLY_MAX_VEC, cut into chunks under NLLS_OPT_APPLY_SCRATCH; every sum has a fixed order (no atomics): two calls return identical bytes, vector k
+ * of a call equals the call on it alone, a chunked call equals the unchunked one.
+ *   nlls_schur_apply    y_k = S(lambda) v_k
+ *   nlls_schur_reduce   s_k = b_r - E (C + lambda I)^-1 b_e
+ *   nlls_schur_expand   the r entries of y_k are yr_k, bit for bit; the e entries are (C + lambda I)^-1 (b_e - E' yr_k): expand(b, S^-1 reduce(b)) solves (H + lambda I) y = b
+ * NLLS_ERR_INVALID_ARG where nlls_hess_apply returns it (nothing enqueued, no byte written); NLLS_ERR_NOT_READY before an upload; NLLS_ERR_UNSUPPORTED where
+ * nlls_hess_apply refuses, and when the upload eliminated nothing (a dense system, NLLS_FLAG_NO_SCHUR): nlls_last_error says so; NLLS_ERR_NOT_SPD when a block
+ * C_e + lambda I has no Cholesky factor, no output byte written.
+ * nlls_solve_pcg_schur stands where nlls_solve_pcg stands: the gradient of the last sweep, H at CURRENT, the context's damping.  Conjugate gradients from 0 on
+ * S yr = reduce(b), then y = expand(b, yr) and x = -y as the context's step.  precond: NLLS_PCG_PRECOND_NONE, or NLLS_PCG_PRECOND_BLOCK_JACOBI -- here the diagonal
+ * blocks of B + lambda I.  It stops on the recurrence's ||r|| <= rtol ||s|| of the REDUCED system.  Statuses, return codes and stats_out[8] as nlls_solve_pcg, with
+ * ||s|| and the reduced ||r|| in [2], [3]; status 3 also covers an eliminated block without a factor; on 2 or 3 the step and x_out stay byte for byte.  The counters
+ * of nlls_get_solve_stats and nlls_get_phase_times keep describing the last nlls_solve_pcg.  NLLS_OPT_PCG_ROUND, NLLS_OPT_PCG_GRID_MAX and NLLS_OPT_APPLY_WAVE_MIN
+ * mean here what they mean for the full products. */
+int  nlls_schur_info(const nlls_ctx* ctx, int64_t* nred_out, int64_t* nelim_out, uint8_t* is_elim_out /* nblocks, may be NULL */);
+int  nlls_schur_apply(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* v /* nvec x nred */, double* y_out /* nvec x nred */);
+int  nlls_schur_reduce(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* b /* nvec x ndof */, double* s_out /* nvec x nred */);
+int  nlls_schur_expand(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* b /* nvec x ndof */, const double* yr /* nvec x nred */, double* y_out /* nvec x ndof */);
+int  nlls_solve_pcg_schur(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out);
+
 /* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
  * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
  *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.

@@ -40,7 +40,8 @@ nlls_get_reduce_buffer nlls_get_step_shard nlls_get_shard_info nlls_get_grad_own
 nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag nlls_comm_agreed_flag nlls_comm_info nlls_get_memory_info nlls_flush_cache nlls_check_analytic nlls_set_option nlls_get_time_buckets nlls_get_phase_times
 nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
 nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim
-nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg nlls_solve_pcg_rhs nlls_marginal_cov""".split()
+nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg nlls_solve_pcg_rhs nlls_marginal_cov
+nlls_schur_info nlls_schur_apply nlls_schur_reduce nlls_schur_expand nlls_solve_pcg_schur""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -141,6 +142,8 @@ def lib():
         L.nlls_jact_apply.argtypes = [vp, i32, i32, i32, vp, vp]; L.nlls_hess_block_diag.argtypes = [vp, i32, dbl, vp]
         L.nlls_solve_pcg.argtypes = [vp, i32, i32, dbl, vp, vp]
         L.nlls_solve_pcg_rhs.argtypes = [vp, i32, dbl, i32, i32, dbl, i32, vp, vp, vp]; L.nlls_marginal_cov.argtypes = [vp, i32, dbl, i64, vp, i32, i32, dbl, vp, vp]
+        L.nlls_schur_info.argtypes = [vp, vp, vp, vp]; L.nlls_schur_apply.argtypes = [vp, i32, dbl, i32, vp, vp]; L.nlls_schur_reduce.argtypes = [vp, i32, dbl, i32, vp, vp]
+        L.nlls_schur_expand.argtypes = [vp, i32, dbl, i32, vp, vp, vp]; L.nlls_solve_pcg_schur.argtypes = [vp, i32, i32, dbl, vp, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -205,6 +208,7 @@ class Context:
                 arr[i].robust_params[k] = float(rp[k])
             arr[i].ncost = vi.shape[0]; arr[i].varind = vi.ctypes.data; arr[i].data = da.ctypes.data
         self._var_kind, self._var_dim = vk, vd                   # (marginal_cov: the dof of the listed variables)
+        self._nred_of_upload = None
         self._kinds = [int(g["res_kind"]) for g in groups]      # (eval_jacobians / eval_gradhess: the record sizes of a group's kind)
         self._groups = []; self._ndata = [int(da.size // max(vi.shape[0], 1)) for vi, da in zip(keep[3::2], keep[4::2])]     # doubles of payload per block, per group (set_cost_data)
         self._chk(self.L.nlls_upload_structure(self.h, len(vk), _p(vk), _p(vd), _p(bi), len(groups), arr, flags))
@@ -307,7 +311,7 @@ class Context:
         out = np.zeros((a.shape[0], nout))
         for k0 in range(0, a.shape[0], APPLY_MAX_VEC):
             ak = np.ascontiguousarray(a[k0:k0 + APPLY_MAX_VEC]); ok = out[k0:k0 + APPLY_MAX_VEC]
-            self._chk(fn(self.h, *head, ak.shape[0], _p(ak), _p(ok)))
+            self._chk(fn(self.h, *head, ak.shape[0], _p(ak if ak.size else np.zeros(1)), _p(ok if ok.size else np.zeros(1))))      # (vectors of no entry: pointers that are not null)
         return out[0] if one else out
 
     def _group_rows(self, group):
@@ -402,6 +406,57 @@ class Context:
         self.last_pcg = dict(iterations=int(st[0]), status=int(st[1]), bnorm=float(st[2]), rnorm=float(st[3]), rounds=int(st[4]), launches=int(st[5]))
         self._chk(rc)
         return out, self.last_pcg
+
+    # ---- the reduced system, matrix-free (include/nlls_amd.h) -----------------------------------------------------
+    def schur_info(self):
+        """nlls_schur_info: (nred, nelim, is_elim, red_index) -- the dof of the reduced system, the number of eliminated blocks, a bool per unfixed block, and the
+        positions of the reduced unknowns in b (ascending block order: the order of a reduced vector)"""
+        nb = int(self.info.nblocks); nred, nelim = C.c_int64(0), C.c_int64(0); mask = np.zeros(max(nb, 1), np.uint8)
+        self._chk(self.L.nlls_schur_info(self.h, C.byref(nred), C.byref(nelim), _p(mask)))
+        is_elim = mask[:nb].astype(bool); bs = self.block_sizes()
+        red_index = np.flatnonzero(np.repeat(~is_elim, bs)).astype(np.int64)
+        return int(nred.value), int(nelim.value), is_elim, red_index
+
+    def _nred(self):
+        if getattr(self, "_nred_of_upload", None) is None:       # (asked once per upload: the products need it to shape their arrays)
+            nred = C.c_int64(0); self._chk(self.L.nlls_schur_info(self.h, C.byref(nred), None, None)); self._nred_of_upload = int(nred.value)
+        return self._nred_of_upload
+
+    def schur_apply(self, v, lam=0.0, which=VARS_CURRENT):
+        """nlls_schur_apply: S(lam) v, S = B + lam I - E (C + lam I)^-1 E' over the upload's eliminated set, H evaluated at variable set `which` and never formed.
+        v (nred,) -> (nred,); (nvec, nred) -> (nvec, nred).  An upload that eliminated nothing raises NllsError (ERR_UNSUPPORTED)."""
+        n = self._nred()
+        return self._apply(self.L.nlls_schur_apply, (int(which), float(lam)), v, n, n)
+
+    def schur_reduce(self, b, lam=0.0, which=VARS_CURRENT):
+        """nlls_schur_reduce: b_r - E (C + lam I)^-1 b_e.  b (ndof,) -> (nred,); 2-D input: one row per vector"""
+        return self._apply(self.L.nlls_schur_reduce, (int(which), float(lam)), b, self.info.ndof, self._nred())
+
+    def schur_expand(self, b, yr, lam=0.0, which=VARS_CURRENT):
+        """nlls_schur_expand: yr on the reduced entries, (C + lam I)^-1 (b_e - E' yr) on the eliminated ones: expand(b, S^-1 reduce(b)) solves (H + lam I) y = b.
+        b (ndof,), yr (nred,) -> (ndof,); 2-D inputs: one row per vector"""
+        n, nr = self.info.ndof, self._nred()
+        a = np.ascontiguousarray(b, np.float64); y = np.ascontiguousarray(yr, np.float64); one = a.ndim == 1
+        a = a.reshape(1, -1) if one else a; y = y.reshape(1, -1) if y.ndim == 1 else y
+        assert a.ndim == 2 and a.shape[1] == n and y.shape == (a.shape[0], nr), f"expected b of length {n} and yr of length {nr}, one row per vector"
+        out = np.zeros((a.shape[0], n))
+        for k0 in range(0, a.shape[0], APPLY_MAX_VEC):
+            ak = np.ascontiguousarray(a[k0:k0 + APPLY_MAX_VEC]); yk = np.ascontiguousarray(y[k0:k0 + APPLY_MAX_VEC]); ok = out[k0:k0 + APPLY_MAX_VEC]
+            self._chk(self.L.nlls_schur_expand(self.h, int(which), float(lam), ak.shape[0], _p(ak), _p(yk if yk.size else np.zeros(1)), _p(ok)))      # (nred 0: a pointer that is not null)
+        return out[0] if one else out
+
+    def solve_pcg_schur(self, precond=PCG_PRECOND_BLOCK_JACOBI, maxiters=None, rtol=1e-8, want_x=False):
+        """nlls_solve_pcg_schur: solve_pcg on the reduced system -- conjugate gradients from 0 on S yr = reduce(b), y = expand(b, yr), x = -y as the step.  precond:
+        1 / "blockjacobi" (the diagonal blocks of B + lambda I), 0 / "none"; maxiters: 4 ndof when None; rtol on the REDUCED residual.  -> (x or None, stats) with
+        solve_pcg's dictionary, bnorm and rnorm those of the reduced system.  A breakdown (status 2, 3; an eliminated block without a factor is 3) raises NllsError
+        with code ERR_NOT_SPD and leaves the step as it was; last_pcg_schur holds its stats.  An upload that eliminated nothing raises ERR_UNSUPPORTED."""
+        pc = PCG_PRECONDS[precond] if isinstance(precond, str) or precond is None else int(precond)
+        mi = max(4 * int(self.info.ndof), 1) if maxiters is None else int(maxiters)
+        out = np.zeros(self.info.ndof) if want_x else None; st = np.zeros(8)
+        rc = self.L.nlls_solve_pcg_schur(self.h, pc, mi, float(rtol), _p(out), _p(st))
+        self.last_pcg_schur = dict(iterations=int(st[0]), status=int(st[1]), bnorm=float(st[2]), rnorm=float(st[3]), rounds=int(st[4]), launches=int(st[5]))
+        self._chk(rc)
+        return out, self.last_pcg_schur
 
     @staticmethod
     def _pcg_rhs_stats(st, n):

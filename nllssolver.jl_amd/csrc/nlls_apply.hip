@@ -263,21 +263,30 @@ int apply_prepare(nlls_ctx* c) {
     X.ready = true;
     return NLLS_OK;
 }
-// the rows that take wavefronts, under the threshold the context holds now: one item per row, or per segment of APP_SEGMENT incidences of a longer row
+}  // namespace
+// The row-class rule, for the listed block rows (`blocks` null: all of them, in order): a row of `wave_min` incidences or more takes wavefronts -- one item per row, or
+// per segment of APP_SEGMENT incidences of a longer row, whose segments' sums go to consecutive slots of `part`.  The products of this file and the class-restricted
+// gathers of nlls_schur_apply.hip take their lists from here.
+void classify_rows(const nlls_ctx* c, const uint32_t* blocks, size_t n, int64_t wave_min, RowClasses& out) {
+    const ApplyIndex& X = c->app; out = RowClasses{};
+    for (size_t i = 0; i < n; ++i) { const uint32_t b = blocks ? blocks[i] : (uint32_t)i; const uint32_t p0 = X.h_rowptr[b], p1 = X.h_rowptr[b + 1];
+        if ((int64_t)(p1 - p0) < wave_min) { out.short_rows.push_back(b); continue; }
+        out.long_rows.push_back(b);
+        if (p1 - p0 <= APP_SEGMENT) { out.items.push_back(LongItem{b, p0, p1, DEST_NONE}); continue; }
+        BigRow br{b, out.nslots, 0};
+        for (uint32_t p = p0; p < p1; p += APP_SEGMENT) { out.items.push_back(LongItem{b, p, std::min(p + APP_SEGMENT, p1), out.nslots++}); ++br.nslots; }
+        out.big.push_back(br); out.part_w_vec = std::max(out.part_w_vec, (int)c->blocksizes[b]); out.part_w_diag = std::max(out.part_w_diag, (int)c->blocksizes[b] * (int)c->blocksizes[b]); }
+}
+namespace {
+// the rows that take wavefronts, under the threshold the context holds now
 int apply_classify(nlls_ctx* c) {
     ApplyIndex& X = c->app;
     const int64_t wm = std::max<int64_t>(c->app_wave_min, 1);
     if (X.wave_min_built == wm) return NLLS_OK;
-    std::vector<LongItem> items; std::vector<BigRow> big; int64_t nlong = 0; uint32_t nslots = 0; int wv = 1, wd = 1;
-    for (size_t b = 0; b + 1 < X.h_rowptr.size(); ++b) { const uint32_t p0 = X.h_rowptr[b], p1 = X.h_rowptr[b + 1];
-        if ((int64_t)(p1 - p0) < wm) continue;
-        ++nlong;
-        if (p1 - p0 <= APP_SEGMENT) { items.push_back(LongItem{(uint32_t)b, p0, p1, DEST_NONE}); continue; }
-        BigRow br{(uint32_t)b, nslots, 0};
-        for (uint32_t p = p0; p < p1; p += APP_SEGMENT) { items.push_back(LongItem{(uint32_t)b, p, std::min(p + APP_SEGMENT, p1), nslots++}); ++br.nslots; }
-        big.push_back(br); wv = std::max(wv, (int)c->blocksizes[b]); wd = std::max(wd, (int)c->blocksizes[b] * (int)c->blocksizes[b]); }
-    HIPCHK(X.long_items.upload(items)); HIPCHK(X.big_rows.upload(big));
-    X.nlong = nlong; X.nitems = (int64_t)items.size(); X.nbig = (int64_t)big.size(); X.nslots = nslots; X.part_w_vec = wv; X.part_w_diag = wd; X.wave_min_built = wm;
+    RowClasses R; classify_rows(c, nullptr, X.h_rowptr.size() - 1, wm, R);
+    HIPCHK(X.long_items.upload(R.items)); HIPCHK(X.big_rows.upload(R.big));
+    X.nlong = (int64_t)R.long_rows.size(); X.nitems = (int64_t)R.items.size(); X.nbig = (int64_t)R.big.size(); X.nslots = R.nslots; X.part_w_vec = R.part_w_vec; X.part_w_diag = R.part_w_diag;
+    X.wave_min_built = wm;
     return NLLS_OK;
 }
 int apply_scratch(nlls_ctx* c, int64_t per_vec, int nvec, int& chunk) {
@@ -289,14 +298,14 @@ int apply_scratch(nlls_ctx* c, int64_t per_vec, int nvec, int& chunk) {
     return NLLS_OK;
 }
 template <int MODE>
-int launch_blocks(nlls_ctx* c, size_t g, int which, int nvec, const double* in, int64_t in_stride, double* out, int64_t out_stride) {
+int launch_blocks(nlls_ctx* c, size_t g, int which, int nvec, const double* in, int64_t in_stride, double* out, int64_t out_stride, const uint32_t* boff = nullptr) {      // boff: a table of the caller's (nlls_schur_apply.hip) in place of ApplyIndex::boff
     const Group& G = c->groups[g];
     if (G.ncost <= 0) return NLLS_OK;
     const double* vars = vars_ptr(c, which);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((G.ncost + TPB - 1) / TPB, 2048));
     const bool known = dispatch_res(G.res_kind, [&](auto k) {
         if constexpr (is_cost_kind<k()> && (MODE == APP_JAC || MODE == APP_JACT)) return false;
-        else { hipLaunchKernelGGL((apply_blocks_kernel<k(), MODE>), dim3(grid), dim3(TPB), 0, c->stream, vars, G.data.p, G.voff.p, c->app.boff[g].p, G.ncost, G.rk, nvec, in, in_stride, out, out_stride);
+        else { hipLaunchKernelGGL((apply_blocks_kernel<k(), MODE>), dim3(grid), dim3(TPB), 0, c->stream, vars, G.data.p, G.voff.p, boff ? boff : c->app.boff[g].p, G.ncost, G.rk, nvec, in, in_stride, out, out_stride);
                return true; } }, false);
     if (!known) { c->err = "matrix-free products: no kernel for this residual kind"; return NLLS_ERR_UNSUPPORTED; }
     HIPCHK(hipGetLastError());
@@ -353,6 +362,20 @@ int enqueue_hess_apply(nlls_ctx* c, int which, double lambda, int nvec, const do
     ph.close(8.0 * (double)nvec * (double)(X.rec_vec + ndof));
     c->app_short = (int64_t)c->blocksizes.size() - X.nlong; c->app_long = X.nlong; c->app_chunks = nchunks;
     return NLLS_OK;
+}
+// what the products with the Schur complement (nlls_schur_apply.hip) share with this file: the index and its row classes, the record scratch (nvec cut into chunks of
+// `chunk` under nlls_ctx::app_scratch_cap), and the block launch of one group on a table of the caller's
+int apply_index(nlls_ctx* c) { const int rc = apply_prepare(c); return rc != NLLS_OK ? rc : apply_classify(c); }
+int apply_records(nlls_ctx* c, int nvec, int& chunk) { return apply_scratch(c, c->app.rec_vec, nvec, chunk); }
+// the diagonal-block records of every group at vars[which] into ApplyIndex::rec (one "vector" of rec_diag doubles): enqueue_hess_block_diag without its gather
+int enqueue_diag_blocks(nlls_ctx* c, int which) {
+    ApplyIndex& X = c->app; int chunk = 1;
+    int rc = apply_scratch(c, X.rec_diag, 1, chunk); if (rc != NLLS_OK) return rc;
+    for (size_t g = 0; g < c->groups.size(); ++g) { rc = launch_blocks<APP_DIAG>(c, g, which, 1, nullptr, 0, X.rec.p + X.gbase_diag[g], X.rec_diag); if (rc != NLLS_OK) return rc; }
+    return NLLS_OK;
+}
+int enqueue_hess_blocks(nlls_ctx* c, size_t g, int which, int nvec, const uint32_t* boff, const double* d_in, int64_t in_stride) {
+    return launch_blocks<APP_HESS>(c, g, which, nvec, d_in, in_stride, c->app.rec.p + c->app.gbase_vec[g], c->app.rec_vec, boff);
 }
 int enqueue_jac_apply(nlls_ctx* c, int which, int group, int nvec, const double* d_v, double* d_u) {
     const int64_t ndof = c->info.ndof;

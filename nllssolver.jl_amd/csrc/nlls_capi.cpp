@@ -575,6 +575,75 @@ int nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel,
     return pcg_solve_cols(ctx, PcgCall{.name = "nlls_marginal_cov", .which = which, .lambda = lambda, .precond = precond, .maxiters = maxiters, .rtol = rtol, .ncols = m, .rows = rows.data(), .out = cov_out}, stats_out);
     NLLS_API_END(ctx)
 }
+// ---- the reduced system, matrix-free (nlls_schur_apply.hip) ------------------------------------------------------------------------------------------
+// The three products: everything is refused before anything is built or enqueued; then the r/e index, the caller's vectors into SchurIndex::io, the e blocks' inverses,
+// the product; the factor's status comes home first, and only a call whose blocks all have a factor copies a result out.  Read only: no event of nlls_state.hpp.
+static int schur_product(nlls_ctx* ctx, const char* name, int mode, int32_t which, double lambda, int32_t nvec, const double* a, const double* yr, double* out) {
+    const std::string nm(name);
+    if (!valid_set(which) || nvec < 1 || nvec > NLLS_APPLY_MAX_VEC || !std::isfinite(lambda)) return fail(ctx, NLLS_ERR_INVALID_ARG, nm + ": bad variable set, nvec or lambda");
+    TRY(schur_check(ctx, name));
+    TRY(schur_prepare(ctx));
+    SchurIndex& Z = ctx->sch;
+    const size_t nf = (size_t)nvec * (size_t)ctx->info.ndof, nr = (size_t)nvec * (size_t)Z.nred;
+    const size_t na = mode == SCHUR_APPLY ? nr : nf, ny = mode == SCHUR_EXPAND ? nr : 0, no = mode == SCHUR_EXPAND ? nf : nr, nd = (size_t)std::max<int64_t>(apply_diag_len(ctx), 1);
+    if (no == 0) return NLLS_OK;            // (every unfixed block eliminated: a reduced vector has no entry, nlls_schur_apply and nlls_schur_reduce have nothing to write)
+    auto need = [&](DevBuf<double>& buf, size_t n, const char* what) -> int {
+        if (buf.n >= n && buf.p) return NLLS_OK;
+        const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(ctx, e, (nm + ": " + what).c_str()); }
+        return NLLS_OK; };
+    TRY(need(Z.io, std::max<size_t>(na + ny + no, 1), "staging for the vectors")); TRY(need(Z.Cinv, nd, "the eliminated blocks' inverses")); TRY(need(Z.scal, PCG_NSCAL, "the factor's status"));
+    double* const io = Z.io.p; double st[PCG_NSCAL] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(ctx, hipMemsetAsync(Z.scal.p, 0, sizeof(double) * PCG_NSCAL, ctx->stream));
+    if (na) HIP_TRY(ctx, hipMemcpyAsync(io, a, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
+    if (ny) HIP_TRY(ctx, hipMemcpyAsync(io + na, yr, sizeof(double) * ny, hipMemcpyHostToDevice, ctx->stream));
+    TRY(enqueue_schur_setup(ctx, which, lambda, false, Z.Cinv.p, Z.scal.p, nullptr));
+    TRY(enqueue_schur_op(ctx, mode, which, lambda, Z.Cinv.p, nvec, io, io + na, io + na + ny));
+    HIP_TRY(ctx, hipMemcpyAsync(st, Z.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (st[PCG_STATUS] != 0.0) return fail(ctx, NLLS_ERR_NOT_SPD, nm + ": an eliminated block C_e + lambda I is not positive definite");
+    if (no) HIP_TRY(ctx, hipMemcpyAsync(out, io + na + ny, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
+}
+int nlls_schur_info(const nlls_ctx* ctx, int64_t* nred_out, int64_t* nelim_out, uint8_t* is_elim_out) { NLLS_API_BEGIN
+    if (!ctx) return NLLS_ERR_INVALID_ARG;
+    if (!ctx->ready) return NLLS_ERR_NOT_READY;
+    const size_t nb = ctx->blocksizes.size(); const bool have = ctx->is_elim.size() == nb;
+    int64_t nred = 0, nelim = 0;
+    for (size_t b = 0; b < nb; ++b) { const bool e = have && ctx->is_elim[b]; if (e) ++nelim; else nred += ctx->blocksizes[b]; if (is_elim_out) is_elim_out[b] = e ? 1 : 0; }
+    if (nred_out) *nred_out = nred;
+    if (nelim_out) *nelim_out = nelim;
+    return NLLS_OK;
+    NLLS_API_END(const_cast<nlls_ctx*>(ctx))
+}
+int nlls_schur_apply(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* v, double* y_out) { NLLS_API_BEGIN
+    if (!ctx || !v || !y_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    return schur_product(ctx, "nlls_schur_apply", SCHUR_APPLY, which, lambda, nvec, v, nullptr, y_out);
+    NLLS_API_END(ctx)
+}
+int nlls_schur_reduce(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* b, double* s_out) { NLLS_API_BEGIN
+    if (!ctx || !b || !s_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    return schur_product(ctx, "nlls_schur_reduce", SCHUR_REDUCE, which, lambda, nvec, b, nullptr, s_out);
+    NLLS_API_END(ctx)
+}
+int nlls_schur_expand(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* b, const double* yr, double* y_out) { NLLS_API_BEGIN
+    if (!ctx || !b || !yr || !y_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    return schur_product(ctx, "nlls_schur_expand", SCHUR_EXPAND, which, lambda, nvec, b, yr, y_out);
+    NLLS_API_END(ctx)
+}
+// nlls_solve_pcg on the reduced system: refused as it refuses, and where nothing was eliminated; the transition nlls_set_step makes on success (inside pcg_solve_schur)
+int nlls_solve_pcg_schur(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out) { NLLS_API_BEGIN
+    if (!ctx) return NLLS_ERR_INVALID_ARG;
+    if (!pcg_iteration_args_ok(precond, maxiters, rtol)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg_schur: bad preconditioner, maxiters or rtol");
+    NEED_GRAD_LAZY();
+    TRY(schur_check(ctx, "nlls_solve_pcg_schur"));
+    TRY(ensure_grad(ctx, 2)); TRY(ensure_reduced_summed(ctx));      // (b as nlls_get_grad reads it)
+    return pcg_solve_schur(ctx, precond, maxiters, rtol, x_out, stats_out);
+    NLLS_API_END(ctx)
+}
 // One Levenberg-Marquardt trial in one call and one synchronisation (src/iterators.jl:149-157): uniformscaling!(H, dlambda),
 // solve!, negate!, update!(to, from, x), cost(to).  Same kernels, same order as the separate entry points.
 int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, double* cost_out) { NLLS_API_BEGIN

@@ -228,6 +228,31 @@ struct ApplyIndex {
     uint32_t nslots = 0; int part_w_vec = 1, part_w_diag = 1;      // segments of all cut rows; widest cut row (unknowns; entries of its diagonal block)
 };
 
+// ---- products with the Schur complement of the upload's eliminated set (nlls_schur_apply.hip): S v, reduce, expand; nlls_solve_pcg_schur --------------------
+// Two row classes over the unfixed blocks: r (0, not eliminated) and e (1, nlls_ctx::is_elim), each in ascending block order.  A vector of the PERMUTED layout holds the
+// r blocks' entries first (the reduced layout, nred doubles), then the e blocks'; cstart[b] is where block b starts in it.  A product is the block launch of
+// nlls_apply.hip twice, with tables of its own that say where a slot's variable lies in the launch's input (boff1: the reduced layout, e and fixed slots absent; boff2: the
+// permuted layout), and gathers over ONE class each: item lists per class, so that no lane is launched for a row the pass does not write.  Built at the first call after
+// an upload, dropped by the next; the item lists again when NLLS_OPT_APPLY_WAVE_MIN changes.  Everything lies outside the hot arena.
+struct ShortElem { uint32_t row, q; };             // entry q of block row `row`
+struct SchurClass {
+    int64_t nblk = 0, ndof = 0;
+    DevBuf<int32_t> bsz; DevBuf<uint32_t> dstart;  // per block of the class: its dof, where its diagonal block starts in nlls_hess_block_diag's layout (the factor launch takes them)
+    std::vector<uint32_t> blocks;                  // the class's blocks
+    DevBuf<ShortElem> shorts, longel, dshorts;     // the entries of its rows gathered one lane each / of its rows that take wavefronts / of the short rows' diagonal blocks
+    DevBuf<LongItem> items; DevBuf<BigRow> big;
+    int64_t nshort = 0, nlongel = 0, ndshort = 0, nitems = 0, nbig = 0, nlong = 0; uint32_t nslots = 0; int part_w = 1, part_w_diag = 1;
+};
+struct SchurIndex {
+    bool ready = false; int64_t nred = 0, nedof = 0, wave_min_built = -1;
+    std::vector<DevBuf<uint32_t>> boff1, boff2;    // per cost group [ncost][ndeps]
+    DevBuf<uint32_t> cstart, erow_r;               // per block: its start in the permuted layout; per reduced unknown: its block (PcgArgs::erow)
+    SchurClass cls[2];
+    DevBuf<double> z, t, part;                     // per chunk of vectors, permuted layout: [v | w]; the sums of the e rows that take wavefronts; the cut rows' partial sums
+    DevBuf<double> Cinv, scal, io, sred, full;     // the ABI bodies' inverses, factor status and staging; nlls_solve_pcg_schur's reduced right-hand side and expanded solution
+    int64_t launches = 0;                          // of the last product, all its chunks
+};
+
 // ---- block-Jacobi conjugate gradients on the device (nlls_pcg.hip): nlls_solve_pcg, nlls_solve_pcg_rhs, nlls_marginal_cov ------------------------------------
 // ONE set of buffers of the solver's own for the three of them, outside the hot arena: grown on demand by the driver (pcg_solve_cols), dropped by the next upload.  Up to
 // NLLS_APPLY_MAX_VEC columns iterate together; a call lays the buffers out by its own cap = min(columns, NLLS_APPLY_MAX_VEC), nlls_solve_pcg's is 1.
@@ -442,4 +467,6 @@ struct nlls_ctx {
     int64_t pcg_round = 1, pcg_grid_max = 1024;      // (the round length with the smallest wall time on ba_1kx100k: notes/r18.md)
     int64_t pcg_iters = 0, pcg_status = 0, pcg_rounds = 0;
     bool pcg_pending = false; double pcg_ms = 0.0;
+    // nlls_schur_apply / _reduce / _expand / nlls_solve_pcg_schur (nlls_schur_apply.hip): the r/e index of the reduced layout and the products' buffers
+    nlls::SchurIndex sch;
 };

@@ -90,9 +90,33 @@ struct PcgCall {
     int64_t ncols;
     const double* d_b = nullptr; const double* B = nullptr; const int64_t* rows = nullptr; double* out = nullptr;
     bool look_first = true;                // the first look at the stop flags before the first product (a zero column, a missing factor pay for none) or behind the first round (one synchronisation less)
+    bool schur = false;                    // the operator is S(lambda) of the upload's eliminated set, the vectors have nred entries (d_b only: reduced on the device, the solution expanded there)
 };
 // NLLS_ERR_NOT_SPD: a column broke down (the error text names the first one).  stats: 4 * ncols + 4 doubles (may be null)
 int pcg_solve_cols(nlls_ctx* c, const PcgCall& call, double* stats);
+// nlls_solve_pcg_schur: the driver on one column of the reduced system; what pcg_solve does around it, without the phase events and the counters of nlls_get_solve_stats
+int pcg_solve_schur(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats);
+// Cholesky and inverse, in place, of n diagonal blocks listed by dof and start (nlls_pcg.hip, pcg_factor_kernel): a block without a factor leaves status 3 and the stop flag in scal
+int enqueue_block_factor(nlls_ctx* c, const int32_t* d_bsz, const uint32_t* d_dstart, int64_t n, double* d_blocks, double* d_scal);
+// what nlls_schur_apply.hip takes from nlls_apply.hip: the index with its row classes, the record scratch for nvec vectors (cut into chunks of `chunk`), the block launch of
+// group g on a table of the caller's (where each slot's variable starts in d_in; DEST_NONE: its entries count as 0), records into ApplyIndex::rec
+int apply_index(nlls_ctx* c);
+struct RowClasses { std::vector<uint32_t> short_rows, long_rows; std::vector<LongItem> items; std::vector<BigRow> big; uint32_t nslots = 0; int part_w_vec = 1, part_w_diag = 1; };
+void classify_rows(const nlls_ctx* c, const uint32_t* blocks /* null: all */, size_t n, int64_t wave_min, RowClasses& out);      // the row-class rule of the gathers (needs apply_index)
+int enqueue_diag_blocks(nlls_ctx* c, int which);      // every group's diagonal-block records into ApplyIndex::rec, no gather
+int apply_records(nlls_ctx* c, int nvec, int& chunk);
+int enqueue_hess_blocks(nlls_ctx* c, size_t g, int which, int nvec, const uint32_t* boff, const double* d_in, int64_t in_stride);
+// products with S(lambda) = B + lambda I - E (C + lambda I)^-1 E' over the upload's eliminated set (nlls_schur_apply.hip): device pointers, on c->stream, no synchronisation.
+// schur_check: NLLS_OK, or the status with nlls_last_error set (what apply_check refuses; nothing eliminated).  schur_prepare builds the r/e index.  enqueue_schur_setup
+// leaves the inverses of the e blocks of H + lambda I (with_r: of the r blocks too) in d_Minv, nlls_hess_block_diag's layout, and status 3 in d_scal where one has no factor.
+enum { SCHUR_APPLY = 0, SCHUR_REDUCE = 1, SCHUR_EXPAND = 2 };
+int schur_check(nlls_ctx* c, const char* name);
+int schur_prepare(nlls_ctx* c);
+int enqueue_schur_setup(nlls_ctx* c, int which, double lambda, bool with_r, double* d_Minv, double* d_scal, int64_t* launches);
+//   SCHUR_APPLY   a = v (nvec x nred)                       out = S v (nvec x nred)
+//   SCHUR_REDUCE  a = b (nvec x ndof)                       out = b_r - E (C + lambda I)^-1 b_e (nvec x nred)
+//   SCHUR_EXPAND  a = b (nvec x ndof), yr (nvec x nred)     out (nvec x ndof): yr on the r entries, (C + lambda I)^-1 (b_e - E' yr) on the e entries
+int enqueue_schur_op(nlls_ctx* c, int mode, int which, double lambda, const double* d_Minv, int nvec, const double* d_a, const double* d_yr, double* d_out);
 int enqueue_update_scatter(nlls_ctx* c, Group& G, int64_t n, bool indexed);   // (nlls_update.hip) nlls_set_cost_data: c->upd_stage (blocks c->upd_index) -> every copy of the group's payload
 size_t singles_group_size();
 void singles_group_fill(void* dst, const Group& G);

@@ -210,20 +210,22 @@ int64_t product_launches(const nlls_ctx* c) {
 // The driver of the three entry points: the only place that allocates, launches and loops.  The caller has checked the arguments.  stats: 4 * ncols + 4 doubles (may be null)
 int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     constexpr int MAXC = NLLS_APPLY_MAX_VEC;
-    const int64_t ndof = c->info.ndof, ncols = k.ncols; const int maxiters = k.maxiters; const bool jacobi = k.precond == NLLS_PCG_PRECOND_BLOCK_JACOBI; const std::string nm(k.name);
+    const int64_t ndof = k.schur ? c->sch.nred : c->info.ndof, ncols = k.ncols; const int maxiters = k.maxiters; const bool jacobi = k.precond == NLLS_PCG_PRECOND_BLOCK_JACOBI; const std::string nm(k.name);
     const double* const B = k.B; const bool step = k.d_b != nullptr, units = k.rows != nullptr;
     PcgState& S = c->pcg; const int cap = (int)std::min<int64_t>(ncols, MAXC);
     auto need = [&](auto& buf, size_t n, const char* what) -> int {
         if (buf.n >= n && buf.p) return NLLS_OK;
         const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(c, e, (nm + ": " + what).c_str()); }
         return NLLS_OK; };
-    S.pw = (ndof + TPB - 1) / TPB;
+    S.pw = std::max<int64_t>((ndof + TPB - 1) / TPB, 1);      // (at least one workgroup and one partial: the vector kernels store theirs unconditionally)
     int rc = need(S.vec, (size_t)(6 * cap * ndof), "the vectors"); if (rc != NLLS_OK) return rc;
     rc = need(S.part, (size_t)(3 * S.pw * cap), "the partial sums"); if (rc != NLLS_OK) return rc;
     rc = need(S.scal, (size_t)((MAXC + 1) * PCG_NSCAL), "the scalars"); if (rc != NLLS_OK) return rc;
     rc = need(S.h_scal, (size_t)(MAXC * PCG_NSCAL), "the pinned mirror of the scalars"); if (rc != NLLS_OK) return rc;
     if (!step) { rc = need(S.io, (size_t)((B ? ncols : (int64_t)cap) * ndof), "the columns"); if (rc != NLLS_OK) return rc; }
-    if (jacobi) { rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "the preconditioner's blocks"); if (rc != NLLS_OK) return rc; }
+    if (jacobi || k.schur) { rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "the preconditioner's blocks"); if (rc != NLLS_OK) return rc; }
+    if (k.schur) { rc = need(c->sch.sred, (size_t)ndof, "the reduced right-hand side"); if (rc != NLLS_OK) return rc;
+                   rc = need(c->sch.full, (size_t)c->info.ndof, "the expanded solution"); if (rc != NLLS_OK) return rc; }
     if (units) { rc = need(S.rows, (size_t)ncols, "the selected unknowns"); if (rc != NLLS_OK) return rc;
                  rc = need(S.cov, (size_t)(ncols * ncols), "the covariance block"); if (rc != NLLS_OK) return rc; }
     const int64_t vs = (int64_t)cap * ndof;      // doubles of one of the six arrays: the layout is this call's, whatever an earlier call left in the buffers
@@ -238,7 +240,14 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = k.rtol * k.rtol;
     a.Minv = S.Minv.p; a.y = y; a.r_old = r[1]; a.r_new = r[0]; a.z = z; a.p = p; a.q = q;
     a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.pstride = 3 * S.pw; a.scal = S.scal.p;
-    if (jacobi) {       // the preconditioner: once per call, whatever the number of batches (Minv is this call's: an earlier one left it at its own lambda)
+    const double* rhs = k.d_b;
+    if (k.schur) {      // the reduced system (the caller has built its index: schur_prepare): the e blocks' inverses -- the operator needs them under either preconditioner -- the
+                        // r blocks' under block Jacobi, the reduced layout for the vector kernels, and s = reduce(b) as the one right-hand side
+        rc = enqueue_schur_setup(c, k.which, k.lambda, jacobi, S.Minv.p, fscal, &launches); if (rc != NLLS_OK) return rc;
+        a.erow = c->sch.erow_r.p; a.start = c->sch.cstart.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;
+        rc = enqueue_schur_op(c, SCHUR_REDUCE, k.which, k.lambda, S.Minv.p, 1, k.d_b, nullptr, c->sch.sred.p); if (rc != NLLS_OK) return rc; launches += c->sch.launches;
+        rhs = c->sch.sred.p;
+    } else if (jacobi) {       // the preconditioner: once per call, whatever the number of batches (Minv is this call's: an earlier one left it at its own lambda)
         rc = enqueue_hess_block_diag(c, k.which, k.lambda, S.Minv.p); if (rc != NLLS_OK) return rc; launches += product_launches(c);
         a.erow = c->app.erow_vec.p; a.start = c->app.start_vec.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;       // (the index of the products exists: enqueue_hess_block_diag built it)
         PcgArgs f = a; f.scal = fscal;
@@ -251,7 +260,7 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
         if (B) HIPCHK(hipMemcpyAsync(bio, B + j0 * ndof, sizeof(double) * (size_t)(nb * ndof), hipMemcpyHostToDevice, c->stream));
         if (units) { hipLaunchKernelGGL(pcg_unit_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, bio, ndof, S.rows.p + j0); ++launches; }
         hipLaunchKernelGGL(pcg_cols_begin_kernel, dim3(1), dim3(TPB), 0, c->stream, fscal, S.scal.p, nb);
-        a.b = step ? k.d_b : bio; a.cols = 0x76543210u; a.parity = 0; a.r_old = r[1]; a.r_new = r[0];
+        a.b = step ? rhs : bio; a.cols = 0x76543210u; a.parity = 0; a.r_old = r[1]; a.r_new = r[0];
         hipLaunchKernelGGL(pcg_init_kernel, dim3(grid, nb), dim3(TPB), 0, c->stream, a);
         hipLaunchKernelGGL(pcg_start_kernel, dim3(1, nb), dim3(TPB), 0, c->stream, a); launches += 3;
         HIPCHK(hipGetLastError());
@@ -291,11 +300,12 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
             a.cols = 0; for (int s = 0; s < active; ++s) a.cols |= (uint32_t)slot_col[s] << (4 * s);
             for (int64_t i = 0; i < n; ++i, ++it) {
                 a.parity = (int)(it & 1); a.r_old = r[it & 1]; a.r_new = r[(it + 1) & 1];
-                rc = enqueue_hess_apply(c, k.which, k.lambda, active, p, q); if (rc != NLLS_OK) return rc;
+                rc = k.schur ? enqueue_schur_op(c, SCHUR_APPLY, k.which, k.lambda, S.Minv.p, active, p, nullptr, q) : enqueue_hess_apply(c, k.which, k.lambda, active, p, q);
+                if (rc != NLLS_OK) return rc;
                 hipLaunchKernelGGL(pcg_dot_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
                 hipLaunchKernelGGL(pcg_step_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
                 hipLaunchKernelGGL(pcg_dir_kernel, dim3(grid, active), dim3(TPB), 0, c->stream, a);
-                launches += product_launches(c) + 3; products += active;
+                launches += (k.schur ? c->sch.launches : product_launches(c)) + 3; products += active;
             }
             HIPCHK(hipGetLastError());
         }
@@ -304,7 +314,10 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     }
     if (bad_status == 3) for (int64_t j = 0; j < ncols; ++j) { st[4 * j] = 0.0; st[4 * j + 1] = 3.0; st[4 * j + 2] = 0.0; st[4 * j + 3] = 0.0; }   // call-wide: no column started
     if (!bad) {         // every column of the call has ended well: only now does a result leave the solver's own buffers
-        if (step) { hipLaunchKernelGGL(pcg_finish_kernel, dim3(grid), dim3(TPB), 0, c->stream, y, c->x.p, ndof); ++launches; HIPCHK(hipGetLastError()); }      // (pcg_solve waits for it)
+        const double* yfull = y;
+        if (k.schur) { rc = enqueue_schur_op(c, SCHUR_EXPAND, k.which, k.lambda, S.Minv.p, 1, k.d_b, y, c->sch.full.p); if (rc != NLLS_OK) return rc; launches += c->sch.launches; yfull = c->sch.full.p; }
+        const int fgrid = (int)std::max<int64_t>(1, std::min<int64_t>((c->info.ndof + TPB - 1) / TPB, std::max<int64_t>(c->pcg_grid_max, 1)));      // (the step has ndof entries on either path)
+        if (step) { hipLaunchKernelGGL(pcg_finish_kernel, dim3(fgrid), dim3(TPB), 0, c->stream, yfull, c->x.p, c->info.ndof); ++launches; HIPCHK(hipGetLastError()); }      // (pcg_solve waits for it)
         else {
             // (a batch at a time, as the right-hand sides came: one copy of 16 columns of ba_1kx100k into pageable memory took longer than two of 8, notes/r19.md)
             if (B) { for (int64_t j0 = 0; j0 < ncols; j0 += MAXC) { const int64_t nb = std::min<int64_t>(MAXC, ncols - j0);
@@ -317,10 +330,20 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     tail[0] = (double)syncs; tail[1] = (double)launches; tail[2] = (double)products; tail[3] = (double)batches;
     if (stats) std::copy(st.begin(), st.end(), stats);
     if (bad) {
-        c->err = bad_status == 3 ? nm + ": a diagonal block of H + lambda I is not positive definite (status 3)"
+        c->err = bad_status == 3 ? nm + (k.schur ? ": an eliminated block C_e + lambda I -- or, under block Jacobi, a diagonal block of B + lambda I -- is not positive definite (status 3)"
+                                                 : ": a diagonal block of H + lambda I is not positive definite (status 3)")
                                  : nm + ": p'(H + lambda I)p is not positive, or a scalar of the recurrence is not finite (status 2, column " + std::to_string(bad_col) + ")";
         return NLLS_ERR_NOT_SPD;
     }
+    return NLLS_OK;
+}
+
+// the factor launch on a list of blocks of the caller's (nlls_schur_apply.hip: one row class of the reduced layout)
+int enqueue_block_factor(nlls_ctx* c, const int32_t* d_bsz, const uint32_t* d_dstart, int64_t n, double* d_blocks, double* d_scal) {
+    if (n <= 0) return NLLS_OK;
+    PcgArgs f{}; f.nblocks = n; f.bsz = d_bsz; f.dstart = d_dstart; f.scal = d_scal;
+    hipLaunchKernelGGL(pcg_factor_kernel, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, f, d_blocks);
+    HIPCHK(hipGetLastError());
     return NLLS_OK;
 }
 
@@ -349,5 +372,53 @@ int pcg_solve(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out
     return NLLS_OK;
 }
 
-}  // namespace nlls
+// Every unfixed block is eliminated (a bundle adjustment with all cameras fixed): the reduced system has no unknown, there is nothing to iterate on, and the step is
+// x = -expand(b, []) = -(C + lambda I)^-1 b -- status 0, no iteration; an eliminated block without a factor is status 3 as elsewhere, the step untouched
+static int pcg_solve_schur_empty(nlls_ctx* c, double* x_out, double* stats) {
+    PcgState& S = c->pcg; const int64_t ndof = c->info.ndof; double st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, h[PCG_NSCAL]; int64_t launches = 0;
+    auto need = [&](DevBuf<double>& buf, size_t n, const char* what) -> int {
+        if (buf.n >= n && buf.p) return NLLS_OK;
+        const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(c, e, what); }
+        return NLLS_OK; };
+    int rc = need(S.Minv, (size_t)std::max<int64_t>(apply_diag_len(c), 1), "nlls_solve_pcg_schur: the eliminated blocks' inverses"); if (rc != NLLS_OK) return rc;
+    rc = need(S.scal, (size_t)((NLLS_APPLY_MAX_VEC + 1) * PCG_NSCAL), "nlls_solve_pcg_schur: the scalars"); if (rc != NLLS_OK) return rc;
+    rc = need(c->sch.full, (size_t)ndof, "nlls_solve_pcg_schur: the expanded solution"); if (rc != NLLS_OK) return rc;
+    HIPCHK(hipMemsetAsync(S.scal.p, 0, sizeof(double) * PCG_NSCAL, c->stream));
+    rc = enqueue_schur_setup(c, NLLS_VARS_CURRENT, c->lambda, false, S.Minv.p, S.scal.p, &launches); if (rc != NLLS_OK) return rc;
+    rc = enqueue_schur_op(c, SCHUR_EXPAND, NLLS_VARS_CURRENT, c->lambda, S.Minv.p, 1, c->b.p, nullptr, c->sch.full.p); if (rc != NLLS_OK) return rc; launches += c->sch.launches;
+    HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    st[4] = 1.0; st[5] = (double)launches;
+    if (h[PCG_STATUS] != 0.0) { st[1] = 3.0; if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
+        c->err = "nlls_solve_pcg_schur: an eliminated block C_e + lambda I is not positive definite (status 3)"; return NLLS_ERR_NOT_SPD; }
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ndof + TPB - 1) / TPB, std::max<int64_t>(c->pcg_grid_max, 1)));
+    hipLaunchKernelGGL(pcg_finish_kernel, dim3(grid), dim3(TPB), 0, c->stream, c->sch.full.p, c->x.p, ndof); HIPCHK(hipGetLastError());
+    step_replaced(c);
+    if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    st[4] = 2.0; st[5] = (double)(launches + 1);
+    if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
+    return NLLS_OK;
+}
 
+// nlls_solve_pcg_schur: the same column on the reduced system -- S yr = reduce(b) from 0, y = expand(b, yr), x = -y -- with pcg_solve's transitions and none of its
+// counters or phase events: nlls_get_solve_stats [53..55] and nlls_get_phase_times [14] keep describing the last nlls_solve_pcg
+int pcg_solve_schur(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats) {
+    double st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cs[8];
+    int rc = schur_prepare(c); if (rc != NLLS_OK) return rc;
+    if (c->sch.nred == 0) return pcg_solve_schur_empty(c, x_out, stats);
+    rc = pcg_solve_cols(c, PcgCall{.name = "nlls_solve_pcg_schur", .which = NLLS_VARS_CURRENT, .lambda = c->lambda, .precond = precond, .maxiters = maxiters, .rtol = rtol,
+                                   .ncols = 1, .d_b = c->b.p, .look_first = false, .schur = true}, cs);
+    if (rc != NLLS_OK && rc != NLLS_ERR_NOT_SPD) return rc;
+    for (int i = 0; i < 6; ++i) st[i] = cs[i];
+    if (rc == NLLS_OK) {
+        step_replaced(c);
+        if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)c->info.ndof, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        st[4] += 1.0;
+    }
+    if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
+    return rc;
+}
+
+}  // namespace nlls

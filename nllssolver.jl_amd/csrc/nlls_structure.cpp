@@ -208,7 +208,7 @@ int build_structure(nlls_ctx* c, int64_t nvar, const int32_t* var_kind, const in
     c->n_tiles_light = c->n_tiles_image = c->n_tiles_direct = c->n_tiles_partial = c->n_fold_groups = c->sweep_fused_groups = 0;
     { std::vector<HotItem> v; hot_set(c, v); for (HotItem& it : v) if (!*it.owned) { *it.pp = nullptr; *it.owned = true; } }   // what lived in the previous upload's arena is gone with it
     c->arena.release(); c->arena_pre.release();     // ... so release it NOW: a re-upload would otherwise hold two arenas (and every buffer once more) at its peak
-    c->groups.clear(); c->app = ApplyIndex{}; c->pcg = PcgState{};         // (the products' index is built again at their first call: nlls_apply.hip)
+    c->groups.clear(); c->app = ApplyIndex{}; c->pcg = PcgState{}; c->sch = SchurIndex{};         // (the products' index is built again at their first call: nlls_apply.hip)
     // ---- variables ------------------------------------------------------------------------------
     c->var_kind.assign(var_kind, var_kind + nvar); c->var_dim.assign(var_dim, var_dim + nvar);
     c->var_off.assign(nvar + 1, 0);

@@ -22,11 +22,12 @@ def _timed(data, field, fn):
 class PCG:
     """NLLSOptions(linearsolver=PCG(...)): the iterators' linear solves by conjugate gradients on the device's matrix-free operator (nlls_solve_pcg) where they
     factor by default -- no reduced system, and with `maxiters` small a truncated-Newton step.  precond: "blockjacobi" (the diagonal blocks of H + lambda I) or "none";
-    maxiters None: 4 ndof.  A breakdown (the system is not positive definite) is what a bad pivot is to the direct solve: Levenberg-Marquardt damps more."""
+    maxiters None: 4 ndof.  schur=True: the same on the reduced system of the upload's eliminated set (nlls_solve_pcg_schur; "blockjacobi" is then the diagonal blocks of
+    B + lambda I, rtol bounds the reduced residual); a problem without an eliminated set raises NllsError (ERR_UNSUPPORTED), it does not fall back.  A breakdown (the system is not positive definite) is what a bad pivot is to the direct solve: Levenberg-Marquardt damps more."""
 
-    def __init__(self, rtol=1e-8, maxiters=None, precond="blockjacobi"):
+    def __init__(self, rtol=1e-8, maxiters=None, precond="blockjacobi", schur=False):
         assert precond in ("blockjacobi", "none") and rtol >= 0 and (maxiters is None or maxiters >= 1)
-        self.rtol, self.maxiters, self.precond = float(rtol), maxiters, precond
+        self.rtol, self.maxiters, self.precond, self.schur = float(rtol), maxiters, precond, bool(schur)
 
 
 def _solve(ls, options):
@@ -34,6 +35,8 @@ def _solve(ls, options):
     pcg = getattr(options, "linearsolver", None)
     if pcg is None:
         return ls.solve()
+    if getattr(pcg, "schur", False):
+        return ls.solve_pcg_schur(pcg.precond, pcg.maxiters, pcg.rtol)
     return ls.solve_pcg(pcg.precond, pcg.maxiters, pcg.rtol)
 
 

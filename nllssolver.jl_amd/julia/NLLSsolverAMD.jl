@@ -202,6 +202,30 @@ function marginalcov(ls::MultiVariateLSgpu, varindices::Vector{Int64}, dofs::Vec
                         ls.ctx, which, λ, length(varindices), varindices, precond, maxiters, rtol, cov, stats))
     return cov, Int.(stats[2:4:4 * m])
 end
+# The reduced system of the upload's eliminated set (src/linearsolver.jl:20-32), applied and never formed: S(λ) = B + λ I - E (C + λ I)^-1 E' over the unfixed blocks that
+# are not eliminated, in ascending block order (nred unknowns).  schurinfo: (nred, eliminated blocks, one byte per unfixed block).  v, y: nred, or nred x nvec with
+# nvec <= 8; b: ndof (x nvec).  expand(b, S^-1 reduce(b)) solves (H + λ I) y = b.  A structure without an eliminated set errors (NLLS_ERR_UNSUPPORTED).
+function schurinfo(ls::MultiVariateLSgpu, nblocks::Integer)
+    nred = Ref(Int64(0)); nelim = Ref(Int64(0)); iselim = zeros(UInt8, max(nblocks, 1))
+    check(ls.ctx, ccall((:nlls_schur_info, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{UInt8}), ls.ctx, nred, nelim, iselim))
+    return Int(nred[]), Int(nelim[]), iselim[1:nblocks] .!= 0
+end
+function schurapply!(y::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, v::AbstractVecOrMat{Float64}, λ::Real=0.0, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_schur_apply, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, λ, apply_nvec(v), v, y)); return y
+end
+function schurreduce!(s::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, b::AbstractVecOrMat{Float64}, λ::Real=0.0, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_schur_reduce, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, λ, apply_nvec(b), b, s)); return s
+end
+function schurexpand!(y::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, b::AbstractVecOrMat{Float64}, yr::AbstractVecOrMat{Float64}, λ::Real=0.0, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_schur_expand, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, λ, apply_nvec(b), b, yr, y)); return y
+end
+# solvepcg! on that reduced system: conjugate gradients from 0 on S yr = reduce(b), the step x = -expand(b, yr) left in ls.x.  precond 1: the diagonal blocks of B + λ I.
+# rtol bounds the REDUCED residual.  Returns (iterations, status); a breakdown, an eliminated block without a factor included, errors and leaves the step as it was.
+function solvepcgschur!(ls::MultiVariateLSgpu; precond::Integer=1, maxiters::Integer=4 * max(ls.ndof, 1), rtol::Real=1e-8)
+    stats = zeros(8)
+    check(ls.ctx, ccall((:nlls_solve_pcg_schur, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}), ls.ctx, precond, maxiters, rtol, ls.x, stats))
+    return Int(stats[1]), Int(stats[2])
+end
 # optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
 # re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
 function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)

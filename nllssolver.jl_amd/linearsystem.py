@@ -91,6 +91,27 @@ class MultiVariateLSgpu:
         self._x = None
         return self.ctx.solve_pcg(precond, maxiters, rtol, want_x)
 
+    def solve_pcg_schur(self, precond="blockjacobi", maxiters=None, rtol=1e-8, want_x=False):
+        """solve_pcg on the reduced system of the upload's eliminated set (nlls_solve_pcg_schur) -> (x or None, stats)   src/linearsolver.jl:20-32"""
+        self._x = None
+        return self.ctx.solve_pcg_schur(precond, maxiters, rtol, want_x)
+
+    def schur_info(self):
+        """(nred, nelim, is_elim per unfixed block, positions of the reduced unknowns in the gradient) (nlls_schur_info)"""
+        return self.ctx.schur_info()
+
+    def schur_apply(self, v, lam=0.0, which=VARS_CURRENT):
+        """S(lam) v, S = B + lam I - E (C + lam I)^-1 E', never formed (nlls_schur_apply)"""
+        return self.ctx.schur_apply(v, lam, which)
+
+    def schur_reduce(self, b, lam=0.0, which=VARS_CURRENT):
+        """b_r - E (C + lam I)^-1 b_e (nlls_schur_reduce)"""
+        return self.ctx.schur_reduce(b, lam, which)
+
+    def schur_expand(self, b, yr, lam=0.0, which=VARS_CURRENT):
+        """yr on the reduced entries, (C + lam I)^-1 (b_e - E' yr) on the eliminated ones (nlls_schur_expand)"""
+        return self.ctx.schur_expand(b, yr, lam, which)
+
     def solve_pcg_rhs(self, B, lam=0.0, which=VARS_CURRENT, precond="blockjacobi", maxiters=None, rtol=1e-8):
         """(hessian + lam I) x_k = b_k for right-hand sides of the caller's, eight at a time on the device (nlls_solve_pcg_rhs) -> (X, stats); the linear system is
         left as it is   src/linearsolver.jl:20-32"""

@@ -376,6 +376,12 @@ class Solver:
         self._start()
         return HessianOperator(self.ls, lam)
 
+    def schur_operator(self, lam=0.0):
+        """S(lam) = B + lam I - E (C + lam I)^-1 E' of the upload's eliminated set at problem.variables (as they are NOW) as a linear operator on the reduced
+        unknowns: .shape, .index, .matvec(v), .reduce(b), .expand(b, yr), .diag_blocks().  A problem without an eliminated set raises NllsError (ERR_UNSUPPORTED)."""
+        self._start()
+        return SchurOperator(self.ls, lam)
+
     def set_data(self, group, data, index=None):
         """New data (measurements) for blocks of cost group `group` (0-based, the order of problem.costs): `data` (n x ndata) for the blocks `index` (0-BASED here, as
         `group` is; distinct) or, index=None, for the first n.  Written to the device (nlls_set_cost_data) and to the problem's CostGroup: the two never disagree."""
@@ -424,6 +430,34 @@ class HessianOperator:
     def solve(self, B, precond="blockjacobi", maxiters=None, rtol=1e-8):
         """(H + lam I)^-1 B by conjugate gradients on the device (nlls_solve_pcg_rhs): B (ndof,) or (nrhs, ndof) -> (X, stats)"""
         return self.ls.solve_pcg_rhs(B, self.lam, VARS_CURRENT, precond, maxiters, rtol)
+
+
+class SchurOperator:
+    """v -> S(lam) v on the reduced unknowns of a linear system's CURRENT variables, evaluated on the device with every product (nlls_schur_apply): neither H nor S is
+    held.  index: the positions of the reduced unknowns in the gradient; reduce / expand carry a right-hand side to the reduced system and a reduced solution back, so
+    that expand(b, S^-1 reduce(b)) solves (H + lam I) y = b; diag_blocks(): the diagonal blocks of B + lam I, a block-Jacobi preconditioner for S."""
+
+    def __init__(self, ls, lam=0.0):
+        self.ls = ls; self.lam = float(lam)
+        nred, nelim, self.is_elim, self.index = ls.schur_info()
+        if nelim == 0:
+            ls.schur_apply(np.zeros(nred), self.lam, VARS_CURRENT)      # (the library's refusal, with its text)
+        self.shape = (nred, nred); self.dtype = np.dtype(np.float64)
+
+    def matvec(self, v):
+        return self.ls.schur_apply(v, self.lam, VARS_CURRENT)
+
+    __call__ = matvec
+
+    def reduce(self, b):
+        return self.ls.schur_reduce(b, self.lam, VARS_CURRENT)
+
+    def expand(self, b, yr):
+        return self.ls.schur_expand(b, yr, self.lam, VARS_CURRENT)
+
+    def diag_blocks(self):
+        blocks = self.ls.hess_block_diag(self.lam, VARS_CURRENT)
+        return [blk for blk, e in zip(blocks, self.is_elim) if not e]
 
 
 SINGLES_MAX_DOF = 12          # NLLS_SINGLES_MAX_DOF (include/nlls_amd.h)

@@ -10,7 +10,11 @@ Solver.operator at the same tolerance (tools/apply_only.py --cg; --no-host-cg sk
   --round      NLLS_OPT_PCG_ROUND; a comma list measures each value (the table of notes/r18.md)
   --rhs K      nlls_solve_pcg_rhs instead: the first K unit columns (K = 6: those of the first unfixed camera) in ONE call, against K single-column calls and against K
                host-composed solves, same context, same run: wall time, product vectors, synchronisations
-  --cov N      nlls_marginal_cov instead: the joint covariance block of the first N unfixed cameras, against the same columns through --rhs's one call"""
+  --cov N      nlls_marginal_cov instead: the joint covariance block of the first N unfixed cameras, against the same columns through --rhs's one call
+  --schur      nlls_solve_pcg_schur beside nlls_solve_pcg and nlls_solve, same context, same run: iterations, median wall time, synchronisations and launches of each, each
+               one's distance to nlls_solve's step (the two iterations stop on different residuals -- the reduced system's and the full one's -- so compare them at the
+               distance reached: --schur-rtols 1e-8,1e-12 adds runs of both at other tolerances), and the event pair around one nlls_schur_apply beside one
+               nlls_hess_apply.  The workload graph_leaves_2kx100k (a general graph: 2000 chained hubs, 100000 leaves on three hubs each, scalar unknowns) is for this mode"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,10 +22,11 @@ import nllssolver_jl_amd as N
 from nllssolver_jl_amd import synthetic, _capi
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--workload", default="ba_1kx100k", choices=("ba_100x10k", "ba_1kx100k", "ba_so3_500x50k", "ba_20x2k", "ba_10x200_fixed"))
+ap.add_argument("--workload", default="ba_1kx100k", choices=("ba_100x10k", "ba_1kx100k", "ba_so3_500x50k", "ba_20x2k", "ba_10x200_fixed", "graph_leaves_2kx100k"))
 ap.add_argument("--lam", type=float, default=1e-3); ap.add_argument("--rtol", type=float, default=1e-10); ap.add_argument("--precond", default="blockjacobi", choices=("blockjacobi", "none"))
 ap.add_argument("--round", default=""); ap.add_argument("--repeats", type=int, default=7); ap.add_argument("--maxiters", type=int, default=0)
 ap.add_argument("--rhs", type=int, default=0); ap.add_argument("--cov", type=int, default=0)
+ap.add_argument("--schur", action="store_true"); ap.add_argument("--schur-rtols", default="")
 ap.add_argument("--no-schur", action="store_true"); ap.add_argument("--no-host-cg", action="store_true"); ap.add_argument("--host-cg-maxiter", type=int, default=2000)
 a = ap.parse_args()
 a.repeats = max(a.repeats, 7); unfixed = None
@@ -31,6 +36,9 @@ if a.workload == "ba_10x200_fixed":
     (g,) = p.costs.values(); vi, da = g.arrays(); rng = np.random.default_rng(4); pick = rng.choice(vi.shape[0], 150, replace=False)
     p.addcosts(K.RES_BA_AFFINE, vi[pick], da[pick] + 0.01 * rng.standard_normal((150, 2)), N.GemanMcclureKernel(0.01))
     unfixed = np.ones(p.nvariables, bool); unfixed[[0, 1]] = False; unfixed[10:40] = False
+elif a.workload == "graph_leaves_2kx100k":
+    from tests.helpers import scalar_graph_problem, shared_leaves_edges
+    e, n = shared_leaves_edges(2000, 100000); p = scalar_graph_problem(e, n, seed=5)      # (no robust kernel: H = J'J is positive semi-definite, any lambda > 0 will do)
 elif a.workload == "ba_so3_500x50k":
     p = synthetic.perturb_ba_problem(synthetic.create_so3_ba_problem(500, 50000, 0.02, seed=1, adaptive=True), 1e-3, 1e-3)
 else:
@@ -82,7 +90,32 @@ with N.Solver(p, unfixed, flags=_capi.FLAG_NO_SCHUR if a.no_schur else 0) as s:
         return {"iterations": st["iterations"].tolist(), "status": st["status"].tolist(), "synchronisations": st["synchronisations"], "launches": st["launches"],
                 "product_vectors": st["product_vectors"], "batches": st["batches"]}
 
-    if a.rhs:
+    if a.schur:
+        nred, nelim, _, _ = ctx.schur_info(); out["schur"] = {"nred": nred, "eliminated_blocks": nelim}
+        xs = ctx.solve(want_x=True)
+        def timed(call):
+            ms = []
+            for _ in range(a.repeats + 1):
+                t0 = time.perf_counter(); x, st = call(); ms.append(1e3 * (time.perf_counter() - t0))
+            return {"iterations": st["iterations"], "status": st["status"], "synchronisations": st["rounds"], "launches": st["launches"],
+                    "relative_residual": st["rnorm"] / max(st["bnorm"], 1e-300), "wall_ms": float(np.median(ms[1:])), "wall_ms_all": [round(m, 3) for m in ms[1:]],
+                    "distance_to_nlls_solve": float(np.max(np.abs(x - xs)) / np.max(np.abs(xs)))}
+        for rt in [a.rtol] + [float(v) for v in a.schur_rtols.split(",") if v]:
+            out["schur"][f"rtol_{rt:g}"] = {"nlls_solve_pcg": timed(lambda: ctx.solve_pcg(a.precond, maxiters, rt, want_x=True)),
+                                            "nlls_solve_pcg_schur": timed(lambda: ctx.solve_pcg_schur(a.precond, maxiters, rt, want_x=True))}
+        ts = []
+        for _ in range(a.repeats + 1):
+            t0 = time.perf_counter(); ctx.solve(); ts.append(1e3 * (time.perf_counter() - t0))
+        out["nlls_solve_ms"] = float(np.median(ts[1:]))
+        rng = np.random.default_rng(1); v = rng.standard_normal(ndof); vr = rng.standard_normal(nred); ctx.set_option(_capi.OPT_PHASE_EVENTS, 1)
+        for key, call in (("hess_apply_launches_us", lambda: ctx.hess_apply(v, lam)), ("schur_apply_launches_us", lambda: ctx.schur_apply(vr, lam))):
+            us = []
+            for _ in range(a.repeats + 1):
+                call(); us.append(ctx.phase_times()["apply_us"])
+            out[key] = float(np.median(us[1:]))
+        ctx.set_option(_capi.OPT_PHASE_EVENTS, 0)
+        out["schur_apply_over_hess_apply"] = out["schur_apply_launches_us"] / out["hess_apply_launches_us"]
+    elif a.rhs:
         B = np.zeros((a.rhs, ndof)); B[np.arange(a.rhs), np.arange(a.rhs)] = 1.0
         one, one_all, (X, st) = median_ms(lambda: ctx.solve_pcg_rhs(B, lam, _capi.VARS_CURRENT, a.precond, maxiters, a.rtol))
         def singles():
