@@ -475,6 +475,32 @@ int  nlls_schur_reduce(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec
 int  nlls_schur_expand(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* b /* nvec x ndof */, const double* yr /* nvec x nred */, double* y_out /* nvec x ndof */);
 int  nlls_solve_pcg_schur(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out);
 
+/* ---- conjugate gradients inside a trust region (Steihaug-Toint) --------------------------------------------------------------
+ * replaces: the dogleg iterator's Cauchy point plus Gauss-Newton solve (src/iterators.jl:47-115) by ONE iterative call: without a preconditioner the first iterate of
+ *           the method is the Cauchy point and its last the Newton step, with every piece of the path in between, and no factorisation.
+ * nlls_solve_pcg_tr stands where nlls_solve_pcg stands: b the gradient of the last sweep, H evaluated at NLLS_VARS_CURRENT by the launches of nlls_hess_apply, lambda
+ * the context's damping (normally 0 under a trust region; any finite value).  From y = 0 it approximately minimises q(y) = 1/2 y'(H + lambda I)y - b'y subject to
+ * ||y||_M <= radius and leaves x = -y as the context's step.  M is the preconditioner: the identity under NLLS_PCG_PRECOND_NONE (the Euclidean norm), the diagonal
+ * blocks of H + lambda I under NLLS_PCG_PRECOND_BLOCK_JACOBI (an ellipsoid) -- the norm in which the iterates of preconditioned conjugate gradients grow
+ * monotonically, the only one in which "stop at the boundary" is well defined.  H need not be positive definite.  Statuses:
+ *   0  ||r|| <= rtol ||b||, inside the region
+ *   1  maxiters reached, inside the region
+ *   4  the next iterate would leave the region: y = y_k + tau p_k with ||y||_M = radius
+ *   5  p'(H + lambda I)p <= 0: y = y_k + tau p_k, to the boundary along p_k
+ *   2  a scalar of the recurrence is not finite, or the curvature is not positive and radius is +inf (there is no boundary to go to)
+ *   3  a block of the preconditioner has no Cholesky factor
+ * 0, 1, 4 and 5 return NLLS_OK and set the step: every such exit is a descent step.  2 and 3 return NLLS_ERR_NOT_SPD and leave the step, x_out and everything else
+ * byte for byte, as nlls_solve_pcg does.  tau is the positive root of pp tau^2 + 2 yp tau + (yy - radius^2) = 0 with yy = ||y_k||_M^2, yp = y_k'M p_k,
+ * pp = ||p_k||_M^2, in the form that does not cancel: tau = (radius^2 - yy) / (yp + sqrt(yp^2 + pp (radius^2 - yy))).  The three follow from scalars the recurrence
+ * has: the call makes the launches and synchronisations of nlls_solve_pcg, no more, and with radius = +inf on a positive definite system its x_out and stats_out[0..5]
+ * are nlls_solve_pcg's byte for byte.
+ * stats_out[8] (may be NULL): [0] .. [5] as nlls_solve_pcg, [3] the residual r_k - tau q_k at the returned point; [6] ||y||_M at exit (status 4, 5: the radius);
+ * [7] the predicted reduction -q(y) = b'y - 1/2 y'(H + lambda I)y >= 0, in the units of nlls_sweep_cost: the denominator of the iterators' gain ratio, sign turned.
+ * NLLS_ERR_INVALID_ARG -- nothing enqueued, nothing written -- for what nlls_solve_pcg refuses and for a radius that is NaN or <= 0 (+inf is allowed);
+ * NLLS_ERR_NOT_READY and NLLS_ERR_UNSUPPORTED as nlls_solve_pcg (a sharded context among them); ndof == 0: NLLS_OK; ||b|| == 0: status 0, 0 iterations, x = 0.
+ * The bit rules of nlls_solve_pcg hold.  The counters of nlls_get_solve_stats and nlls_get_phase_times keep describing the last nlls_solve_pcg. */
+int  nlls_solve_pcg_tr(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double radius, double* x_out, double* stats_out);
+
 /* ---- the costs of an uploaded structure, changed in place -------------------------------------------------------------
  * replaces: the reference's mutable cost objects -- a residual's measurement, a robust kernel's width -- and optimize! called again on the same
  *           problem (src/optimize.jl:5-17): graduated non-convexity, re-measurement, outer EM / IRLS loops, refits of new data on one structure.

@@ -18,7 +18,7 @@ def __getattr__(name):
     # lazily expose the device-backed API so that host-only use (tests -m "not gpu") needs no .so
     import importlib
     if name in ("optimize", "optimizesingles", "NLLSOptions", "NLLSResult", "cost", "residuals", "squarederrors", "computeresjac", "computecostgradhess", "jacobian", "hessvec", "marginalcovariance", "jacvec", "jactvec", "HessianOperator", "SchurOperator", "Solver", "NLLSIterator", "newton", "levenbergmarquardt", "dogleg",
-                "gradientdescent"):
+                "gradientdescent", "steihaug"):
         return getattr(importlib.import_module(__name__ + ".optimizer"), name)
     if name == "PCG":                                # NLLSOptions(linearsolver=PCG(...)): conjugate gradients on the device in place of the direct solve
         return importlib.import_module(__name__ + ".iterators").PCG

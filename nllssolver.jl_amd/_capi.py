@@ -25,7 +25,7 @@ OPT_APPLY_SCRATCH, OPT_APPLY_WAVE_MIN = 4, 5
 OPT_PCG_ROUND, OPT_PCG_GRID_MAX = 6, 7
 PCG_PRECOND_NONE, PCG_PRECOND_BLOCK_JACOBI = 0, 1
 PCG_PRECONDS = {"none": PCG_PRECOND_NONE, None: PCG_PRECOND_NONE, "blockjacobi": PCG_PRECOND_BLOCK_JACOBI}
-PCG_STATUS = {0: "converged", 1: "maxiters", 2: "breakdown", 3: "preconditioner not positive definite"}
+PCG_STATUS = {0: "converged", 1: "maxiters", 2: "breakdown", 3: "preconditioner not positive definite", 4: "trust-region boundary", 5: "non-positive curvature, to the boundary"}
 APPLY_MAX_VEC = 8
 VARS_CURRENT, VARS_NEXT, VARS_BEST = 0, 1, 2
 
@@ -41,7 +41,7 @@ nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag n
 nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
 nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim
 nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg nlls_solve_pcg_rhs nlls_marginal_cov
-nlls_schur_info nlls_schur_apply nlls_schur_reduce nlls_schur_expand nlls_solve_pcg_schur""".split()
+nlls_schur_info nlls_schur_apply nlls_schur_reduce nlls_schur_expand nlls_solve_pcg_schur nlls_solve_pcg_tr""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -144,6 +144,7 @@ def lib():
         L.nlls_solve_pcg_rhs.argtypes = [vp, i32, dbl, i32, i32, dbl, i32, vp, vp, vp]; L.nlls_marginal_cov.argtypes = [vp, i32, dbl, i64, vp, i32, i32, dbl, vp, vp]
         L.nlls_schur_info.argtypes = [vp, vp, vp, vp]; L.nlls_schur_apply.argtypes = [vp, i32, dbl, i32, vp, vp]; L.nlls_schur_reduce.argtypes = [vp, i32, dbl, i32, vp, vp]
         L.nlls_schur_expand.argtypes = [vp, i32, dbl, i32, vp, vp, vp]; L.nlls_solve_pcg_schur.argtypes = [vp, i32, i32, dbl, vp, vp]
+        L.nlls_solve_pcg_tr.argtypes = [vp, i32, i32, dbl, dbl, vp, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
     return _lib
@@ -457,6 +458,20 @@ class Context:
         self.last_pcg_schur = dict(iterations=int(st[0]), status=int(st[1]), bnorm=float(st[2]), rnorm=float(st[3]), rounds=int(st[4]), launches=int(st[5]))
         self._chk(rc)
         return out, self.last_pcg_schur
+
+    def solve_pcg_tr(self, radius, precond=PCG_PRECOND_BLOCK_JACOBI, maxiters=None, rtol=1e-8, want_x=False):
+        """nlls_solve_pcg_tr: solve_pcg inside the trust region ||y||_M <= radius (Steihaug-Toint), M the preconditioner (the identity under "none"); +inf is allowed.
+        -> (x or None, stats) with solve_pcg's dictionary plus mnorm (||y||_M at exit) and model (the predicted reduction b'y - 1/2 y'(H + lambda I)y >= 0); status 0
+        converged and 1 maxiters inside the region, 4 stopped on the boundary, 5 non-positive curvature followed to the boundary: all four set the step.  A breakdown
+        (status 2, 3) raises NllsError with code ERR_NOT_SPD and leaves the step as it was; last_pcg_tr holds its stats, last_pcg stays solve_pcg's."""
+        pc = PCG_PRECONDS[precond] if isinstance(precond, str) or precond is None else int(precond)
+        mi = max(4 * int(self.info.ndof), 1) if maxiters is None else int(maxiters)
+        out = np.zeros(self.info.ndof) if want_x else None; st = np.zeros(8)
+        rc = self.L.nlls_solve_pcg_tr(self.h, pc, mi, float(rtol), float(radius), _p(out), _p(st))
+        self.last_pcg_tr = dict(iterations=int(st[0]), status=int(st[1]), bnorm=float(st[2]), rnorm=float(st[3]), rounds=int(st[4]), launches=int(st[5]),
+                                mnorm=float(st[6]), model=float(st[7]))
+        self._chk(rc)
+        return out, self.last_pcg_tr
 
     @staticmethod
     def _pcg_rhs_stats(st, n):

@@ -644,6 +644,17 @@ int nlls_solve_pcg_schur(nlls_ctx* ctx, int32_t precond, int32_t maxiters, doubl
     return pcg_solve_schur(ctx, precond, maxiters, rtol, x_out, stats_out);
     NLLS_API_END(ctx)
 }
+// nlls_solve_pcg inside a trust region (Steihaug-Toint; nlls_pcg.hip, pcg_solve_tr): refused as it refuses, and for a radius that is no radius; +inf is one
+int nlls_solve_pcg_tr(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double radius, double* x_out, double* stats_out) { NLLS_API_BEGIN
+    if (!ctx) return NLLS_ERR_INVALID_ARG;
+    if (!pcg_iteration_args_ok(precond, maxiters, rtol) || !(radius > 0.0)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg_tr: bad preconditioner, maxiters, rtol or radius");
+    NEED_GRAD_LAZY();
+    TRY(apply_check(ctx, "nlls_solve_pcg_tr", -1, false));
+    if (ctx->info.ndof == 0) { if (stats_out) for (int k = 0; k < 8; ++k) stats_out[k] = 0.0; return NLLS_OK; }
+    TRY(ensure_grad(ctx, 2)); TRY(ensure_reduced_summed(ctx));      // (b as nlls_get_grad reads it)
+    return pcg_solve_tr(ctx, precond, maxiters, rtol, radius, x_out, stats_out);
+    NLLS_API_END(ctx)
+}
 // One Levenberg-Marquardt trial in one call and one synchronisation (src/iterators.jl:149-157): uniformscaling!(H, dlambda),
 // solve!, negate!, update!(to, from, x), cost(to).  Same kernels, same order as the separate entry points.
 int nlls_lm_trial(nlls_ctx* ctx, double dlambda, int32_t to, int32_t from, double* cost_out) { NLLS_API_BEGIN

@@ -261,7 +261,10 @@ struct SchurIndex {
 // (p'q | r'z | r'r); scal: a scalar block PCG_* per column and one more, the factorisation's, that every column's block starts from; io: the caller's B, overwritten
 // column by column with the results (nlls_marginal_cov: one batch of unit columns; nlls_solve_pcg: unused); rows, cov: the selected unknowns and the m x m block of
 // nlls_marginal_cov.  h_scal: the pinned mirror of the batch's scalar blocks, one copy per round.
-enum { PCG_RZ0 = 0, PCG_RZ1 = 1, PCG_PQ = 2, PCG_RR = 3, PCG_BB = 4, PCG_ITER = 5, PCG_STOP = 6, PCG_STATUS = 7, PCG_NSCAL = 8 };   // r'z by parity of the iteration, p'q, r'r, b'b, iterations, stop, status
+enum { PCG_RZ0 = 0, PCG_RZ1 = 1, PCG_PQ = 2, PCG_RR = 3, PCG_BB = 4, PCG_ITER = 5, PCG_STOP = 6, PCG_STATUS = 7,   // r'z by parity of the iteration, p'q, r'r, b'b, iterations, stop, status
+       // the trust region's (nlls_solve_pcg_tr; carried by every call, read only under a finite radius): ||y||_M^2, y'Mp, ||p||_M^2 by the recurrences of the file's
+       // header, the model value b'y - 1/2 y'(H + lambda I)y, and what pcg_step_kernel records of a boundary exit for pcg_dir_kernel: its tau and its status (4 or 5)
+       PCG_YY = 8, PCG_YP = 9, PCG_PP = 10, PCG_MODEL = 11, PCG_TAU = 12, PCG_EXIT = 13, PCG_NSCAL = 16 };
 struct PinnedBuf {
     double* p = nullptr; size_t n = 0;
     PinnedBuf() = default;

@@ -1,6 +1,7 @@
 // nlls_internal.hpp -- declarations shared by the translation units of libnlls_amd.so
 #pragma once
 
+#include <cmath>
 #include <exception>
 #include <new>
 
@@ -91,11 +92,15 @@ struct PcgCall {
     const double* d_b = nullptr; const double* B = nullptr; const int64_t* rows = nullptr; double* out = nullptr;
     bool look_first = true;                // the first look at the stop flags before the first product (a zero column, a missing factor pay for none) or behind the first round (one synchronisation less)
     bool schur = false;                    // the operator is S(lambda) of the upload's eliminated set, the vectors have nred entries (d_b only: reduced on the device, the solution expanded there)
+    double radius = INFINITY;              // the trust region ||y||_M <= radius (d_b, not schur): a column may then end with status 4 or 5 on the boundary, results like 0 and 1
+    double* tr = nullptr;                  // host, two doubles (d_b only): ||y||_M by the recurrence and the model value b'y - 1/2 y'(H + lambda I)y of the column as it ended
 };
 // NLLS_ERR_NOT_SPD: a column broke down (the error text names the first one).  stats: 4 * ncols + 4 doubles (may be null)
 int pcg_solve_cols(nlls_ctx* c, const PcgCall& call, double* stats);
 // nlls_solve_pcg_schur: the driver on one column of the reduced system; what pcg_solve does around it, without the phase events and the counters of nlls_get_solve_stats
 int pcg_solve_schur(nlls_ctx* c, int precond, int maxiters, double rtol, double* x_out, double* stats);
+// nlls_solve_pcg_tr: the driver on pcg_solve's column inside ||y||_M <= radius (Steihaug-Toint), with pcg_solve's transitions and, like pcg_solve_schur, none of its counters
+int pcg_solve_tr(nlls_ctx* c, int precond, int maxiters, double rtol, double radius, double* x_out, double* stats);
 // Cholesky and inverse, in place, of n diagonal blocks listed by dof and start (nlls_pcg.hip, pcg_factor_kernel): a block without a factor leaves status 3 and the stop flag in scal
 int enqueue_block_factor(nlls_ctx* c, const int32_t* d_bsz, const uint32_t* d_dstart, int64_t n, double* d_blocks, double* d_scal);
 // what nlls_schur_apply.hip takes from nlls_apply.hip: the index with its row classes, the record scratch for nvec vectors (cut into chunks of `chunk`), the block launch of

@@ -21,6 +21,14 @@
 // (nlls_internal.hpp) says where the right-hand sides come from, where a finished column goes and when the first look at the stop flags is due.  pcg_solve is that
 // driver on one column -- H at CURRENT, the context's damping, b the gradient where it lies -- plus what is the step's alone: the phase events, step_replaced, the
 // counters of nlls_get_solve_stats, the copy to x_out, its eight statistics and its error texts.
+// Trust region (nlls_solve_pcg_tr, Steihaug-Toint): the same recurrence, stopped where the iterate would leave ||y||_M <= PcgArgs::radius or where p'q <= 0, and then taken
+// to the boundary along p.  M is the preconditioner (the identity without one), the norm in which the iterates grow monotonically, and in exact arithmetic
+//   yy = ||y||_M^2   yp = y'Mp   pp = ||p||_M^2        start: 0, 0, r'z;   after alpha: yy += 2 alpha yp + alpha^2 pp;   after beta: yp = beta (yp + alpha pp), pp = r'z_new + beta^2 pp
+// follow from scalars the iteration has: no dot product, launch or synchronisation more.  Lane 0 of workgroup 0 of pcg_dir keeps them, with the model value
+// b'y - 1/2 y'(H + lambda I)y (+= 1/2 alpha r'z per full step, += tau r'z - 1/2 tau^2 p'q at the boundary), in every call; only a call with a finite radius reads them,
+// and with radius = +inf the arithmetic on y, r, z, p is nlls_solve_pcg's operation for operation.  The boundary exit is where the stop-flag rule above bites: EVERY
+// workgroup of pcg_step has to write its share of y += tau p, so pcg_step records the exit in PCG_EXIT / PCG_TAU, which no workgroup of its own launch reads, and
+// pcg_dir, which then writes no vector, raises the flag and counts the iteration.
 #include <algorithm>
 #include <cmath>
 
@@ -35,6 +43,7 @@ struct PcgArgs {
     const double* b; const double* Minv; double* y; const double* r_old; double* r_new; double* z; double* p; const double* q;
     double* pa; double* pb; double* pc; double* scal;       // partials of p'q, r'z, r'r
     int64_t pstride; uint32_t cols;                         // doubles between two columns' rows of partials; four bits per slot: the column (of the batch) whose scalars and partials it uses
+    double radius;                                          // the trust region's, in the norm of M; +inf: none (the three solvers of linear systems)
 };
 // the arguments of this workgroup's column (everything here is uniform over the workgroup)
 NLLS_DEV PcgArgs pcg_column(PcgArgs a) {
@@ -123,8 +132,11 @@ __global__ __launch_bounds__(TPB) void pcg_start_kernel(PcgArgs a0) {
     const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     const double rz = pcg_total(a.pb, a.npart, red), bb = pcg_total(a.pc, a.npart, red);
-    if (threadIdx.x == 0) { a.scal[PCG_RZ0] = rz; a.scal[PCG_RR] = bb; a.scal[PCG_BB] = bb; if (bb <= a.rtol2 * bb) a.scal[PCG_STOP] = 1.0; }
+    if (threadIdx.x == 0) { a.scal[PCG_RZ0] = rz; a.scal[PCG_RR] = bb; a.scal[PCG_BB] = bb; a.scal[PCG_PP] = rz; if (bb <= a.rtol2 * bb) a.scal[PCG_STOP] = 1.0; }      // (||p||_M^2 = z'Mz = r'z; ||y||_M^2, y'Mp and the model are 0 from pcg_cols_begin_kernel)
 }
+
+// ||y + alpha p||_M^2 from the three scalars of the trust region
+NLLS_DEV double pcg_yy_next(double yy, double yp, double pp, double alpha) { return fma(alpha, fma(alpha, pp, 2.0 * yp), yy); }
 
 __global__ __launch_bounds__(TPB) void pcg_dot_kernel(PcgArgs a0) {
     __shared__ double red[16];
@@ -141,11 +153,33 @@ __global__ __launch_bounds__(TPB) void pcg_step_kernel(PcgArgs a0) {
     const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
     const double pq = pcg_total(a.pa, a.npart, red), rz = a.scal[PCG_RZ0 + a.parity], alpha = rz / pq;
-    if (!(pq > 0.0) || !isfinite(alpha)) {                  // the same decision in every workgroup: nobody writes a vector
+    // The trust region: from scalars every workgroup holds identically (pcg_dir_kernel of the iteration before left them), so all take the same exit.  exit 5: the
+    // curvature along p is not positive; exit 4: the full step would leave the ball; either way y goes to the boundary along p, tau the positive root of
+    // pp tau^2 + 2 yp tau + (yy - radius^2) = 0 in the form that does not cancel.  A tau that is not a finite step forwards is a breakdown like any other scalar's.
+    int ex = 0; double tau = 0.0;
+    if (isfinite(a.radius)) {
+        const double yy = a.scal[PCG_YY], yp = a.scal[PCG_YP], pp = a.scal[PCG_PP], r2 = a.radius * a.radius;
+        if (pq <= 0.0) ex = 5;
+        else if (pq > 0.0 && isfinite(alpha) && pcg_yy_next(yy, yp, pp, alpha) >= r2) ex = 4;
+        if (ex) { const double d = r2 - yy; tau = d / (yp + sqrt(fma(yp, yp, pp * d))); if (!(isfinite(tau) && tau >= 0.0)) ex = -1; }
+    }
+    if (ex < 0 || (!ex && (!(pq > 0.0) || !isfinite(alpha)))) {      // the same decision in every workgroup: nobody writes a vector
         if (blockIdx.x == 0 && threadIdx.x == 0) { a.scal[PCG_PQ] = pq; a.scal[PCG_ITER] += 1.0; a.scal[PCG_STATUS] = 2.0; a.scal[PCG_STOP] = 1.0; }
         return;
     }
     const double* __restrict__ ro = a.r_old; const double* __restrict__ q = a.q;
+    if (ex) {         // every workgroup writes its share of y += tau p and r_new = r - tau q.  NOT the stop flag: a workgroup of this launch that starts late would find it
+                        // at entry and leave its share unwritten -- the exit is recorded in scalars nobody of this launch reads, and pcg_dir_kernel stops the column
+        double srr = 0;
+        for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) {
+            const double re = fma(-tau, q[e], ro[e]);
+            a.y[e] = fma(tau, a.p[e], a.y[e]); a.r_new[e] = re;
+            srr += re * re;
+        }
+        srr = block_sum(srr, red);
+        if (threadIdx.x == 0) { a.pc[blockIdx.x] = srr; if (blockIdx.x == 0) { a.scal[PCG_PQ] = pq; a.scal[PCG_TAU] = tau; a.scal[PCG_EXIT] = (double)ex; } }
+        return;
+    }
     double srz = 0, srr = 0;
     for (int64_t e = (int64_t)blockIdx.x * TPB + threadIdx.x; e < a.ndof; e += (int64_t)gridDim.x * TPB) {
         const double re = fma(-alpha, q[e], ro[e]);         // (the block's other entries of r_new are formed the same way below: r is never read while it is written)
@@ -161,10 +195,23 @@ __global__ __launch_bounds__(TPB) void pcg_dir_kernel(PcgArgs a0) {
     __shared__ double red[16];
     const PcgArgs a = pcg_column(a0);
     if (pcg_stopped(a.scal, red)) return;
+    if (a.scal[PCG_EXIT] != 0.0) {      // pcg_step_kernel went to the boundary (every workgroup reads what that launch recorded): the residual there, the model value, the
+                                        // iteration, and the stop -- here, where no vector is written any more (p, which nobody reads again, stays as it is)
+        const double rr = pcg_total(a.pc, a.npart, red);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const double tau = a.scal[PCG_TAU], pq = a.scal[PCG_PQ], rz = a.scal[PCG_RZ0 + a.parity];
+            a.scal[PCG_RR] = rr; a.scal[PCG_ITER] += 1.0; a.scal[PCG_YY] = a.radius * a.radius; a.scal[PCG_MODEL] += tau * rz - 0.5 * tau * tau * pq;
+            a.scal[PCG_STATUS] = a.scal[PCG_EXIT]; a.scal[PCG_STOP] = 1.0;
+        }
+        return;
+    }
     const double rz = pcg_total(a.pb, a.npart, red), rr = pcg_total(a.pc, a.npart, red);
     const double beta = rz / a.scal[PCG_RZ0 + a.parity], bb = a.scal[PCG_BB];
     const bool done = rr <= a.rtol2 * bb, bad = !done && !(isfinite(beta) && isfinite(rr));
     if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double rz0 = a.scal[PCG_RZ0 + a.parity], alpha = rz0 / a.scal[PCG_PQ], yp = a.scal[PCG_YP], pp = a.scal[PCG_PP];      // (alpha as pcg_step_kernel formed it)
+        a.scal[PCG_YY] = pcg_yy_next(a.scal[PCG_YY], yp, pp, alpha); a.scal[PCG_MODEL] += 0.5 * alpha * rz0;
+        a.scal[PCG_YP] = beta * fma(alpha, pp, yp); a.scal[PCG_PP] = fma(beta * beta, pp, rz);
         a.scal[PCG_RZ0 + (a.parity ^ 1)] = rz; a.scal[PCG_RR] = rr; a.scal[PCG_ITER] += 1.0;
         if (done) a.scal[PCG_STOP] = 1.0;
         if (bad) { a.scal[PCG_STATUS] = 2.0; a.scal[PCG_STOP] = 1.0; }
@@ -237,7 +284,7 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     if (units) HIPCHK(hipMemcpyAsync(S.rows.p, k.rows, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(fscal, 0, sizeof(double) * PCG_NSCAL, c->stream));
     PcgArgs a{};
-    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = k.rtol * k.rtol;
+    a.ndof = ndof; a.nblocks = (int64_t)c->blocksizes.size(); a.precond = jacobi ? 1 : 0; a.npart = grid; a.parity = 0; a.rtol2 = k.rtol * k.rtol; a.radius = k.radius;
     a.Minv = S.Minv.p; a.y = y; a.r_old = r[1]; a.r_new = r[0]; a.z = z; a.p = p; a.q = q;
     a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.pstride = 3 * S.pw; a.scal = S.scal.p;
     const double* rhs = k.d_b;
@@ -267,11 +314,13 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
         int slot_col[MAXC]; for (int s = 0; s < MAXC; ++s) slot_col[s] = s;
         int active = nb; int64_t it = 0;
         auto stopped = [&](int s) { return h[slot_col[s] * PCG_NSCAL + PCG_STOP] != 0.0; };
-        auto finalize = [&](int s) -> hipError_t {          // the column's four statistics; its y to its place among the results (the step's one column stays in slot 0)
+        auto finalize = [&](int s) -> hipError_t {          // the column's four statistics; its y to its place among the results (the step's one column stays in slot 0).
+                                                            // Statuses 4 and 5, the trust region's boundary exits, are results like 0 and 1
             const int col = slot_col[s]; const double* hc = h + col * PCG_NSCAL; double* sc = st.data() + 4 * (j0 + col);
             const int status = hc[PCG_STOP] != 0.0 ? (int)hc[PCG_STATUS] : 1;
             sc[0] = hc[PCG_ITER]; sc[1] = status; sc[2] = std::sqrt(hc[PCG_BB]); sc[3] = std::sqrt(hc[PCG_RR]);
-            if (status >= 2) { if (!bad) { bad = true; bad_col = j0 + col; bad_status = status; } if (status == 3) bad_status = 3; return hipSuccess; }
+            if (k.tr) { k.tr[0] = std::sqrt(hc[PCG_YY]); k.tr[1] = hc[PCG_MODEL]; }
+            if (status == 2 || status == 3) { if (!bad) { bad = true; bad_col = j0 + col; bad_status = status; } if (status == 3) bad_status = 3; return hipSuccess; }
             if (step) return hipSuccess;
             return hipMemcpyAsync(bio + (int64_t)col * ndof, y + (int64_t)s * ndof, sizeof(double) * (size_t)ndof, hipMemcpyDeviceToDevice, c->stream); };
         // a look, then a round.  look_first: the first look finds the columns that need no iteration (b == 0; no factor), so that they pay for no product either; without
@@ -416,6 +465,26 @@ int pcg_solve_schur(nlls_ctx* c, int precond, int maxiters, double rtol, double*
         if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)c->info.ndof, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         st[4] += 1.0;
+    }
+    if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
+    return rc;
+}
+
+// nlls_solve_pcg_tr: pcg_solve's column -- H at CURRENT, the context's damping, the gradient where it lies -- inside ||y||_M <= radius, with pcg_solve's transitions and,
+// like pcg_solve_schur, none of its counters or phase events.  The six statistics of pcg_solve, then ||y||_M and the predicted reduction: on a boundary exit the norm IS
+// the radius (the recurrence's value there is radius^2 by construction)
+int pcg_solve_tr(nlls_ctx* c, int precond, int maxiters, double rtol, double radius, double* x_out, double* stats) {
+    double st[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cs[8], tr[2] = {0, 0};
+    const int rc = pcg_solve_cols(c, PcgCall{.name = "nlls_solve_pcg_tr", .which = NLLS_VARS_CURRENT, .lambda = c->lambda, .precond = precond, .maxiters = maxiters, .rtol = rtol,
+                                             .ncols = 1, .d_b = c->b.p, .look_first = false, .radius = radius, .tr = tr}, cs);
+    if (rc != NLLS_OK && rc != NLLS_ERR_NOT_SPD) return rc;
+    for (int i = 0; i < 6; ++i) st[i] = cs[i];
+    if (rc == NLLS_OK) {
+        step_replaced(c);
+        if (x_out) HIPCHK(hipMemcpyAsync(x_out, c->x.p, sizeof(double) * (size_t)c->info.ndof, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        st[4] += 1.0;
+        st[6] = (int)st[1] >= 4 ? radius : tr[0]; st[7] = tr[1];
     }
     if (stats) for (int i = 0; i < 8; ++i) stats[i] = st[i];
     return rc;

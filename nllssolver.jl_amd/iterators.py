@@ -191,6 +191,57 @@ def iterate_dogleg(dd, data, problem, options):     # src/iterators.jl:47-115
             return cost_
 
 
+class SteihaugData:                                 # (not in the reference; the state of DoglegData, src/iterators.jl:30-45)
+    def __init__(self, trustradius=0.0):
+        self.trustradius = float(trustradius)
+        self.statuses = []                          # how every trial's conjugate gradients ended (0, 1 inside the region; 4, 5 on its boundary)
+
+    def reset(self):
+        self.trustradius = 0.0
+        self.statuses = []
+
+    def printable(self):
+        return self.trustradius
+
+
+def _cauchy_mnorm(ls, precond):
+    """the M-norm of the Cauchy step, (b'z / z'Hz) sqrt(b'z) with z = M^-1 b -- sqrt(b'z) where z'Hz <= 0: the first radius of iterate_steihaug"""
+    b = np.asarray(ls.b, np.float64); z = b.copy()
+    if precond == "blockjacobi":
+        o = 0
+        for blk in ls.hess_block_diag(0.0):
+            d = blk.shape[0]; z[o:o + d] = np.linalg.solve(blk, b[o:o + d]); o += d
+    bz = float(b @ z); zhz = float(z @ ls.hess_apply(z))
+    radius = (bz / zhz) * math.sqrt(bz) if zhz > 0 and bz > 0 else math.sqrt(max(bz, 0.0))
+    return radius if radius > 0 and math.isfinite(radius) else 1.0       # (b == 0: any ball holds the zero step)
+
+
+def iterate_steihaug(sd, data, problem, options):
+    """A trust-region iteration whose every trial is ONE call: Steihaug-Toint conjugate gradients on the device (nlls_solve_pcg_tr) in the place of dogleg's Cauchy point
+    plus Gauss-Newton solve (src/iterators.jl:47-115), with dogleg's radius rule (:101-106) in the norm of the preconditioner.  rtol, maxiters and precond come from
+    options.linearsolver (None: PCG(rtol=1e-2)); a preconditioner block without a factor (status 3) raises, as everywhere: there is no fall-back."""
+    ls = data.linsystem
+    pcg = getattr(options, "linearsolver", None) or PCG(rtol=1e-2)
+    if getattr(pcg, "schur", False):
+        raise ValueError("iterate_steihaug: PCG(schur=True) has no trust region -- a ball in the norm of the reduced system is not a ball of the step")
+    if sd.trustradius == 0:
+        sd.trustradius = _timed(data, "timesolver", lambda: _cauchy_mnorm(ls, pcg.precond))
+    while True:
+        _, st = _timed(data, "timesolver", lambda: ls.solve_pcg_tr(sd.trustradius, pcg.precond, pcg.maxiters, pcg.rtol))
+        data.linearsolvers += 1
+        sd.statuses.append(st["status"])
+        ls.update(VARS_NEXT, VARS_CURRENT)
+        cost_ = _timed(data, "timecost", lambda: ls.cost(VARS_NEXT))
+        data.costcomputations += 1
+        mu = (data.bestcost - cost_) / (st["model"] + FLOATMIN)
+        if mu > 0.375:
+            sd.trustradius = max(sd.trustradius, 3 * st["mnorm"])
+        elif mu < 0.125:
+            sd.trustradius *= 0.5
+        if not (cost_ > data.bestcost) or ls.step_maxabs() < options.dstep:
+            return cost_
+
+
 class GradientDescentData:                          # src/iterators.jl:177-185
     def __init__(self):
         self.stepsize = 1.0

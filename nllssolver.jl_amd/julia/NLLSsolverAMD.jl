@@ -226,6 +226,14 @@ function solvepcgschur!(ls::MultiVariateLSgpu; precond::Integer=1, maxiters::Int
     check(ls.ctx, ccall((:nlls_solve_pcg_schur, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}), ls.ctx, precond, maxiters, rtol, ls.x, stats))
     return Int(stats[1]), Int(stats[2])
 end
+# solvepcg! inside the trust region ||y||_M <= radius (Steihaug-Toint; M the preconditioner, the identity under precond 0), in the place of the dogleg iterator's Cauchy
+# point plus Gauss-Newton solve (src/iterators.jl:47-115): the step x = -y left in ls.x.  Returns (iterations, status, ||y||_M, predicted reduction); status 0, 1 inside
+# the region, 4 stopped on its boundary, 5 non-positive curvature followed to the boundary.  A breakdown (2, 3) errors and leaves the step as it was.
+function solvepcgtr!(ls::MultiVariateLSgpu, radius::Real; precond::Integer=1, maxiters::Integer=4 * max(ls.ndof, 1), rtol::Real=1e-8)
+    stats = zeros(8)
+    check(ls.ctx, ccall((:nlls_solve_pcg_tr, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Float64, Float64, Ptr{Float64}, Ptr{Float64}), ls.ctx, precond, maxiters, rtol, radius, ls.x, stats))
+    return Int(stats[1]), Int(stats[2]), stats[7], stats[8]
+end
 # optimize(kernel::ContaminatedGaussian, squarederrors, maxiters) (src/robustadaptive.jl:48-73) on the device: the kernel variable `kernelvar` (1-based) of set `which`
 # re-estimated by Expectation-Maximization on the squared errors of its blocks and written back into that set; returns its storage (1/sigma1, 1/sigma2, w).
 function adaptiveem!(ls::MultiVariateLSgpu, which::Integer, kernelvar::Integer, maxiters::Integer=10)

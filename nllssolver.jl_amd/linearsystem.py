@@ -96,6 +96,12 @@ class MultiVariateLSgpu:
         self._x = None
         return self.ctx.solve_pcg_schur(precond, maxiters, rtol, want_x)
 
+    def solve_pcg_tr(self, radius, precond="blockjacobi", maxiters=None, rtol=1e-8, want_x=False):
+        """solve_pcg inside the trust region ||y||_M <= radius, M the preconditioner (Steihaug-Toint; nlls_solve_pcg_tr) -> (x or None, stats with mnorm and model)
+        in the place of the dogleg iterator's Cauchy point plus Gauss-Newton solve   src/iterators.jl:47-115"""
+        self._x = None
+        return self.ctx.solve_pcg_tr(radius, precond, maxiters, rtol, want_x)
+
     def schur_info(self):
         """(nred, nelim, is_elim per unfixed block, positions of the reduced unknowns in the gradient) (nlls_schur_info)"""
         return self.ctx.schur_info()

@@ -17,9 +17,10 @@ class NLLSIterator(enum.IntEnum):                   # src/structs.jl:5
     levenbergmarquardt = 1
     dogleg = 2
     gradientdescent = 3
+    steihaug = 4                                    # (not in the reference: Steihaug-Toint conjugate gradients inside a trust region, nlls_solve_pcg_tr)
 
 
-newton, levenbergmarquardt, dogleg, gradientdescent = NLLSIterator
+newton, levenbergmarquardt, dogleg, gradientdescent, steihaug = NLLSIterator
 
 
 class NLLSOptions:                                   # src/structs.jl:22-35
@@ -85,6 +86,7 @@ _ITER = {
     levenbergmarquardt: (It.LevMarData, It.iterate_levmar),
     dogleg: (It.DoglegData, It.iterate_dogleg),
     gradientdescent: (It.GradientDescentData, It.iterate_gradientdescent),
+    steihaug: (It.SteihaugData, It.iterate_steihaug),
 }
 
 

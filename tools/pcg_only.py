@@ -14,7 +14,10 @@ Solver.operator at the same tolerance (tools/apply_only.py --cg; --no-host-cg sk
   --schur      nlls_solve_pcg_schur beside nlls_solve_pcg and nlls_solve, same context, same run: iterations, median wall time, synchronisations and launches of each, each
                one's distance to nlls_solve's step (the two iterations stop on different residuals -- the reduced system's and the full one's -- so compare them at the
                distance reached: --schur-rtols 1e-8,1e-12 adds runs of both at other tolerances), and the event pair around one nlls_schur_apply beside one
-               nlls_hess_apply.  The workload graph_leaves_2kx100k (a general graph: 2000 chained hubs, 100000 leaves on three hubs each, scalar unknowns) is for this mode"""
+               nlls_hess_apply.  The workload graph_leaves_2kx100k (a general graph: 2000 chained hubs, 100000 leaves on three hubs each, scalar unknowns) is for this mode
+  --tr F       nlls_solve_pcg_tr beside nlls_solve_pcg, same context, same run: first with radius +inf (the same iteration: its time per iteration against
+               nlls_solve_pcg's), then at F times the M-norm of that converged step (a comma list measures each fraction): iterations, status, median wall time,
+               synchronisations and launches of each"""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,7 +29,7 @@ ap.add_argument("--workload", default="ba_1kx100k", choices=("ba_100x10k", "ba_1
 ap.add_argument("--lam", type=float, default=1e-3); ap.add_argument("--rtol", type=float, default=1e-10); ap.add_argument("--precond", default="blockjacobi", choices=("blockjacobi", "none"))
 ap.add_argument("--round", default=""); ap.add_argument("--repeats", type=int, default=7); ap.add_argument("--maxiters", type=int, default=0)
 ap.add_argument("--rhs", type=int, default=0); ap.add_argument("--cov", type=int, default=0)
-ap.add_argument("--schur", action="store_true"); ap.add_argument("--schur-rtols", default="")
+ap.add_argument("--schur", action="store_true"); ap.add_argument("--schur-rtols", default=""); ap.add_argument("--tr", default="")
 ap.add_argument("--no-schur", action="store_true"); ap.add_argument("--no-host-cg", action="store_true"); ap.add_argument("--host-cg-maxiter", type=int, default=2000)
 a = ap.parse_args()
 a.repeats = max(a.repeats, 7); unfixed = None
@@ -115,6 +118,20 @@ with N.Solver(p, unfixed, flags=_capi.FLAG_NO_SCHUR if a.no_schur else 0) as s:
             out[key] = float(np.median(us[1:]))
         ctx.set_option(_capi.OPT_PHASE_EVENTS, 0)
         out["schur_apply_over_hess_apply"] = out["schur_apply_launches_us"] / out["hess_apply_launches_us"]
+    elif a.tr:
+        def timed(call):
+            ms = []
+            for _ in range(a.repeats + 1):
+                t0 = time.perf_counter(); _, st = call(); ms.append(1e3 * (time.perf_counter() - t0))
+            wall = float(np.median(ms[1:]))
+            return dict({k: st[k] for k in ("iterations", "status", "launches", "mnorm", "model") if k in st}, synchronisations=st["rounds"], wall_ms=wall,
+                        wall_ms_all=[round(m, 3) for m in ms[1:]], us_per_iteration=1e3 * wall / max(st["iterations"], 1))
+        out["tr"] = {"nlls_solve_pcg": timed(lambda: ctx.solve_pcg(a.precond, maxiters, a.rtol)),
+                     "nlls_solve_pcg_tr_inf": timed(lambda: ctx.solve_pcg_tr(np.inf, a.precond, maxiters, a.rtol))}
+        full = out["tr"]["nlls_solve_pcg_tr_inf"]["mnorm"]
+        for fr in (float(v) for v in a.tr.split(",") if v):
+            out["tr"][f"nlls_solve_pcg_tr_{fr:g}"] = dict(timed(lambda: ctx.solve_pcg_tr(fr * full, a.precond, maxiters, a.rtol)), radius=fr * full)
+        out["tr"]["tr_inf_over_pcg_per_iteration"] = out["tr"]["nlls_solve_pcg_tr_inf"]["us_per_iteration"] / out["tr"]["nlls_solve_pcg"]["us_per_iteration"]
     elif a.rhs:
         B = np.zeros((a.rhs, ndof)); B[np.arange(a.rhs), np.arange(a.rhs)] = 1.0
         one, one_all, (X, st) = median_ms(lambda: ctx.solve_pcg_rhs(B, lam, _capi.VARS_CURRENT, a.precond, maxiters, a.rtol))
