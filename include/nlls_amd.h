@@ -406,6 +406,8 @@ int  nlls_hess_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d
  * describe its last product. */
 #define NLLS_PCG_PRECOND_NONE          0   /* M = I */
 #define NLLS_PCG_PRECOND_BLOCK_JACOBI  1   /* M = the diagonal blocks of H + lambda I (nlls_hess_block_diag) */
+/* 2 is unassigned and refused by every entry point, on purpose: it is the value the refusal tests of the four conjugate-gradient entry points hold */
+#define NLLS_PCG_PRECOND_SCHUR_JACOBI  3   /* M = the diagonal blocks of S(lambda) (nlls_schur_block_diag); nlls_solve_pcg_schur only: the others refuse it with NLLS_ERR_INVALID_ARG */
 int  nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out);
 
 /* ---- conjugate gradients on the caller's right-hand sides; marginal covariance blocks ----------------------------------
@@ -468,7 +470,21 @@ int  nlls_marginal_cov(nlls_ctx* ctx, int32_t which, double lambda, int64_t nsel
  * blocks of B + lambda I.  It stops on the recurrence's ||r|| <= rtol ||s|| of the REDUCED system.  Statuses, return codes and stats_out[8] as nlls_solve_pcg, with
  * ||s|| and the reduced ||r|| in [2], [3]; status 3 also covers an eliminated block without a factor; on 2 or 3 the step and x_out stay byte for byte.  The counters
  * of nlls_get_solve_stats and nlls_get_phase_times keep describing the last nlls_solve_pcg.  NLLS_OPT_PCG_ROUND, NLLS_OPT_PCG_GRID_MAX and NLLS_OPT_APPLY_WAVE_MIN
- * mean here what they mean for the full products. */
+ * mean here what they mean for the full products.
+ * Under NLLS_PCG_PRECOND_SCHUR_JACOBI (Ceres' SCHUR_JACOBI) M is the diagonal blocks of S(lambda) itself -- every eliminated neighbour takes its curvature off a reduced
+ * block, which the blocks of B + lambda I do not see.  Everything above holds; status 3 also covers an S_ii without a Cholesky factor, and stats_out[5] counts the
+ * set-up's extra launches (the off-diagonal records of every group, the subtraction).  The iteration's launches, scalars and synchronisations are block Jacobi's.
+ * nlls_schur_block_diag returns those blocks, unfactored: for a reduced block i, with the sum over its eliminated neighbours e,
+ *   S_ii = B_ii + lambda I - sum_e E_ie (C_e + lambda I)^-1 E_ie'
+ * where E_ie is the SUM of the off-diagonal blocks of every cost block that joins i and e, taken before the product.  d_out (a HOST pointer, as every vector of the
+ * products; synchronous): the reduced blocks in ascending block order -- the order of the reduced vector -- block i at offset sum_{c < i, c reduced} dof_c^2,
+ * column-major, full symmetric: nlls_hess_block_diag's layout restricted to the r class.  A reduced block without an eliminated neighbour holds the bytes
+ * nlls_hess_block_diag returns for it.  An indefinite S_ii is returned as it is.  Rules and refusals of nlls_schur_apply: H at set `which` at call time, lambda the
+ * argument, an upload and no sweep, read only (the counters of the last nlls_solve_pcg included), fixed-order sums and identical bytes from two calls;
+ * NLLS_ERR_INVALID_ARG for a null pointer, `which` outside 0 .. 2, a lambda that is not finite; NLLS_ERR_NOT_READY; NLLS_ERR_UNSUPPORTED for a sharded context, a
+ * dynamic-size group, an upload that eliminated nothing; NLLS_ERR_NOT_SPD, no byte written, where a C_e + lambda I has no Cholesky factor; nred == 0: NLLS_OK, nothing
+ * written. */
+int  nlls_schur_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d_out /* sum over the reduced blocks of dof^2 */);
 int  nlls_schur_info(const nlls_ctx* ctx, int64_t* nred_out, int64_t* nelim_out, uint8_t* is_elim_out /* nblocks, may be NULL */);
 int  nlls_schur_apply(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* v /* nvec x nred */, double* y_out /* nvec x nred */);
 int  nlls_schur_reduce(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec, const double* b /* nvec x ndof */, double* s_out /* nvec x nred */);

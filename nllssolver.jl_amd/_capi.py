@@ -23,8 +23,8 @@ FLAG_MATERIALIZE = 2048
 OPT_MATERIALIZE, OPT_LOOKAHEAD, OPT_PHASE_EVENTS = 1, 2, 3
 OPT_APPLY_SCRATCH, OPT_APPLY_WAVE_MIN = 4, 5
 OPT_PCG_ROUND, OPT_PCG_GRID_MAX = 6, 7
-PCG_PRECOND_NONE, PCG_PRECOND_BLOCK_JACOBI = 0, 1
-PCG_PRECONDS = {"none": PCG_PRECOND_NONE, None: PCG_PRECOND_NONE, "blockjacobi": PCG_PRECOND_BLOCK_JACOBI}
+PCG_PRECOND_NONE, PCG_PRECOND_BLOCK_JACOBI, PCG_PRECOND_SCHUR_JACOBI = 0, 1, 3      # (2 is unassigned: every entry point refuses it)
+PCG_PRECONDS = {"none": PCG_PRECOND_NONE, None: PCG_PRECOND_NONE, "blockjacobi": PCG_PRECOND_BLOCK_JACOBI, "schurjacobi": PCG_PRECOND_SCHUR_JACOBI}
 PCG_STATUS = {0: "converged", 1: "maxiters", 2: "breakdown", 3: "preconditioner not positive definite", 4: "trust-region boundary", 5: "non-positive curvature, to the boundary"}
 APPLY_MAX_VEC = 8
 VARS_CURRENT, VARS_NEXT, VARS_BEST = 0, 1, 2
@@ -41,7 +41,7 @@ nlls_set_allreduce nlls_comm_unique_id nlls_comm_init_rccl nlls_comm_post_flag n
 nlls_eval_blocks nlls_adaptive_em nlls_set_cost_data nlls_set_robust_params
 nlls_eval_jacobians nlls_eval_gradhess nlls_res_jac_cols nlls_res_gh_dim
 nlls_hess_apply nlls_jac_apply nlls_jact_apply nlls_hess_block_diag nlls_solve_pcg nlls_solve_pcg_rhs nlls_marginal_cov
-nlls_schur_info nlls_schur_apply nlls_schur_reduce nlls_schur_expand nlls_solve_pcg_schur nlls_solve_pcg_tr""".split()
+nlls_schur_info nlls_schur_apply nlls_schur_reduce nlls_schur_expand nlls_solve_pcg_schur nlls_solve_pcg_tr nlls_schur_block_diag""".split()
 
 
 class LmOptions(C.Structure):          # nlls_lm_options
@@ -144,6 +144,7 @@ def lib():
         L.nlls_solve_pcg_rhs.argtypes = [vp, i32, dbl, i32, i32, dbl, i32, vp, vp, vp]; L.nlls_marginal_cov.argtypes = [vp, i32, dbl, i64, vp, i32, i32, dbl, vp, vp]
         L.nlls_schur_info.argtypes = [vp, vp, vp, vp]; L.nlls_schur_apply.argtypes = [vp, i32, dbl, i32, vp, vp]; L.nlls_schur_reduce.argtypes = [vp, i32, dbl, i32, vp, vp]
         L.nlls_schur_expand.argtypes = [vp, i32, dbl, i32, vp, vp, vp]; L.nlls_solve_pcg_schur.argtypes = [vp, i32, i32, dbl, vp, vp]
+        L.nlls_schur_block_diag.argtypes = [vp, i32, dbl, vp]
         L.nlls_solve_pcg_tr.argtypes = [vp, i32, i32, dbl, dbl, vp, vp]
         L.nlls_comm_post_flag.argtypes = [vp, dbl]; L.nlls_comm_agreed_flag.argtypes = [vp, dbl, vp]; L.nlls_comm_info.argtypes = [vp, vp, i32]
         _lib = L
@@ -446,9 +447,18 @@ class Context:
             self._chk(self.L.nlls_schur_expand(self.h, int(which), float(lam), ak.shape[0], _p(ak), _p(yk if yk.size else np.zeros(1)), _p(ok)))      # (nred 0: a pointer that is not null)
         return out[0] if one else out
 
+    def schur_block_diag(self, lam=0.0, which=VARS_CURRENT):
+        """nlls_schur_block_diag: the diagonal blocks of S(lam) itself -- B_ii + lam I - sum over the eliminated neighbours e of E_ie (C_e + lam I)^-1 E_ie' -- one
+        (dof, dof) array per REDUCED block, in ascending block order, unfactored (what "schurjacobi" inverts).  An eliminated block without a factor raises
+        NllsError (ERR_NOT_SPD); an upload that eliminated nothing raises ERR_UNSUPPORTED."""
+        is_elim = self.schur_info()[2]; bs = self.block_sizes()[~is_elim]; out = np.zeros(max(int((bs * bs).sum()), 1))
+        self._chk(self.L.nlls_schur_block_diag(self.h, int(which), float(lam), _p(out)))
+        off = np.concatenate(([0], np.cumsum(bs * bs)))
+        return [out[off[b]:off[b + 1]].reshape(bs[b], bs[b]).T.copy() for b in range(bs.size)]
+
     def solve_pcg_schur(self, precond=PCG_PRECOND_BLOCK_JACOBI, maxiters=None, rtol=1e-8, want_x=False):
         """nlls_solve_pcg_schur: solve_pcg on the reduced system -- conjugate gradients from 0 on S yr = reduce(b), y = expand(b, yr), x = -y as the step.  precond:
-        1 / "blockjacobi" (the diagonal blocks of B + lambda I), 0 / "none"; maxiters: 4 ndof when None; rtol on the REDUCED residual.  -> (x or None, stats) with
+        1 / "blockjacobi" (the diagonal blocks of B + lambda I), 3 / "schurjacobi" (the diagonal blocks of S itself), 0 / "none"; maxiters: 4 ndof when None; rtol on the REDUCED residual.  -> (x or None, stats) with
         solve_pcg's dictionary, bnorm and rnorm those of the reduced system.  A breakdown (status 2, 3; an eliminated block without a factor is 3) raises NllsError
         with code ERR_NOT_SPD and leaves the step as it was; last_pcg_schur holds its stats.  An upload that eliminated nothing raises ERR_UNSUPPORTED."""
         pc = PCG_PRECONDS[precond] if isinstance(precond, str) or precond is None else int(precond)

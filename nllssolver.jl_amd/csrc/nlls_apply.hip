@@ -16,7 +16,7 @@
 
 namespace nlls {
 
-enum { APP_HESS = 0, APP_JAC = 1, APP_JACT = 2, APP_DIAG = 3 };
+enum { APP_HESS = 0, APP_JAC = 1, APP_JACT = 2, APP_DIAG = 3, APP_OFFD = 4 };
 
 // ================================================================================================
 // block launch
@@ -30,6 +30,11 @@ template <int KIND> struct AppSize {
     static constexpr int doff(int s) { int n = 0; for (int t = 0; t < s; ++t) n += dof(t) * dof(t); return n; }   // first entry of slot s's diagonal block in a record
     static constexpr int DD = doff(ND);
     static constexpr int dslot(int q) { int s = 0; while (s + 1 < ND && q >= doff(s + 1)) ++s; return s; }
+    // the off-diagonal blocks of H_blk, one per slot pair s < t in the order (0, 1), (0, 2), .., (1, 2), ..: first entry of pair (s, t) in a record (a pair that does
+    // not exist: the records' length), and the pair s * ND + t that entry q belongs to
+    static constexpr int ooff(int s, int t) { int n = 0; for (int a = 0; a < ND; ++a) for (int b = a + 1; b < ND; ++b) { if (a == s && b == t) return n; n += dof(a) * dof(b); } return n; }
+    static constexpr int OD = ooff(ND, ND);
+    static constexpr int opair(int q) { int n = 0; for (int a = 0; a < ND; ++a) for (int b = a + 1; b < ND; ++b) { n += dof(a) * dof(b); if (q < n) return a * ND + b; } return 0; }
     static_assert(!R::ADAPT || I::dof(0) == 3, "the adaptive kernel is slot 0, three unknowns");
 };
 template <int KIND>
@@ -82,6 +87,7 @@ NLLS_DEV void app_hx(const BlockGH<KIND>& B, const double* x, double* y) {
 // v count as 0 and nobody gathers its rows of the record).  Vector k: in + k * in_stride -> out + k * out_stride.
 //   APP_HESS  in = v,  record i of out: P doubles, H_blk P' P v          APP_JAC   in = v,  out = u: M doubles per block, J P v
 //   APP_JACT  in = u,  record i of out: P doubles, J' u (kernel rows 0)  APP_DIAG  one "vector": record i = the slots' diagonal blocks of H_blk, column-major each
+//   APP_OFFD  one "vector": record i = for every slot pair s < t the block H_blk[slot s rows, slot t columns], column-major dof_s x dof_t (AppSize::ooff)
 // The k loop is a run-time loop over one body: vector k of a call of many carries the bits of a call of its own.
 template <int KIND, int MODE>
 __global__ __launch_bounds__(TPB) void apply_blocks_kernel(const double* __restrict__ vars, const double* __restrict__ data, const uint32_t* __restrict__ voff,
@@ -110,6 +116,11 @@ __global__ __launch_bounds__(TPB) void apply_blocks_kernel(const double* __restr
             store_records<S::DD>(out, first, cnt, slab, [&](auto q) {
                 constexpr int s = S::dslot(q()), e = q() - S::doff(s), ds = S::dof(s);
                 return app_h<KIND>(B, S::loff(s) + e % ds, S::loff(s) + e / ds); });
+        } else if constexpr (MODE == APP_OFFD) {
+            if constexpr (S::OD > 0)
+                store_records<S::OD>(out, first, cnt, slab, [&](auto q) {
+                    constexpr int pr = S::opair(q()), s = pr / S::ND, t = pr % S::ND, e = q() - S::ooff(s, t), ds = S::dof(s);
+                    return app_h<KIND>(B, S::loff(s) + e % ds, S::loff(t) + e / ds); });
         } else {
             for (int k = 0; k < nvec; ++k) {
                 const double* __restrict__ ik = in + (int64_t)k * in_stride; double* __restrict__ ok = out + (int64_t)k * out_stride;
@@ -305,6 +316,7 @@ int launch_blocks(nlls_ctx* c, size_t g, int which, int nvec, const double* in, 
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((G.ncost + TPB - 1) / TPB, 2048));
     const bool known = dispatch_res(G.res_kind, [&](auto k) {
         if constexpr (is_cost_kind<k()> && (MODE == APP_JAC || MODE == APP_JACT)) return false;
+        else if constexpr (MODE == APP_OFFD && AppSize<k()>::OD == 0) return true;      // (a kind of one slot: no record, no launch)
         else { hipLaunchKernelGGL((apply_blocks_kernel<k(), MODE>), dim3(grid), dim3(TPB), 0, c->stream, vars, G.data.p, G.voff.p, boff ? boff : c->app.boff[g].p, G.ncost, G.rk, nvec, in, in_stride, out, out_stride);
                return true; } }, false);
     if (!known) { c->err = "matrix-free products: no kernel for this residual kind"; return NLLS_ERR_UNSUPPORTED; }
@@ -374,6 +386,13 @@ int enqueue_diag_blocks(nlls_ctx* c, int which) {
     for (size_t g = 0; g < c->groups.size(); ++g) { rc = launch_blocks<APP_DIAG>(c, g, which, 1, nullptr, 0, X.rec.p + X.gbase_diag[g], X.rec_diag); if (rc != NLLS_OK) return rc; }
     return NLLS_OK;
 }
+// the off-diagonal records of one group (Schur-Jacobi, nlls_schur_apply.hip): the sizes the host index needs, and the launch
+bool apply_offd_dims(int kind, int& nd, int& od, int* dof) {
+    if (is_dyn_kind(kind)) return false;
+    return dispatch_res(kind, [&](auto k) { using S = AppSize<k()>; nd = S::ND; od = S::OD; for (int s = 0; s < S::ND; ++s) dof[s] = S::dof(s); return true; }, false);
+}
+int enqueue_offd_blocks(nlls_ctx* c, size_t g, int which, double* d_out) { return launch_blocks<APP_OFFD>(c, g, which, 1, nullptr, 0, d_out, 0); }
+int apply_need_records(nlls_ctx* c, int64_t doubles) { int chunk = 1; return apply_scratch(c, doubles, 1, chunk); }
 int enqueue_hess_blocks(nlls_ctx* c, size_t g, int which, int nvec, const uint32_t* boff, const double* d_in, int64_t in_stride) {
     return launch_blocks<APP_HESS>(c, g, which, nvec, d_in, in_stride, c->app.rec.p + c->app.gbase_vec[g], c->app.rec_vec, boff);
 }

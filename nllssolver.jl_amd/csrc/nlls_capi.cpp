@@ -524,14 +524,19 @@ int nlls_solve(nlls_ctx* ctx, double* x_out) { NLLS_API_BEGIN
     NLLS_API_END(ctx)
 }
 // The iteration's own arguments: the one condition of nlls_solve_pcg, nlls_solve_pcg_rhs and nlls_marginal_cov
-static bool pcg_iteration_args_ok(int32_t precond, int32_t maxiters, double rtol) {
-    return (precond == NLLS_PCG_PRECOND_NONE || precond == NLLS_PCG_PRECOND_BLOCK_JACOBI) && maxiters >= 1 && std::isfinite(rtol) && rtol >= 0;
+static bool pcg_iteration_args_ok(int32_t precond, int32_t maxiters, double rtol, bool reduced = false) {
+    return (precond == NLLS_PCG_PRECOND_NONE || precond == NLLS_PCG_PRECOND_BLOCK_JACOBI || (reduced && precond == NLLS_PCG_PRECOND_SCHUR_JACOBI)) && maxiters >= 1 && std::isfinite(rtol) && rtol >= 0;
+}
+// NLLS_PCG_PRECOND_SCHUR_JACOBI where there is no reduced system: refused like any bad preconditioner, and the text says where it belongs
+static std::string pcg_bad_args(const char* name, int32_t precond, const char* what) {
+    if (precond == NLLS_PCG_PRECOND_SCHUR_JACOBI) return std::string(name) + ": NLLS_PCG_PRECOND_SCHUR_JACOBI belongs to the reduced system: it preconditions nlls_solve_pcg_schur only";
+    return std::string(name) + ": bad " + what;
 }
 // The same solve by conjugate gradients on the matrix-free operator (nlls_pcg.hip): (H + lambda I) y = b from y = 0, x = -y.  Everything is refused here, before anything is
 // enqueued; the solver's rounds synchronise.  On success the transition nlls_set_step makes (step_replaced, inside pcg_solve); a breakdown leaves x as it was.
 int nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out) { NLLS_API_BEGIN
     if (!ctx) return NLLS_ERR_INVALID_ARG;
-    if (!pcg_iteration_args_ok(precond, maxiters, rtol)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg: bad preconditioner, maxiters or rtol");
+    if (!pcg_iteration_args_ok(precond, maxiters, rtol)) return fail(ctx, NLLS_ERR_INVALID_ARG, pcg_bad_args("nlls_solve_pcg", precond, "preconditioner, maxiters or rtol"));
     NEED_GRAD_LAZY();
     TRY(apply_check(ctx, "nlls_solve_pcg", -1, false));
     if (ctx->info.ndof == 0) { ctx->pcg_iters = ctx->pcg_status = ctx->pcg_rounds = 0; if (stats_out) for (int k = 0; k < 8; ++k) stats_out[k] = 0.0; return NLLS_OK; }
@@ -543,7 +548,7 @@ int nlls_solve_pcg(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol
 // no event of nlls_state.hpp, nothing of the last nlls_solve_pcg's counters.  Everything is refused here, before anything is enqueued or written.
 static int pcg_cols_check(nlls_ctx* ctx, const char* name, int32_t which, double lambda, int32_t precond, int32_t maxiters, double rtol) {
     if (!valid_set(which) || !std::isfinite(lambda) || !pcg_iteration_args_ok(precond, maxiters, rtol))
-        return fail(ctx, NLLS_ERR_INVALID_ARG, std::string(name) + ": bad variable set, lambda, preconditioner, maxiters or rtol");
+        return fail(ctx, NLLS_ERR_INVALID_ARG, pcg_bad_args(name, precond, "variable set, lambda, preconditioner, maxiters or rtol"));
     return NLLS_OK;
 }
 int nlls_solve_pcg_rhs(nlls_ctx* ctx, int32_t which, double lambda, int32_t precond, int32_t maxiters, double rtol, int32_t nrhs, const double* B, double* X_out, double* stats_out) { NLLS_API_BEGIN
@@ -596,7 +601,7 @@ static int schur_product(nlls_ctx* ctx, const char* name, int mode, int32_t whic
     HIP_TRY(ctx, hipMemsetAsync(Z.scal.p, 0, sizeof(double) * PCG_NSCAL, ctx->stream));
     if (na) HIP_TRY(ctx, hipMemcpyAsync(io, a, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
     if (ny) HIP_TRY(ctx, hipMemcpyAsync(io + na, yr, sizeof(double) * ny, hipMemcpyHostToDevice, ctx->stream));
-    TRY(enqueue_schur_setup(ctx, which, lambda, false, Z.Cinv.p, Z.scal.p, nullptr));
+    TRY(enqueue_schur_setup(ctx, which, lambda, SCHUR_R_NONE, Z.Cinv.p, Z.scal.p, nullptr));
     TRY(enqueue_schur_op(ctx, mode, which, lambda, Z.Cinv.p, nvec, io, io + na, io + na + ny));
     HIP_TRY(ctx, hipMemcpyAsync(st, Z.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -634,10 +639,40 @@ int nlls_schur_expand(nlls_ctx* ctx, int32_t which, double lambda, int32_t nvec,
     return schur_product(ctx, "nlls_schur_expand", SCHUR_EXPAND, which, lambda, nvec, b, yr, y_out);
     NLLS_API_END(ctx)
 }
+// The diagonal blocks of S(lambda), unfactored (nlls_schur_apply.hip, enqueue_schur_setup under SCHUR_R_S): the rules of the products -- refused before anything is built
+// or enqueued, the e factor's status home before a byte is copied out, read only.  The set-up is no product: the products' statistics (nlls_get_solve_stats [47..50])
+// keep describing the last product.
+int nlls_schur_block_diag(nlls_ctx* ctx, int32_t which, double lambda, double* d_out) { NLLS_API_BEGIN
+    if (!ctx || !d_out) return NLLS_ERR_INVALID_ARG;
+    NEED_READY();
+    if (!valid_set(which) || !std::isfinite(lambda)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_schur_block_diag: bad variable set or lambda");
+    TRY(schur_check(ctx, "nlls_schur_block_diag"));
+    TRY(schur_prepare(ctx));
+    SchurIndex& Z = ctx->sch;
+    if (Z.nred == 0) return NLLS_OK;        // (every unfixed block eliminated: there is no reduced block)
+    size_t no = 0; for (size_t b = 0; b < ctx->blocksizes.size(); ++b) if (!ctx->is_elim[b]) no += (size_t)ctx->blocksizes[b] * (size_t)ctx->blocksizes[b];
+    auto need = [&](DevBuf<double>& buf, size_t n, const char* what) -> int {
+        if (buf.n >= n && buf.p) return NLLS_OK;
+        const hipError_t e = buf.alloc(n); if (e != hipSuccess) { buf.release(); (void)hipGetLastError(); return hip_fail(ctx, e, (std::string("nlls_schur_block_diag: ") + what).c_str()); }
+        return NLLS_OK; };
+    TRY(need(Z.io, std::max<size_t>(no, 1), "staging for the blocks")); TRY(need(Z.Cinv, (size_t)std::max<int64_t>(apply_diag_len(ctx), 1), "the eliminated blocks' inverses")); TRY(need(Z.scal, PCG_NSCAL, "the factor's status"));
+    double st[PCG_NSCAL] = {0, 0, 0, 0, 0, 0, 0, 0}; const int64_t scratch = ctx->app_scratch;
+    HIP_TRY(ctx, hipMemsetAsync(Z.scal.p, 0, sizeof(double) * PCG_NSCAL, ctx->stream));
+    const int rc = enqueue_schur_setup(ctx, which, lambda, SCHUR_R_S, Z.Cinv.p, Z.scal.p, nullptr, Z.io.p);
+    ctx->app_scratch = scratch;
+    TRY(rc);
+    HIP_TRY(ctx, hipMemcpyAsync(st, Z.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (st[PCG_STATUS] != 0.0) return fail(ctx, NLLS_ERR_NOT_SPD, "nlls_schur_block_diag: an eliminated block C_e + lambda I is not positive definite");
+    HIP_TRY(ctx, hipMemcpyAsync(d_out, Z.io.p, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return NLLS_OK;
+    NLLS_API_END(ctx)
+}
 // nlls_solve_pcg on the reduced system: refused as it refuses, and where nothing was eliminated; the transition nlls_set_step makes on success (inside pcg_solve_schur)
 int nlls_solve_pcg_schur(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double* x_out, double* stats_out) { NLLS_API_BEGIN
     if (!ctx) return NLLS_ERR_INVALID_ARG;
-    if (!pcg_iteration_args_ok(precond, maxiters, rtol)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg_schur: bad preconditioner, maxiters or rtol");
+    if (!pcg_iteration_args_ok(precond, maxiters, rtol, /*reduced=*/true)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg_schur: bad preconditioner, maxiters or rtol");
     NEED_GRAD_LAZY();
     TRY(schur_check(ctx, "nlls_solve_pcg_schur"));
     TRY(ensure_grad(ctx, 2)); TRY(ensure_reduced_summed(ctx));      // (b as nlls_get_grad reads it)
@@ -647,7 +682,7 @@ int nlls_solve_pcg_schur(nlls_ctx* ctx, int32_t precond, int32_t maxiters, doubl
 // nlls_solve_pcg inside a trust region (Steihaug-Toint; nlls_pcg.hip, pcg_solve_tr): refused as it refuses, and for a radius that is no radius; +inf is one
 int nlls_solve_pcg_tr(nlls_ctx* ctx, int32_t precond, int32_t maxiters, double rtol, double radius, double* x_out, double* stats_out) { NLLS_API_BEGIN
     if (!ctx) return NLLS_ERR_INVALID_ARG;
-    if (!pcg_iteration_args_ok(precond, maxiters, rtol) || !(radius > 0.0)) return fail(ctx, NLLS_ERR_INVALID_ARG, "nlls_solve_pcg_tr: bad preconditioner, maxiters, rtol or radius");
+    if (!pcg_iteration_args_ok(precond, maxiters, rtol) || !(radius > 0.0)) return fail(ctx, NLLS_ERR_INVALID_ARG, pcg_bad_args("nlls_solve_pcg_tr", precond, "preconditioner, maxiters, rtol or radius"));
     NEED_GRAD_LAZY();
     TRY(apply_check(ctx, "nlls_solve_pcg_tr", -1, false));
     if (ctx->info.ndof == 0) { if (stats_out) for (int k = 0; k < 8; ++k) stats_out[k] = 0.0; return NLLS_OK; }

@@ -243,8 +243,27 @@ struct SchurClass {
     DevBuf<LongItem> items; DevBuf<BigRow> big;
     int64_t nshort = 0, nlongel = 0, ndshort = 0, nitems = 0, nbig = 0, nlong = 0; uint32_t nslots = 0; int part_w = 1, part_w_diag = 1;
 };
+// The diagonal blocks of S (NLLS_PCG_PRECOND_SCHUR_JACOBI, nlls_schur_block_diag): per reduced block its distinct eliminated neighbours in ascending block order (a
+// PAIR each), per pair the off-diagonal record blocks that join the two, in ascending (group, block, slot) order.  Built on the host at the first call that needs it
+// after an upload; the item lists again when NLLS_OPT_APPLY_WAVE_MIN changes.  A row without a pair is in no list: no lane is launched for it.
+struct SjTerm { uint32_t off, tr; };               // where the block starts in the off-diagonal records; tr: the r slot comes behind the e slot, the stored block is E_ie'
+struct SjPair { uint32_t e, t0, t1; };             // the eliminated block, its terms [t0, t1)
+struct SchurJacobiIndex {
+    bool ready = false; int64_t wave_min_built = -1;
+    std::vector<int64_t> gbase;                    // per group: first double of its off-diagonal records
+    std::vector<uint8_t> has_offd;                 // per group: it has cost blocks and its kind more than one slot -- an off-diagonal record launch
+    int64_t rec_offd = 0, nrd2 = 0;                // doubles of all off-diagonal records; of the reduced blocks (nlls_schur_block_diag's output)
+    std::vector<uint32_t> h_prow;                  // [nblocks + 1] the pairs of every block row (an eliminated row has none)
+    std::vector<SjPair> h_pairs;
+    DevBuf<uint32_t> prow, rstart;                 // rstart: per block, where a reduced block starts in nlls_schur_block_diag's output
+    DevBuf<SjPair> pairs; DevBuf<SjTerm> terms;
+    DevBuf<ShortElem> shorts; DevBuf<LongItem> items; DevBuf<BigRow> big;      // the row classes of classify_rows over the r rows that have pairs; an item's [p0, p1) are PAIRS
+    int64_t nshort = 0, nitems = 0, nbig = 0; uint32_t nslots = 0; int part_w = 1, ntri = 1;      // ntri: entries of the largest wavefront row's upper triangle
+    int64_t launches = 0;                          // of the last set-up: what Schur-Jacobi adds to block Jacobi's
+};
 struct SchurIndex {
     bool ready = false; int64_t nred = 0, nedof = 0, wave_min_built = -1;
+    SchurJacobiIndex sj;
     std::vector<DevBuf<uint32_t>> boff1, boff2;    // per cost group [ncost][ndeps]
     DevBuf<uint32_t> cstart, erow_r;               // per block: its start in the permuted layout; per reduced unknown: its block (PcgArgs::erow)
     SchurClass cls[2];

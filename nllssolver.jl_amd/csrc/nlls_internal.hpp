@@ -112,12 +112,19 @@ int enqueue_diag_blocks(nlls_ctx* c, int which);      // every group's diagonal-
 int apply_records(nlls_ctx* c, int nvec, int& chunk);
 int enqueue_hess_blocks(nlls_ctx* c, size_t g, int which, int nvec, const uint32_t* boff, const double* d_in, int64_t in_stride);
 // products with S(lambda) = B + lambda I - E (C + lambda I)^-1 E' over the upload's eliminated set (nlls_schur_apply.hip): device pointers, on c->stream, no synchronisation.
-// schur_check: NLLS_OK, or the status with nlls_last_error set (what apply_check refuses; nothing eliminated).  schur_prepare builds the r/e index.  enqueue_schur_setup
-// leaves the inverses of the e blocks of H + lambda I (with_r: of the r blocks too) in d_Minv, nlls_hess_block_diag's layout, and status 3 in d_scal where one has no factor.
+// schur_check: NLLS_OK, or the status with nlls_last_error set (what apply_check refuses; nothing eliminated).  schur_prepare builds the r/e index.
 enum { SCHUR_APPLY = 0, SCHUR_REDUCE = 1, SCHUR_EXPAND = 2 };
 int schur_check(nlls_ctx* c, const char* name);
 int schur_prepare(nlls_ctx* c);
-int enqueue_schur_setup(nlls_ctx* c, int which, double lambda, bool with_r, double* d_Minv, double* d_scal, int64_t* launches);
+// enqueue_schur_setup leaves the inverses of the e blocks of H + lambda I in d_Minv, nlls_hess_block_diag's layout, and status 3 in d_scal where a block has no factor;
+// r_blocks says what becomes of the r class: nothing; the blocks of B + lambda I, inverted (block Jacobi); the blocks of S(lambda) (Schur-Jacobi) -- inverted in d_Minv,
+// or, with d_sout set, left UNFACTORED in d_sout in nlls_schur_block_diag's layout (SchurJacobiIndex::rstart) while d_Minv holds the e blocks' inverses alone.
+enum { SCHUR_R_NONE = 0, SCHUR_R_B = 1, SCHUR_R_S = 2 };
+int enqueue_schur_setup(nlls_ctx* c, int which, double lambda, int r_blocks, double* d_Minv, double* d_scal, int64_t* launches, double* d_sout = nullptr);
+// the off-diagonal records (nlls_apply.hip, the block launch's fifth mode): sizes per kind, and group g's records at vars[which] to d_out
+bool apply_offd_dims(int kind, int& nd, int& od, int* dof /* MAX_SLOTS */);
+int enqueue_offd_blocks(nlls_ctx* c, size_t g, int which, double* d_out);
+int apply_need_records(nlls_ctx* c, int64_t doubles);      // ApplyIndex::rec holds at least this many
 //   SCHUR_APPLY   a = v (nvec x nred)                       out = S v (nvec x nred)
 //   SCHUR_REDUCE  a = b (nvec x ndof)                       out = b_r - E (C + lambda I)^-1 b_e (nvec x nred)
 //   SCHUR_EXPAND  a = b (nvec x ndof), yr (nvec x nred)     out (nvec x ndof): yr on the r entries, (C + lambda I)^-1 (b_e - E' yr) on the e entries

@@ -257,7 +257,7 @@ int64_t product_launches(const nlls_ctx* c) {
 // The driver of the three entry points: the only place that allocates, launches and loops.  The caller has checked the arguments.  stats: 4 * ncols + 4 doubles (may be null)
 int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     constexpr int MAXC = NLLS_APPLY_MAX_VEC;
-    const int64_t ndof = k.schur ? c->sch.nred : c->info.ndof, ncols = k.ncols; const int maxiters = k.maxiters; const bool jacobi = k.precond == NLLS_PCG_PRECOND_BLOCK_JACOBI; const std::string nm(k.name);
+    const int64_t ndof = k.schur ? c->sch.nred : c->info.ndof, ncols = k.ncols; const int maxiters = k.maxiters; const bool sjacobi = k.schur && k.precond == NLLS_PCG_PRECOND_SCHUR_JACOBI, jacobi = k.precond == NLLS_PCG_PRECOND_BLOCK_JACOBI || sjacobi; const std::string nm(k.name);      // (Schur-Jacobi IS block Jacobi to the seven kernels: only the set-up differs)
     const double* const B = k.B; const bool step = k.d_b != nullptr, units = k.rows != nullptr;
     PcgState& S = c->pcg; const int cap = (int)std::min<int64_t>(ncols, MAXC);
     auto need = [&](auto& buf, size_t n, const char* what) -> int {
@@ -289,8 +289,9 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     a.pa = S.part.p; a.pb = S.part.p + S.pw; a.pc = S.part.p + 2 * S.pw; a.pstride = 3 * S.pw; a.scal = S.scal.p;
     const double* rhs = k.d_b;
     if (k.schur) {      // the reduced system (the caller has built its index: schur_prepare): the e blocks' inverses -- the operator needs them under either preconditioner -- the
-                        // r blocks' under block Jacobi, the reduced layout for the vector kernels, and s = reduce(b) as the one right-hand side
-        rc = enqueue_schur_setup(c, k.which, k.lambda, jacobi, S.Minv.p, fscal, &launches); if (rc != NLLS_OK) return rc;
+                        // r blocks' under block Jacobi (of B + lambda I) or Schur-Jacobi (of S itself), the reduced layout for the vector kernels, and s = reduce(b) as the
+                        // one right-hand side
+        rc = enqueue_schur_setup(c, k.which, k.lambda, sjacobi ? SCHUR_R_S : (jacobi ? SCHUR_R_B : SCHUR_R_NONE), S.Minv.p, fscal, &launches); if (rc != NLLS_OK) return rc;
         a.erow = c->sch.erow_r.p; a.start = c->sch.cstart.p; a.dstart = c->app.start_diag.p; a.bsz = c->d_blocksizes.p;
         rc = enqueue_schur_op(c, SCHUR_REDUCE, k.which, k.lambda, S.Minv.p, 1, k.d_b, nullptr, c->sch.sred.p); if (rc != NLLS_OK) return rc; launches += c->sch.launches;
         rhs = c->sch.sred.p;
@@ -379,7 +380,7 @@ int pcg_solve_cols(nlls_ctx* c, const PcgCall& k, double* stats) {
     tail[0] = (double)syncs; tail[1] = (double)launches; tail[2] = (double)products; tail[3] = (double)batches;
     if (stats) std::copy(st.begin(), st.end(), stats);
     if (bad) {
-        c->err = bad_status == 3 ? nm + (k.schur ? ": an eliminated block C_e + lambda I -- or, under block Jacobi, a diagonal block of B + lambda I -- is not positive definite (status 3)"
+        c->err = bad_status == 3 ? nm + (k.schur ? ": an eliminated block C_e + lambda I -- or, under block Jacobi, a diagonal block of B + lambda I; under Schur-Jacobi, of S -- is not positive definite (status 3)"
                                                  : ": a diagonal block of H + lambda I is not positive definite (status 3)")
                                  : nm + ": p'(H + lambda I)p is not positive, or a scalar of the recurrence is not finite (status 2, column " + std::to_string(bad_col) + ")";
         return NLLS_ERR_NOT_SPD;
@@ -433,7 +434,7 @@ static int pcg_solve_schur_empty(nlls_ctx* c, double* x_out, double* stats) {
     rc = need(S.scal, (size_t)((NLLS_APPLY_MAX_VEC + 1) * PCG_NSCAL), "nlls_solve_pcg_schur: the scalars"); if (rc != NLLS_OK) return rc;
     rc = need(c->sch.full, (size_t)ndof, "nlls_solve_pcg_schur: the expanded solution"); if (rc != NLLS_OK) return rc;
     HIPCHK(hipMemsetAsync(S.scal.p, 0, sizeof(double) * PCG_NSCAL, c->stream));
-    rc = enqueue_schur_setup(c, NLLS_VARS_CURRENT, c->lambda, false, S.Minv.p, S.scal.p, &launches); if (rc != NLLS_OK) return rc;
+    rc = enqueue_schur_setup(c, NLLS_VARS_CURRENT, c->lambda, SCHUR_R_NONE, S.Minv.p, S.scal.p, &launches); if (rc != NLLS_OK) return rc;
     rc = enqueue_schur_op(c, SCHUR_EXPAND, NLLS_VARS_CURRENT, c->lambda, S.Minv.p, 1, c->b.p, nullptr, c->sch.full.p); if (rc != NLLS_OK) return rc; launches += c->sch.launches;
     HIPCHK(hipMemcpyAsync(h, S.scal.p, sizeof(double) * PCG_NSCAL, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

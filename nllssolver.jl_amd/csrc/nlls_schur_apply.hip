@@ -15,7 +15,8 @@
 //   pass 2   blocks again on [v ; w] (table boff2, the permuted layout of SchurIndex::z), then a gather over the R ROWS ONLY, plus lambda v.
 // reduce and expand are the same pieces: w = (C + lambda I)^-1 (-b_e - 0) and pass 2 on [0 ; w] plus b_r; pass 1 on yr and (C + lambda I)^-1 (b_e - t_e).
 // The set-up of a call gathers, with the same three kernels in their `diag` form, the diagonal blocks of H + lambda I of the e class (under block Jacobi: of the r class
-// too) from 4.11's diagonal-block records, and the factor launch of nlls_pcg.hip inverts them in place; a class nobody asked for is not gathered.
+// too) from 4.11's diagonal-block records, and the factor launch of nlls_pcg.hip inverts them in place; a class nobody asked for is not gathered.  Under Schur-Jacobi
+// three kernels of their own subtract, from every reduced block, E (C + lambda I)^-1 E' over its eliminated neighbours before that launch: the diagonal blocks of S.
 // Every sum has the order of nlls_apply.hip: a row's incidences in ascending (group, block, slot) order, a wavefront row by lane stride 64 and wave_sum's tree, a cut row
 // segment by segment.  No atomics.  The k loops are run-time loops over one body: vector k of a call of many carries the bits of a call of its own, and so does a chunk.
 // Built like nlls_apply.hip, WITHOUT -fno-honor-nans / -fno-signed-zeros.
@@ -109,6 +110,76 @@ __global__ __launch_bounds__(TPB) void schur_cut_kernel(SchurGather a) {
         a.y[(int64_t)k * a.y_stride + a.ostart[br.row] + q] = schur_tail(a, k, br.row, q, s); }
 }
 
+// ---- the diagonal blocks of S(lambda) (Schur-Jacobi, nlls_schur_block_diag) ---------------------------------------------------------
+// Entry (a, b) of reduced block `row`, in place: y[ostart[row] + a + b d] -= sum over the row's pairs of sum_k Ebar[a, k] (sum_l W[k, l] Ebar[b, l]), with W the pair's
+// eliminated block's inverse (Minv + wstart[e]) and Ebar[a, k] the pair's terms, entry (a, k) of each (the transpose where SjTerm::tr says so), summed in list order
+// BEFORE the product.  y holds the block of B + lambda I the gather in front left there.  Block sizes are run-time values and nothing is indexed by them: Ebar is summed
+// again where it is needed, d_e (d_e + 1) sums a pair and entry.  Entries (a, b) and (b, a) are both computed as (min, max): what is subtracted is symmetric to the bit.
+struct SjArgs {
+    const uint32_t* prow; const SjPair* pairs; const SjTerm* terms; const int32_t* bsz; const uint32_t* wstart;
+    const ShortElem* el; int64_t nel; const LongItem* items; int64_t nitems; const BigRow* big; int64_t nbig;
+    const double* rec; const double* Minv; double* y; const uint32_t* ostart; double* part; int part_w;
+    int ntri;      // entries of the upper triangle of the largest wavefront row: the wavefronts launched per item
+};
+NLLS_DEV double sj_ebar(const SjArgs& g, uint32_t t0, uint32_t t1, uint32_t a, uint32_t k, uint32_t dr, uint32_t de) {
+    double s = 0;
+    for (uint32_t t = t0; t < t1; ++t) { const SjTerm m = g.terms[t]; s += g.rec[m.off + (m.tr ? k + a * de : a + k * dr)]; }
+    return s;
+}
+NLLS_DEV double sj_pair(const SjArgs& g, uint32_t p, uint32_t a, uint32_t b, uint32_t dr) {
+    const SjPair pr = g.pairs[p]; const uint32_t de = (uint32_t)g.bsz[pr.e];
+    const double* __restrict__ w = g.Minv + g.wstart[pr.e];
+    double s = 0;
+    for (uint32_t k = 0; k < de; ++k) { double u = 0;
+        for (uint32_t l = 0; l < de; ++l) u += w[k + l * de] * sj_ebar(g, pr.t0, pr.t1, b, l, dr, de);
+        s += sj_ebar(g, pr.t0, pr.t1, a, k, dr, de) * u; }
+    return s;
+}
+// rows subtracted one lane per entry: the row's pairs in order
+__global__ __launch_bounds__(TPB) void schur_sj_rows_kernel(SjArgs g) {
+    const int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (i >= g.nel) return;
+    const ShortElem se = g.el[i]; const uint32_t row = se.row, dr = (uint32_t)g.bsz[row], a = se.q % dr, b = se.q / dr, lo = a < b ? a : b, hi = a < b ? b : a;
+    double s = 0;
+    for (uint32_t p = g.prow[row]; p < g.prow[row + 1]; ++p) s += sj_pair(g, p, lo, hi, dr);
+    const int64_t o = (int64_t)g.ostart[row] + se.q;
+    g.y[o] = g.y[o] - s;
+}
+// rows that take wavefronts: a wavefront per item AND entry of the upper triangle (entry t lies in column b, row a = t - b (b + 1) / 2), lanes striding the item's
+// pairs, lane 0 storing both mirror entries -- a whole row in place, a segment of a cut row to `part`.  The entries of a row are independent sums: taken in sequence by
+// one wavefront per item they took 2.13 ms on 1 000 wavefronts at ba_1kx100k, spread like this 1.37 ms (notes/r26.md); an entry's sum, and so its bits, is the same either way.
+__global__ __launch_bounds__(TPB) void schur_sj_wave_kernel(SjArgs g) {
+    const int64_t w = (int64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (w >= g.nitems * g.ntri) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const LongItem it = g.items[w / g.ntri]; const uint32_t row = it.row, dr = (uint32_t)g.bsz[row], t = (uint32_t)(w % g.ntri);
+    uint32_t b = 0; while ((b + 1) * (b + 2) / 2 <= t) ++b;
+    const uint32_t a = t - b * (b + 1) / 2;
+    if (b >= dr) return;          // (a row smaller than the largest; the whole wavefront leaves)
+    {
+        double s = 0;
+        for (uint32_t p = it.p0 + lane; p < it.p1; p += 64) s += sj_pair(g, p, a, b, dr);
+        s = wave_sum(s);
+        if (lane == 0) { const uint32_t q1 = a + b * dr, q2 = b + a * dr;
+            if (it.slot == DEST_NONE) { const int64_t o = (int64_t)g.ostart[row];
+                g.y[o + q1] = g.y[o + q1] - s;
+                if (q2 != q1) g.y[o + q2] = g.y[o + q2] - s; }
+            else { double* pt = g.part + (int64_t)it.slot * g.part_w; pt[q1] = s; pt[q2] = s; } }
+    }
+}
+// one lane per (cut row, entry): the row's segments in order
+__global__ __launch_bounds__(TPB) void schur_sj_cut_kernel(SjArgs g) {
+    const int64_t t = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    const int64_t b = t / g.part_w; const uint32_t q = (uint32_t)(t - b * g.part_w);
+    if (b >= g.nbig) return;
+    const BigRow br = g.big[b];
+    if (q >= (uint32_t)(g.bsz[br.row] * g.bsz[br.row])) return;
+    double s = 0;
+    for (uint32_t i = 0; i < br.nslots; ++i) s += g.part[(int64_t)(br.slot0 + i) * g.part_w + q];
+    const int64_t o = (int64_t)g.ostart[br.row] + q;
+    g.y[o] = g.y[o] - s;
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -199,20 +270,114 @@ int schur_prepare(nlls_ctx* c) {
     return schur_classify(c);
 }
 
-// (C_e + lambda I)^-1 for the e blocks -- and (B_r + lambda I)^-1 for the r blocks, block Jacobi of the reduced system -- from the diagonal blocks of H + lambda I
-int enqueue_schur_setup(nlls_ctx* c, int which, double lambda, bool with_r, double* d_Minv, double* d_scal, int64_t* launches) {
+// The index of Schur-Jacobi, once per upload (behind schur_prepare): for every reduced block its pairs, for every pair its terms; then the row classes under the
+// threshold the context holds now.  Only a cost block's slot pairs with ONE reduced and ONE eliminated variable count: a fixed slot contributes nothing, two reduced
+// slots would be off-diagonal fill of S, two eliminated ones do not exist (the set is independent).
+namespace {
+struct SjHostTerm { uint32_t row, e; SjTerm t; };
+int schur_sj_classify(nlls_ctx* c) {
+    SchurJacobiIndex& J = c->sch.sj;
+    const int64_t wm = std::max<int64_t>(c->app_wave_min, 1);
+    if (J.wave_min_built == wm) return NLLS_OK;
+    std::vector<uint32_t> rows;                                   // the r rows with something to subtract
+    for (const uint32_t b : c->sch.cls[0].blocks) if (J.h_prow[b + 1] > J.h_prow[b]) rows.push_back(b);
+    RowClasses R; classify_rows(c, rows.data(), rows.size(), wm, R);      // the products' rule decides lane or wavefront; the items here run over PAIRS, and a row is cut by its TERMS
+    std::vector<ShortElem> sh; std::vector<LongItem> items; std::vector<BigRow> big; uint32_t nslots = 0; int part_w = 1, ntri = 1;
+    for (const uint32_t b : R.short_rows) { const uint32_t d = (uint32_t)c->blocksizes[b]; for (uint32_t q = 0; q < d * d; ++q) sh.push_back(ShortElem{b, q}); }
+    for (const uint32_t b : R.long_rows) { const uint32_t p0 = J.h_prow[b], p1 = J.h_prow[b + 1];
+        ntri = std::max(ntri, (int)c->blocksizes[b] * ((int)c->blocksizes[b] + 1) / 2);
+        if (p1 == p0 || J.h_pairs[p1 - 1].t1 - J.h_pairs[p0].t0 <= APP_SEGMENT) { items.push_back(LongItem{b, p0, p1, DEST_NONE}); continue; }      // (a row's terms are contiguous)
+        BigRow br{b, nslots, 0};                                  // more than APP_SEGMENT terms: a cut row, a segment ends behind the pair that brings its terms to APP_SEGMENT
+        for (uint32_t p = p0; p < p1;) { uint32_t q = p, nt = 0;
+            while (q < p1 && nt < APP_SEGMENT) { nt += J.h_pairs[q].t1 - J.h_pairs[q].t0; ++q; }
+            items.push_back(LongItem{b, p, q, nslots++}); ++br.nslots; p = q; }
+        big.push_back(br); part_w = std::max(part_w, (int)c->blocksizes[b] * (int)c->blocksizes[b]); }
+    HIPCHK(J.shorts.upload(sh)); HIPCHK(J.items.upload(items)); HIPCHK(J.big.upload(big));
+    J.nshort = (int64_t)sh.size(); J.nitems = (int64_t)items.size(); J.nbig = (int64_t)big.size(); J.nslots = nslots; J.part_w = part_w; J.ntri = ntri;
+    J.wave_min_built = wm;
+    return NLLS_OK;
+}
+int schur_sj_prepare(nlls_ctx* c) {
+    SchurIndex& Z = c->sch; SchurJacobiIndex& J = Z.sj; const ApplyIndex& X = c->app;
+    if (!J.ready) {
+        const size_t nb = c->blocksizes.size(), ng = c->groups.size(); const int64_t ndof = c->info.ndof;
+        std::vector<uint32_t> blk_at((size_t)ndof, 0), rstart(nb, DEST_NONE);
+        uint64_t nr2 = 0;
+        for (size_t b = 0; b < nb; ++b) { blk_at[(size_t)c->boffsets[b]] = (uint32_t)b;
+            if (!c->is_elim[b]) { rstart[b] = (uint32_t)nr2; nr2 += (uint64_t)c->blocksizes[b] * (uint64_t)c->blocksizes[b]; } }
+        J.gbase.assign(ng, 0); J.has_offd.assign(ng, 0); uint64_t ro = 0;
+        std::vector<SjHostTerm> ht;
+        for (size_t g = 0; g < ng; ++g) { const Group& G = c->groups[g]; int nd = 0, od = 0, dof[MAX_SLOTS] = {};
+            if (!apply_offd_dims(G.res_kind, nd, od, dof)) { c->err = "the diagonal blocks of S: a dynamic-size kind has no per-block Hessian"; return NLLS_ERR_UNSUPPORTED; }
+            J.gbase[g] = (int64_t)ro; J.has_offd[g] = G.ncost > 0 && od > 0;
+            const size_t n = (size_t)G.ncost * (size_t)nd; if (!n || !od || !X.boff[g].p) continue;
+            if (ro + (uint64_t)G.ncost * (uint64_t)od > 0xFFFFFFF0ull) { c->err = "the diagonal blocks of S: the off-diagonal records exceed 32-bit offsets"; return NLLS_ERR_UNSUPPORTED; }
+            std::vector<uint32_t> bo(n);
+            HIPCHK(hipMemcpy(bo.data(), X.boff[g].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));      // (written once, by apply_prepare)
+            for (int64_t k = 0; k < G.ncost; ++k) { uint32_t po = 0;
+                for (int s = 0; s < nd; ++s) for (int t = s + 1; t < nd; ++t) { const uint32_t at = po; po += (uint32_t)(dof[s] * dof[t]);
+                    const uint32_t os = bo[(size_t)k * nd + s], ot = bo[(size_t)k * nd + t];
+                    if (os == DEST_NONE || ot == DEST_NONE) continue;
+                    const uint32_t bs = blk_at[os], bt = blk_at[ot]; const bool es = c->is_elim[bs] != 0, et = c->is_elim[bt] != 0;
+                    if (es == et) continue;
+                    // slot s reduced: the stored block, rows of slot s, is E_ie; slot t reduced: it is E_ie'
+                    ht.push_back(SjHostTerm{es ? bt : bs, es ? bs : bt, SjTerm{(uint32_t)(ro + (uint64_t)k * od + at), es ? 1u : 0u}}); } }
+            ro += (uint64_t)G.ncost * (uint64_t)od; }
+        if (ht.size() > 0xFFFFFFF0ull) { c->err = "the diagonal blocks of S: the terms exceed 32-bit offsets"; return NLLS_ERR_UNSUPPORTED; }
+        // (ht is in ascending (group, block, slot pair) order: a stable sort by (row, e) keeps that order inside a pair)
+        std::stable_sort(ht.begin(), ht.end(), [](const SjHostTerm& x, const SjHostTerm& y) { return x.row != y.row ? x.row < y.row : x.e < y.e; });
+        std::vector<SjTerm> terms(ht.size()); J.h_pairs.clear(); J.h_prow.assign(nb + 1, 0);
+        for (size_t i = 0; i < ht.size(); ++i) { terms[i] = ht[i].t;
+            if (i == 0 || ht[i].row != ht[i - 1].row || ht[i].e != ht[i - 1].e) { J.h_pairs.push_back(SjPair{ht[i].e, (uint32_t)i, (uint32_t)i}); ++J.h_prow[ht[i].row + 1]; }
+            J.h_pairs.back().t1 = (uint32_t)i + 1; }
+        for (size_t b = 0; b < nb; ++b) J.h_prow[b + 1] += J.h_prow[b];
+        J.rec_offd = (int64_t)ro; J.nrd2 = (int64_t)nr2;
+        HIPCHK(J.prow.upload(J.h_prow)); HIPCHK(J.pairs.upload(J.h_pairs)); HIPCHK(J.terms.upload(terms)); HIPCHK(J.rstart.upload(rstart));
+        J.wave_min_built = -1; J.ready = true;
+    }
+    return schur_sj_classify(c);
+}
+}  // namespace
+
+// (C_e + lambda I)^-1 for the e blocks, and what r_blocks asks of the r class: the inverses of the blocks of B + lambda I (block Jacobi), or the blocks of S(lambda)
+// (Schur-Jacobi) -- inverted too, or left as they are in d_sout.  One call's order: the diagonal-block records; the e gather and factor; the r gather; the off-diagonal
+// records, into the same scratch (the stream orders them behind the gathers); the subtraction; the r factor.
+int enqueue_schur_setup(nlls_ctx* c, int which, double lambda, int r_blocks, double* d_Minv, double* d_scal, int64_t* launches, double* d_sout) {
+    SchurIndex& Z = c->sch; SchurJacobiIndex& J = Z.sj; const ApplyIndex& X = c->app; const bool sj = r_blocks == SCHUR_R_S;
+    int rc;
+    if (sj) { rc = schur_sj_prepare(c); if (rc != NLLS_OK) return rc;
+              rc = apply_need_records(c, std::max(X.rec_diag, J.rec_offd)); if (rc != NLLS_OK) return rc; }      // (both sets of records before the first launch: nothing is freed under one)
+    { size_t pn = 0;
+      for (int e = 1; e >= (r_blocks ? 0 : 1); --e) pn = std::max(pn, (size_t)Z.cls[e].nslots * (size_t)Z.cls[e].part_w_diag);
+      if (sj) pn = std::max(pn, (size_t)J.nslots * (size_t)J.part_w);
+      if (pn > 0) { rc = schur_need(c, Z.part, pn, "products with the Schur complement: partial sums of the cut rows' diagonal blocks"); if (rc != NLLS_OK) return rc; } }
     // 4.11's diagonal-block records of every cost block, then nlls_hess_block_diag's gather over the classes that are wanted alone -- the same sums in the same order, so
-    // a block of d_Minv holds the bytes nlls_hess_block_diag returns for it; the blocks of a class nobody asked for are not gathered and stay unwritten
-    int rc = enqueue_diag_blocks(c, which); if (rc != NLLS_OK) return rc;
+    // a block holds the bytes nlls_hess_block_diag returns for it; the blocks of a class nobody asked for are not gathered and stay unwritten
+    rc = enqueue_diag_blocks(c, which); if (rc != NLLS_OK) return rc;
     int64_t n = 0; for (const Group& G : c->groups) n += G.ncost > 0;
-    SchurIndex& Z = c->sch; const ApplyIndex& X = c->app;
-    for (int e = 1; e >= (with_r ? 0 : 1); --e) { const SchurClass& K = Z.cls[e]; if (K.nblk == 0) continue;
-        if (K.nslots > 0) { rc = schur_need(c, Z.part, (size_t)K.nslots * (size_t)K.part_w_diag, "products with the Schur complement: partial sums of the cut rows' diagonal blocks"); if (rc != NLLS_OK) return rc; }
+    double* const rout = d_sout ? d_sout : d_Minv; const uint32_t* const rstart = d_sout ? J.rstart.p : X.start_diag.p;
+    for (int e = 1; e >= (r_blocks ? 0 : 1); --e) { const SchurClass& K = Z.cls[e]; if (K.nblk == 0) continue;
         SchurGather g = gather_base(c, K, 1);
         g.offs = X.off_diag.p; g.rec_stride = X.rec_diag; g.diag = 1; g.lambda = lambda; g.part = Z.part.p; g.part_w = K.part_w_diag;
-        g.el = K.dshorts.p; g.nel = K.ndshort; g.y = d_Minv; g.y_stride = 0; g.ostart = X.start_diag.p;
+        g.el = K.dshorts.p; g.nel = K.ndshort; g.y = e ? d_Minv : rout; g.y_stride = 0; g.ostart = e ? X.start_diag.p : rstart;
         launch_rows(c, g, n); launch_wave_rows(c, g, n);
         HIPCHK(hipGetLastError());
+        if (e == 0 && sj) {          // S_ii = B_ii + lambda I - sum over the row's pairs: the e blocks' inverses are in d_Minv by now
+            int64_t extra = 0;
+            for (size_t gi = 0; gi < c->groups.size(); ++gi) { if (!J.has_offd[gi]) continue;
+                rc = enqueue_offd_blocks(c, gi, which, X.rec.p + J.gbase[gi]); if (rc != NLLS_OK) return rc; ++extra; }
+            SjArgs a{};
+            a.prow = J.prow.p; a.pairs = J.pairs.p; a.terms = J.terms.p; a.bsz = c->d_blocksizes.p; a.wstart = X.start_diag.p;
+            a.el = J.shorts.p; a.nel = J.nshort; a.items = J.items.p; a.nitems = J.nitems; a.big = J.big.p; a.nbig = J.nbig;
+            a.rec = X.rec.p; a.Minv = d_Minv; a.y = rout; a.ostart = rstart; a.part = Z.part.p; a.part_w = J.part_w;
+            if (a.nel > 0) { hipLaunchKernelGGL(schur_sj_rows_kernel, dim3((unsigned)((a.nel + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a); ++extra; }
+            a.ntri = J.ntri;
+            if (a.nitems > 0) { hipLaunchKernelGGL(schur_sj_wave_kernel, dim3((unsigned)((a.nitems * a.ntri + TPB / 64 - 1) / (TPB / 64))), dim3(TPB), 0, c->stream, a); ++extra; }
+            if (a.nbig > 0) { hipLaunchKernelGGL(schur_sj_cut_kernel, dim3((unsigned)((a.nbig * a.part_w + TPB - 1) / TPB)), dim3(TPB), 0, c->stream, a); ++extra; }
+            HIPCHK(hipGetLastError());
+            J.launches = extra; n += extra;
+        }
+        if (e == 0 && d_sout) continue;          // (nlls_schur_block_diag: the blocks leave unfactored)
         rc = enqueue_block_factor(c, Z.cls[e].bsz.p, Z.cls[e].dstart.p, Z.cls[e].nblk, d_Minv, d_scal); if (rc != NLLS_OK) return rc; ++n; }
     if (launches) *launches += n;
     return NLLS_OK;

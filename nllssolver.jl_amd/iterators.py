@@ -23,10 +23,13 @@ class PCG:
     """NLLSOptions(linearsolver=PCG(...)): the iterators' linear solves by conjugate gradients on the device's matrix-free operator (nlls_solve_pcg) where they
     factor by default -- no reduced system, and with `maxiters` small a truncated-Newton step.  precond: "blockjacobi" (the diagonal blocks of H + lambda I) or "none";
     maxiters None: 4 ndof.  schur=True: the same on the reduced system of the upload's eliminated set (nlls_solve_pcg_schur; "blockjacobi" is then the diagonal blocks of
-    B + lambda I, rtol bounds the reduced residual); a problem without an eliminated set raises NllsError (ERR_UNSUPPORTED), it does not fall back.  A breakdown (the system is not positive definite) is what a bad pivot is to the direct solve: Levenberg-Marquardt damps more."""
+    B + lambda I, rtol bounds the reduced residual; precond "schurjacobi" -- with schur=True only, ValueError otherwise -- is the diagonal blocks of S itself, Ceres'
+    SCHUR_JACOBI); a problem without an eliminated set raises NllsError (ERR_UNSUPPORTED), it does not fall back.  A breakdown (the system is not positive definite) is what a bad pivot is to the direct solve: Levenberg-Marquardt damps more."""
 
     def __init__(self, rtol=1e-8, maxiters=None, precond="blockjacobi", schur=False):
-        assert precond in ("blockjacobi", "none") and rtol >= 0 and (maxiters is None or maxiters >= 1)
+        assert precond in ("blockjacobi", "none", "schurjacobi") and rtol >= 0 and (maxiters is None or maxiters >= 1)
+        if precond == "schurjacobi" and not schur:
+            raise ValueError('PCG(precond="schurjacobi") preconditions the reduced system: it needs schur=True')
         self.rtol, self.maxiters, self.precond, self.schur = float(rtol), maxiters, precond, bool(schur)
 
 

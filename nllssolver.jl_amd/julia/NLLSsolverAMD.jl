@@ -219,7 +219,13 @@ end
 function schurexpand!(y::AbstractVecOrMat{Float64}, ls::MultiVariateLSgpu, b::AbstractVecOrMat{Float64}, yr::AbstractVecOrMat{Float64}, λ::Real=0.0, which::Integer=0)
     check(ls.ctx, ccall((:nlls_schur_expand, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ls.ctx, which, λ, apply_nvec(b), b, yr, y)); return y
 end
-# solvepcg! on that reduced system: conjugate gradients from 0 on S yr = reduce(b), the step x = -expand(b, yr) left in ls.x.  precond 1: the diagonal blocks of B + λ I.
+# the diagonal blocks of S(λ) themselves, unfactored (nlls_schur_block_diag): the reduced blocks in ascending block order, block i at offset sum of dof^2 of the reduced
+# blocks before it, column-major -- what solvepcgschur!(precond = PCG_PRECOND_SCHUR_JACOBI) inverts, for a Krylov method of the caller's on schurapply!
+const PCG_PRECOND_SCHUR_JACOBI = 3      # (2 is unassigned; the other conjugate-gradient calls refuse 3)
+function schurblockdiag!(d::AbstractVector{Float64}, ls::MultiVariateLSgpu, λ::Real=0.0, which::Integer=0)
+    check(ls.ctx, ccall((:nlls_schur_block_diag, lib), Cint, (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}), ls.ctx, which, λ, d)); return d
+end
+# solvepcg! on that reduced system: conjugate gradients from 0 on S yr = reduce(b), the step x = -expand(b, yr) left in ls.x.  precond 1: the diagonal blocks of B + λ I; PCG_PRECOND_SCHUR_JACOBI: those of S.
 # rtol bounds the REDUCED residual.  Returns (iterations, status); a breakdown, an eliminated block without a factor included, errors and leaves the step as it was.
 function solvepcgschur!(ls::MultiVariateLSgpu; precond::Integer=1, maxiters::Integer=4 * max(ls.ndof, 1), rtol::Real=1e-8)
     stats = zeros(8)

@@ -110,6 +110,10 @@ class MultiVariateLSgpu:
         """S(lam) v, S = B + lam I - E (C + lam I)^-1 E', never formed (nlls_schur_apply)"""
         return self.ctx.schur_apply(v, lam, which)
 
+    def schur_block_diag(self, lam=0.0, which=VARS_CURRENT):
+        """the diagonal blocks of S(lam), one per reduced block, unfactored (nlls_schur_block_diag)"""
+        return self.ctx.schur_block_diag(lam, which)
+
     def schur_reduce(self, b, lam=0.0, which=VARS_CURRENT):
         """b_r - E (C + lam I)^-1 b_e (nlls_schur_reduce)"""
         return self.ctx.schur_reduce(b, lam, which)

@@ -437,7 +437,8 @@ class HessianOperator:
 class SchurOperator:
     """v -> S(lam) v on the reduced unknowns of a linear system's CURRENT variables, evaluated on the device with every product (nlls_schur_apply): neither H nor S is
     held.  index: the positions of the reduced unknowns in the gradient; reduce / expand carry a right-hand side to the reduced system and a reduced solution back, so
-    that expand(b, S^-1 reduce(b)) solves (H + lam I) y = b; diag_blocks(): the diagonal blocks of B + lam I, a block-Jacobi preconditioner for S."""
+    that expand(b, S^-1 reduce(b)) solves (H + lam I) y = b; diag_blocks(): the diagonal blocks of B + lam I -- B's blocks, NOT S's: what "blockjacobi" inverts;
+    schur_diag_blocks(): the diagonal blocks of S(lam) itself (nlls_schur_block_diag), what "schurjacobi" inverts -- the preconditioner for a Krylov method of the caller's."""
 
     def __init__(self, ls, lam=0.0):
         self.ls = ls; self.lam = float(lam)
@@ -460,6 +461,9 @@ class SchurOperator:
     def diag_blocks(self):
         blocks = self.ls.hess_block_diag(self.lam, VARS_CURRENT)
         return [blk for blk, e in zip(blocks, self.is_elim) if not e]
+
+    def schur_diag_blocks(self):
+        return self.ls.schur_block_diag(self.lam, VARS_CURRENT)
 
 
 SINGLES_MAX_DOF = 12          # NLLS_SINGLES_MAX_DOF (include/nlls_amd.h)

@@ -14,7 +14,11 @@ Solver.operator at the same tolerance (tools/apply_only.py --cg; --no-host-cg sk
   --schur      nlls_solve_pcg_schur beside nlls_solve_pcg and nlls_solve, same context, same run: iterations, median wall time, synchronisations and launches of each, each
                one's distance to nlls_solve's step (the two iterations stop on different residuals -- the reduced system's and the full one's -- so compare them at the
                distance reached: --schur-rtols 1e-8,1e-12 adds runs of both at other tolerances), and the event pair around one nlls_schur_apply beside one
-               nlls_hess_apply.  The workload graph_leaves_2kx100k (a general graph: 2000 chained hubs, 100000 leaves on three hubs each, scalar unknowns) is for this mode
+               nlls_hess_apply.  The workload graph_leaves_2kx100k (a general graph: 2000 chained hubs, 100000 leaves on three hubs each, scalar unknowns) is for this mode.
+               Here --precond also takes schurjacobi (the diagonal blocks of S itself; nlls_solve_pcg beside it then runs under blockjacobi), and a comma list of the
+               three: then ONLY the table of the preconditioners is measured -- per preconditioner its set-up time (the median wall time of the call truncated at ONE
+               iteration: set-up, reduce, one product, expand -- the set-up is all that differs between the preconditioners), and per tolerance (--rtol and
+               --schur-rtols) the iterations, the total time and the distance to nlls_solve's step
   --tr F       nlls_solve_pcg_tr beside nlls_solve_pcg, same context, same run: first with radius +inf (the same iteration: its time per iteration against
                nlls_solve_pcg's), then at F times the M-norm of that converged step (a comma list measures each fraction): iterations, status, median wall time,
                synchronisations and launches of each"""
@@ -26,13 +30,18 @@ from nllssolver_jl_amd import synthetic, _capi
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--workload", default="ba_1kx100k", choices=("ba_100x10k", "ba_1kx100k", "ba_so3_500x50k", "ba_20x2k", "ba_10x200_fixed", "graph_leaves_2kx100k"))
-ap.add_argument("--lam", type=float, default=1e-3); ap.add_argument("--rtol", type=float, default=1e-10); ap.add_argument("--precond", default="blockjacobi", choices=("blockjacobi", "none"))
+ap.add_argument("--lam", type=float, default=1e-3); ap.add_argument("--rtol", type=float, default=1e-10); ap.add_argument("--precond", default="blockjacobi", metavar="NAME[,NAME..]",
+                help="blockjacobi | none; with --schur also schurjacobi, and a comma list of the three (then only the table of the preconditioners is measured)")
 ap.add_argument("--round", default=""); ap.add_argument("--repeats", type=int, default=7); ap.add_argument("--maxiters", type=int, default=0)
 ap.add_argument("--rhs", type=int, default=0); ap.add_argument("--cov", type=int, default=0)
 ap.add_argument("--schur", action="store_true"); ap.add_argument("--schur-rtols", default=""); ap.add_argument("--tr", default="")
 ap.add_argument("--no-schur", action="store_true"); ap.add_argument("--no-host-cg", action="store_true"); ap.add_argument("--host-cg-maxiter", type=int, default=2000)
 a = ap.parse_args()
 a.repeats = max(a.repeats, 7); unfixed = None
+preconds = a.precond.split(",")
+if not all(pc in ("blockjacobi", "none") or (a.schur and pc == "schurjacobi") for pc in preconds) or (len(preconds) > 1 and not a.schur):
+    ap.error("--precond %s: the names are blockjacobi and none; schurjacobi (the diagonal blocks of S) and a comma list need --schur, the reduced system" % a.precond)
+a.precond = preconds[0]; full_precond = "blockjacobi" if a.precond == "schurjacobi" else a.precond      # (the full system has no Schur-Jacobi)
 if a.workload == "ba_10x200_fixed":
     from nllssolver_jl_amd import kinds as K
     p = synthetic.perturb_ba_problem(synthetic.create_ba_problem(10, 200, 0.3, seed=3, robust=N.HuberKernel(0.002)), 1e-3, 1e-3)
@@ -103,9 +112,22 @@ with N.Solver(p, unfixed, flags=_capi.FLAG_NO_SCHUR if a.no_schur else 0) as s:
             return {"iterations": st["iterations"], "status": st["status"], "synchronisations": st["rounds"], "launches": st["launches"],
                     "relative_residual": st["rnorm"] / max(st["bnorm"], 1e-300), "wall_ms": float(np.median(ms[1:])), "wall_ms_all": [round(m, 3) for m in ms[1:]],
                     "distance_to_nlls_solve": float(np.max(np.abs(x - xs)) / np.max(np.abs(xs)))}
-        for rt in [a.rtol] + [float(v) for v in a.schur_rtols.split(",") if v]:
-            out["schur"][f"rtol_{rt:g}"] = {"nlls_solve_pcg": timed(lambda: ctx.solve_pcg(a.precond, maxiters, rt, want_x=True)),
+        rtols = [a.rtol] + [float(v) for v in a.schur_rtols.split(",") if v]
+        if len(preconds) > 1:
+            out["precond"] = preconds; table = out["schur"]["preconditioners"] = {}
+            for pc in preconds:
+                one = timed(lambda: ctx.solve_pcg_schur(pc, 1, a.rtol, want_x=True))
+                table[pc] = {"setup_ms": one["wall_ms"], "setup_ms_all": one["wall_ms_all"], "setup_launches": one["launches"]}
+                for rt in rtols:
+                    t = timed(lambda: ctx.solve_pcg_schur(pc, maxiters, rt, want_x=True))
+                    table[pc][f"rtol_{rt:g}"] = {k: t[k] for k in ("iterations", "status", "wall_ms", "wall_ms_all", "launches", "relative_residual", "distance_to_nlls_solve")}
+                    print(f"# {pc:12s} rtol {rt:g}: set-up {one['wall_ms']:.3f} ms, {t['iterations']} iterations, total {t['wall_ms']:.3f} ms", file=sys.stderr)
+            print(json.dumps(out)); sys.exit(0)
+        for rt in rtols:
+            out["schur"][f"rtol_{rt:g}"] = {"nlls_solve_pcg": timed(lambda: ctx.solve_pcg(full_precond, maxiters, rt, want_x=True)),
                                             "nlls_solve_pcg_schur": timed(lambda: ctx.solve_pcg_schur(a.precond, maxiters, rt, want_x=True))}
+        one = timed(lambda: ctx.solve_pcg_schur(a.precond, 1, a.rtol, want_x=True))
+        out["schur"]["setup_ms"] = one["wall_ms"]; out["schur"]["setup_launches"] = one["launches"]
         ts = []
         for _ in range(a.repeats + 1):
             t0 = time.perf_counter(); ctx.solve(); ts.append(1e3 * (time.perf_counter() - t0))
